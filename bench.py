@@ -2,7 +2,7 @@
 """
 bench.py -- fit-loop throughput of the MI355X-native differentiable-raster path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg1|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg1|cfg5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -20,6 +20,17 @@ views of one time-frame.  Inputs (mesh, blendshapes, texture, 8-bit reference im
 resident in HBM before the timed region.  Weak scaling: every rank owns 32 frames.
 
 Rank 0 prints ONE JSON line; see DESIGN.md section 6 for the roofline / cpu_baseline accounting.
+
+A plain run does only what the headline figure needs: set-up, `--warmup` steps, `--steps` timed steps, the result line (`value`,
+`ms_per_step` = wall-clock milliseconds of one timed step).  `--full` adds everything else the line has carried: the starting coverage,
+per-kernel HIP-event times inside the timed region (`kernels`, `roofline*`, from an extra eager pass when the steps replay HIP graphs), the
+stand-alone operator sweep and the drop-in path, the reference-shaped step and the CPU baseline (`--no-*` switch single legs off).
+`--dump-outputs DIR` writes what the last timed step computed -- the loss, the trainable parameters after the update, their gradients
+and the frames' vertices -- as DIR/<name>.npy (float32; a fixed strided sample of an array when the set exceeds 60 MB).
+The inputs (scene, rendered targets, starting parameters) are bit-identical from run to run, and every step, warm-up or timed, starts
+from the same state -- the starting parameters, zero Adam moments; a multi-tensor copy and a multi-tensor zero at the head of the step --:
+the gradients are summed with float atomics, and a chain of steps would carry their ordering noise (~1e-7) through the rasteriser's edges
+and Adam's per-element normalisation until two runs part.  So each step computes the same thing, and two runs agree to rounding.
 """
 import argparse
 import json
@@ -422,6 +433,45 @@ def cpu_baseline(sc, seconds_budget=30.0):
                       f"wall {time.perf_counter() - t0:.1f} s"}
 
 
+PARAM_NAMES = ("m1", "m2", "m3", "maps_local", "maps_intermediate_local", "t_opt", "q_opt", "per_frame_t", "per_frame_q", "tex_opt")   # Fitter.params
+DUMP_BUDGET_BYTES = 60_000_000
+
+
+def timed_path_outputs(fitter, loss):
+    """What a caller of Fitter.step holds after the last timed step: the loss it returned, the trainable parameters after the update,
+    their gradients and the vertices of this rank's frames (Fitter.result) -- host float32 arrays by name."""
+    out = {"loss": loss.detach().float().cpu().numpy()}
+    for name, p in zip(PARAM_NAMES, fitter.params):
+        if p.requires_grad:
+            out[name] = p.detach().float().cpu().numpy()
+            if p.grad is not None:
+                out["grad_" + name] = p.grad.detach().float().cpu().numpy()
+    out["result"] = fitter.result[fitter.frame_lo:fitter.frame_hi].detach().float().cpu().numpy()
+    return out
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES):
+    """DIR/<name>.npy for every array.  Over `budget` bytes in all, the smallest arrays are kept whole and each larger one is cut to an
+    equal share of what is left: a fixed strided sample of its flattened elements (stride and offset depend on the shape only)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > budget:
+        names = sorted(arrays, key=lambda k: arrays[k].nbytes)
+        left = budget
+        for i, k in enumerate(names):
+            a = arrays[k]
+            share = left // (len(names) - i)
+            if a.nbytes > share:
+                n = max(1, share // a.itemsize)
+                stride = -(-a.size // n)
+                offset = int(np.random.default_rng(a.size).integers(stride))
+                arrays[k] = a.reshape(-1)[offset::stride].copy()
+            left -= arrays[k].nbytes
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -433,12 +483,17 @@ def main():
     ap.add_argument("--early-tex-reduce", action="store_true",
                     help="all-reduce the texture gradient on its own as soon as the backward kernel has produced it (dist.EarlyReduce), "
                          "beside the rest of the backward pass; eager steps only")
-    ap.add_argument("--no-reference-shaped-step", action="store_true", help="skip the reference_shaped_step extra of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline figure: coverage, per-kernel times and rooflines, stand-alone operators, "
+                         "drop-in path, reference-shaped step, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, updated parameters, gradients, vertices) as DIR/<name>.npy")
+    ap.add_argument("--no-reference-shaped-step", action="store_true", help="skip the reference_shaped_step extra of a --full run")
     ap.add_argument("--frames-per-gpu", type=int, default=0)
     ap.add_argument("--channels", type=int, default=1)
     ap.add_argument("--mip", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the cpu_baseline extra of a --full run")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="no per-kernel HIP-event times in a --full run")
     ap.add_argument("--time-all-calls", action="store_true", help="HIP-event timing of every C-ABI call, not only the pixel kernels")
     ap.add_argument("--fill", type=float, default=0.0,
                     help="head height as a fraction of the image height (default: the scene generator's 0.6 = 11.5 %% of a 1080p frame covered)")
@@ -479,36 +534,58 @@ def main():
     H, W = fitter.resolution
     n_cam = len(fitter.cam_idxs)
     C = sc.texture.shape[2]
-    with torch.no_grad():       # covered share of the frame at the starting pose (the sparse objective's speed depends on it)
-        import fpc_diffrend_amd.ops as _dr
-        ids0 = slice(fitter.frame_lo, fitter.frame_lo + 1)
-        pos0 = fit.transform_clip_batched(fitter.mvp(ids0), fitter.vertices(ids0).reshape(1, -1, 3))
-        rast0, _ = _dr.rasterize(_dr.RasterizeGLContext(output_db=False, device=device), pos0, fitter.pos_idx, fitter.resolution)
-        coverage = float((rast0[..., 3] > 0).float().mean())
-        del rast0, pos0
+    coverage = None
+    if args.full:
+        with torch.no_grad():       # covered share of the frame at the starting pose (the sparse objective's speed depends on it)
+            import fpc_diffrend_amd.ops as _dr
+            ids0 = slice(fitter.frame_lo, fitter.frame_lo + 1)
+            pos0 = fit.transform_clip_batched(fitter.mvp(ids0), fitter.vertices(ids0).reshape(1, -1, 3))
+            rast0, _ = _dr.rasterize(_dr.RasterizeGLContext(output_db=False, device=device), pos0, fitter.pos_idx, fitter.resolution)
+            coverage = float((rast0[..., 3] > 0).float().mean())
+            del rast0, pos0
+
+    # every step -- warm-up and timed -- starts from the state the Fitter was built with (its parameters, zero Adam moments): a step's
+    # kernels accumulate gradients with float atomics (summation order varies, ~1e-7), and a trajectory would carry that into the next
+    # step's rasterisation and Adam's per-element normalisation until two runs part.  From the same state each step computes the same
+    # thing; the restore is one multi-tensor copy of the trainable tensors and one multi-tensor zero of the moments on the step's stream
+    # (in front of a graph replay too: the graphs read both in place)
+    start_params = [p.detach().clone() for p in fitter.params]
+
+    def step():
+        live = [(p, s) for p, s in zip(fitter.params, start_params) if p.requires_grad]
+        moments = [t for st in fitter.optimizer.state.values() for k, t in st.items() if k in ("exp_avg", "exp_avg_sq") and torch.is_tensor(t)]
+        with torch.no_grad():
+            torch._foreach_copy_([p for p, _ in live], [s for _, s in live])
+            if moments:
+                torch._foreach_zero_(moments)
+        return fitter.step()
 
     timer = None
-    if not args.no_kernel_timer:
+    if args.full and not args.no_kernel_timer:
         # inside the timed region only the entry points with per-pixel traffic are bracketed by HIP events (an event pair
         # costs the stream ~15 us; eleven calls per step would add 3 % to the step being measured); the small calls'
         # durations are in the rocprofv3 summaries under profiles/
         timer = _lib.KernelTimer(names=None if args.time_all_calls else algorithmic_bytes_per_px(1, False).keys())
     timer_steps = args.steps
-    if use_graph:
+    if use_graph and not args.full:
+        # the Fitter's own eager steps (GRAPH_WARMUP), one that fixes the parameter set, then capture + replay: all before the timed region
+        for _ in range(max(args.warmup, fitter.GRAPH_WARMUP + 2)):
+            step()
+    elif use_graph:
         # HIP events cannot be read back from inside a graph: the per-kernel durations come from an eager pass of the
         # same steps BEFORE the timed region (same kernels, same arguments); the timed region then replays the graphs
         fitter.use_graph = False
         timer_steps = max(args.steps, fitter.GRAPH_WARMUP)
         _lib.TIMER = timer
         for _ in range(timer_steps):
-            fitter.step()
+            step()
         _lib.TIMER = None
         fitter.use_graph = True
         for _ in range(max(args.warmup, 2)):      # one eager step that fixes the parameter set, then capture + replay
-            fitter.step()
+            step()
     else:
         for _ in range(args.warmup):
-            fitter.step()
+            step()
     torch.cuda.synchronize()
     fdist.barrier()
     torch.cuda.synchronize()
@@ -516,7 +593,7 @@ def main():
     t0 = time.perf_counter()
     loss = None
     for _ in range(args.steps):
-        loss = fitter.step()
+        loss = step()
     torch.cuda.synchronize()
     fdist.barrier()
     torch.cuda.synchronize()
@@ -524,6 +601,8 @@ def main():
     _lib.TIMER = None
     elapsed_local = elapsed
     elapsed = fdist.max_over_ranks(elapsed, device)
+    if args.dump_outputs and rank == 0 and loss is not None:
+        dump_outputs(args.dump_outputs, timed_path_outputs(fitter, loss))
 
     # a "frame" = all views of one time-frame; the ref workload renders ONE image (one view of one frame) per step and rank
     frames_step = 1 if args.workload == "ref" else fpg
@@ -544,7 +623,7 @@ def main():
                                   if args.workload == "cfg2" else
                                   f"textured C={C} + antialias fwd/bwd{' + mip' if args.mip else ''}, Adam on weights+pose+texture"
                                   + (" + free-form vertex offsets" if args.workload == "cfg5" else "")),
-                   "coverage": coverage, "frames_per_gpu": fpg, "views": n_cam, "resolution": [H, W], "triangles": int(sc.pos_idx.shape[0]),
+                   **({"coverage": coverage} if coverage is not None else {}), "frames_per_gpu": fpg, "views": n_cam, "resolution": [H, W], "triangles": int(sc.pos_idx.shape[0]),
                    "blendshapes": int(sc.blendshapes.shape[1]), "texture": list(sc.texture.shape),
                    "parallelism": (f"dp{world} (frames sharded, one RCCL all-reduce of {bucket.nbytes / 1e6:.1f} MB per step)" if world > 1
                                    else "one GPU, no collective")},
@@ -751,11 +830,11 @@ def main():
                     del ft_d
                 except Exception as e:
                     out["drop_in_path"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and args.workload in ("cfg3", "ref") and not args.no_reference_shaped_step:
+    if args.full and rank == 0 and world == 1 and args.workload in ("cfg3", "ref") and not args.no_reference_shaped_step:
         del fitter
         torch.cuda.empty_cache()
         out["reference_shaped_step"] = reference_shaped_step(device)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(sc)
         except Exception as e:  # the baseline must never take the measurement down

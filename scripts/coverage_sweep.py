@@ -7,7 +7,7 @@ import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 points = []
 for fill in (0.6, 1.37, 2.45):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--fill", str(fill), "--steps", "10", "--warmup", "3", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--fill", str(fill), "--steps", "10", "--warmup", "3", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=600)
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
     if not line:
