@@ -15,7 +15,7 @@ MAX_ATTR = 32
 MAX_MIP = 16
 LOSS_SLOTS = 256
 OCC_BIN = 32         # FPCDR_OCC_BIN
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 FILTER = {'nearest': 0, 'linear': 1, 'linear-mipmap-nearest': 2, 'linear-mipmap-linear': 3}
 BOUNDARY = {'wrap': 0, 'clamp': 1, 'zero': 2}
@@ -130,7 +130,8 @@ class AdamTensor(ctypes.Structure):
 class AdamParams(ctypes.Structure):
     _fields_ = [("n_tensors", _i), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
                 ("one_minus_beta1", ctypes.c_float), ("one_minus_beta2", ctypes.c_float), ("t", AdamTensor * ADAM_MAX_TENSORS),
-                ("step_table", _p), ("skip_flag", _p), ("skipped", _p), ("lr_skip_gain", ctypes.c_double)]
+                ("step_table", _p), ("skip_flag", _p), ("skipped", _p), ("lr_skip_gain", ctypes.c_double),
+                ("skipped_per_tensor", _p), ("beta1_f64", ctypes.c_double), ("beta2_f64", ctypes.c_double)]
 
 
 # every symbol include/fpcdr.h declares: name -> (restype, argtypes)

@@ -544,18 +544,23 @@ class GroupedAdam(torch.optim.Optimizer):
         self.capturable = bool(capturable)
         self._table_host = self._table_dev = None
         self._ring, self._ring_i = [], 0
-        # steps skipped on the device (fpcdr_adam_params.skip_flag / skipped, include/fpcdr.h ABI v11): `skip_flag` is a one-element float32
-        # device tensor the launch reads -- non-zero: this step's gradients are invalid, touch nothing --, set by the caller before every
-        # step() (None: never skip); `skipped` the device counter the kernel keeps; `lr_skip_gain` = lr(i - 1) / lr(i) of the schedule
+        # steps skipped on the device (fpcdr_adam_params.skip_flag / skipped / skipped_per_tensor, include/fpcdr.h ABI v11, v12): `skip_flag`
+        # is a one-element float32 device tensor the launch reads -- non-zero: this step's gradients are invalid, touch nothing --, set by
+        # the caller before every step() (None: never skip); `skipped` the device counter of skipped steps the kernel keeps, and
+        # `skipped_per_tensor` its count per tensor (by position in the optimiser, _rows) of the skipped steps in which that tensor had a
+        # gradient: those its state['step'] counted and its update never took; `lr_skip_gain` = lr(i - 1) / lr(i) of the schedule.  (The
+        # counters stay out of self.state: it holds torch.optim.Adam's keys only)
         self.skip_flag = None
         self.skipped = None
+        self.skipped_per_tensor = None
         self.lr_skip_gain = 1.0
 
     def enable_skips(self, lr_skip_gain=1.0):
-        """Allocate the device counter of skipped steps (see __init__); returns it."""
+        """Allocate the device counters of skipped steps (see __init__); returns the global one."""
         if self.skipped is None:
             dev = self.param_groups[0]['params'][0].device
             self.skipped = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.skipped_per_tensor = torch.zeros(_lib.ADAM_MAX_TENSORS, dtype=torch.int32, device=dev)
         self.lr_skip_gain = float(lr_skip_gain)
         return self.skipped
 
@@ -641,11 +646,13 @@ class GroupedAdam(torch.optim.Optimizer):
             keep.append(self.skip_flag)
             if self.skipped is not None:
                 P.skipped, P.lr_skip_gain = self.skipped.data_ptr(), self.lr_skip_gain
+                P.skipped_per_tensor = self.skipped_per_tensor.data_ptr()
         for g in self.param_groups:
             b1, b2 = g['betas']
             assert (b1, b2, g['eps']) == (self.param_groups[0]['betas'] + (self.param_groups[0]['eps'],)), \
                 "one launch takes one (betas, eps) for all groups"
             P.beta1, P.beta2, P.eps, P.one_minus_beta1, P.one_minus_beta2 = b1, b2, g['eps'], 1.0 - b1, 1.0 - b2
+            P.beta1_f64, P.beta2_f64 = b1, b2
             for p in g['params']:
                 row += 1
                 ren = id(p) in self._renorm
@@ -1244,6 +1251,12 @@ class Fitter:
         sk = getattr(self.optimizer, "skipped", None)
         return int(sk.item()) if sk is not None else 0
 
+    def skipped_steps_per_tensor(self):
+        """Per parameter tensor (self.params order): the skipped steps in which it had a gradient -- its state['step'] counted them, its
+        update did not (a host read-back)."""
+        sk = getattr(self.optimizer, "skipped_per_tensor", None)
+        return [int(v) for v in sk[:len(self.params)].tolist()] if sk is not None else [0] * len(self.params)
+
     def _update(self, prepared=False):
         if isinstance(self.optimizer, GroupedAdam) and self.optimizer.capturable and not prepared:
             self.optimizer.prepare()      # (an eager step of a graph-mode Fitter: warm-up, or a new set of trainable tensors)
@@ -1395,7 +1408,8 @@ class Fitter:
                 "requires_grad": [bool(p.requires_grad) for p in self.params],
                 "optimizer": self.optimizer.state_dict(), "scheduler": self.scheduler.state_dict(),
                 "iteration": self.iteration, "rng": self.rng.bit_generator.state,
-                "skipped_steps": self.skipped_steps,      # (device-side skips: the update kernel subtracts them from the step counters)
+                "skipped_steps": self.skipped_steps,      # (device-side skips: the update kernel subtracts them from the step counters,
+                "skipped_per_tensor": self.skipped_steps_per_tensor(),      # each tensor its own; the schedule the total)
                 "result": self.result.clone(),      # this rank's rows (others zero): checkpoints are per rank
                 "frame_range": (self.frame_lo, self.frame_hi),
                 "config": dict(self.cfg.__dict__)}
@@ -1406,14 +1420,64 @@ class Fitter:
                 p.copy_(v.to(p.device))
         for p, rg in zip(self.params, state["requires_grad"]):
             p.requires_grad = rg
-        self.optimizer.load_state_dict(state["optimizer"])
+        self._load_optimizer(state["optimizer"])
         self.scheduler.load_state_dict(state["scheduler"])
         self.iteration = int(state["iteration"])
+        total = int(state.get("skipped_steps", 0))
+        per = state.get("skipped_per_tensor")
+        if per is None:      # (a checkpoint from before the per-tensor counts: the global count for every tensor with state, as the old kernel had it)
+            per = [total if 'step' in self.optimizer.state.get(p, {}) else 0 for p in self.params]
+        per = [int(v) for v in per]
+        assert len(per) == len(self.params) and all(0 <= v <= total for v in per), (per, total)
         if getattr(self.optimizer, "skipped", None) is not None:
-            self.optimizer.skipped.fill_(int(state.get("skipped_steps", 0)))
+            self.optimizer.skipped.fill_(total)
+            self.optimizer.skipped_per_tensor.zero_()
+            self.optimizer.skipped_per_tensor[:len(per)].copy_(torch.tensor(per, dtype=torch.int32))
+        elif total > 0:
+            self._forget_skips(total, per)
         self.rng.bit_generator.state = state["rng"]
         self.result.copy_(state["result"].to(self.result.device))
         self._graphs, self._graph_key = None, None
+
+    def _load_optimizer(self, sd):
+        """torch's Optimizer.load_state_dict replaces every param_group by the checkpoint's: a GroupedAdam checkpoint carries lr / betas /
+        eps only, and torch.optim.Adam's groups also hold its implementation switches (fused, capturable, weight_decay, ...) -- a checkpoint
+        of one kind left the other without them.  The groups keep this optimiser's own keys and take the checkpoint's values of the
+        optimisation state (learning rates, betas, eps); a device learning rate (graph mode) stays the device tensor the update reads."""
+        taken = ("lr", "initial_lr", "betas", "eps")
+        groups = []
+        for g, ng in zip(self.optimizer.param_groups, sd["param_groups"]):
+            m = {k: v for k, v in g.items() if k != "params"}
+            for k in taken:
+                if k not in ng:
+                    continue
+                if torch.is_tensor(m.get(k)):
+                    m[k].fill_(float(ng[k]))
+                else:
+                    m[k] = float(ng[k]) if torch.is_tensor(ng[k]) else ng[k]
+            m["params"] = ng["params"]
+            groups.append(m)
+        assert len(groups) == len(sd["param_groups"]) == len(self.optimizer.param_groups)
+        self.optimizer.load_state_dict({"state": sd["state"], "param_groups": groups})
+
+    def _forget_skips(self, total, per):
+        """A checkpoint of a run that skipped steps on the device, loaded into an optimiser that cannot (capturable GroupedAdam,
+        torch.optim.Adam): its step counters and schedule become those of the run that never drew the skipped steps -- what the update
+        kernel formed for them (include/fpcdr.h, fpcdr_adam_params.skipped).  Each tensor's step count loses its own skips, the scheduler's
+        epoch the total, and the groups' current learning rates (device tensors in graph mode) follow the epoch."""
+        for p, k in zip(self.params, per):
+            st = self.optimizer.state.get(p, {})
+            if k and 'step' in st:
+                st['step'] = st['step'] - k
+        sch = self.scheduler
+        sch.last_epoch -= total
+        lrs = [base * lmbda(sch.last_epoch) for base, lmbda in zip(sch.base_lrs, sch.lr_lambdas)]
+        for g, lr in zip(self.optimizer.param_groups, lrs):
+            if torch.is_tensor(g['lr']):
+                g['lr'].fill_(float(lr))
+            else:
+                g['lr'] = lr
+        sch._last_lr = [g['lr'].clone() if torch.is_tensor(g['lr']) else g['lr'] for g in self.optimizer.param_groups]
 
     def save_checkpoint(self, path):
         torch.save(self.state_dict(), path)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define FPCDR_ABI_VERSION 11
+#define FPCDR_ABI_VERSION 12
 
 enum {
     FPCDR_OK = 0,
@@ -464,9 +464,10 @@ typedef struct {
                               the first bias correction, divided in double precision as torch does */
     float bc2_sqrt;        /* sqrt(1 - beta2^step) */
     int32_t renorm;
-    int32_t table_row;     /* ABI v10, with fpcdr_adam_params.step_table: this tensor's row of the table (step_size / bc2_sqrt above unused) */
+    int32_t table_row;     /* ABI v10, with fpcdr_adam_params.step_table: this tensor's row of the table (step_size / bc2_sqrt above unused);
+                              ABI v12, with fpcdr_adam_params.skipped: its entry of skipped_per_tensor */
     /* ABI v11, with fpcdr_adam_params.skipped: what step_size / bc2_sqrt were formed from -- the tensor's step count (this step included)
-     * and its learning rate --, so that the kernel can re-form them for step - *skipped once a step has been skipped */
+     * and its learning rate --, so that the kernel can re-form them for the steps that were not skipped */
     int32_t step;
     float lr;
 } fpcdr_adam_tensor;
@@ -484,13 +485,24 @@ typedef struct {
      *            quaternion division) -- fpcdr_objective_params.skip_out, summed over the ranks
      * skipped    optional DEVICE [1] counter of the steps skipped so far, kept by this kernel (+1 per skipped launch).  The host's step
      *            counters and learning-rate schedule have moved on regardless: with *skipped = s > 0 (and no step_table) the kernel forms
-     *            step_size = lr * lr_skip_gain^s / (1 - beta1^(step - s)) and bc2_sqrt = sqrt(1 - beta2^(step - s)) itself, in double,
-     *            i.e. the update of the run that never drew the skipped steps
+     *            step_size = lr * lr_skip_gain^s / (1 - beta1_f64^(step - s_t)) and bc2_sqrt = sqrt(1 - beta2_f64^(step - s_t)) itself,
+     *            in double,
+     *            i.e. the update of the run that never drew the skipped steps (s_t: skipped_per_tensor below)
      * lr_skip_gain  lr(i - 1) / lr(i) of the caller's schedule (1 for a constant rate; the reference's lr_ramp^(i / max_iter) decays by
-     *            a constant factor per step, fit.py:506-507) */
+     *            a constant factor per step, fit.py:506-507)
+     * ABI v12:
+     * skipped_per_tensor  DEVICE [FPCDR_ADAM_MAX_TENSORS], required with `skipped`: s_t = skipped_per_tensor[t[i].table_row], the skipped
+     *            launches in which tensor i HAD a gradient (the steps its host counter took and its update never did), kept by this kernel.
+     *            The bias corrections come off the tensor's own count: a tensor that starts training after a skip (the learned basis of
+     *            the combined mode) has step <= s, and step - s would be a zero or negative step count.  The learning rate keeps the
+     *            global s: the schedule is shared by all groups.  With `skipped`, the tensors' table_rows must be distinct
+     * beta1_f64, beta2_f64  required with `skipped`: the betas in double precision, as the caller's own bias corrections use them
+     *            (1 - (double)0.999f is 1.3e-5 away from 1 - 0.999: the first re-formed updates would be 6e-6 off torch's) */
     const float *skip_flag;
     int32_t *skipped;
     double lr_skip_gain;
+    int32_t *skipped_per_tensor;
+    double beta1_f64, beta2_f64;
 } fpcdr_adam_params;
 int fpcdr_adam_step(const fpcdr_adam_params *p, void *stream);
 

@@ -8,20 +8,27 @@ import numpy as np
 import pytest
 import torch
 
+from adam_ref import AdamRef
+from helpers import rel_l2
+
 pytestmark = pytest.mark.gpu
+
+RENORM = (6, 8)      # q_opt, per_frame_q: the reference's whole-tensor division (fit.py:616-618)
 
 
 def _onepass_hints(dr):
     return dr._list_hints[next(k for k in dr._list_hints if k[0] == 'onepass')]
 
 
-def _make(targets=None):
+def _make(targets=None, **kw):
     from fpc_diffrend_amd import fit, scene
     sc = scene.cfg('cfg1', n_frames=2)
     sc.q_gt[:] = (0.0, 0.0, 0.0, 1.0)
     # max_iter = 40: LambdaLR's lr_ramp^(i / max_iter) falls by 12 % per step -- a skipped step that left the schedule one step ahead
     # would show at once
-    cfg = fit.FitConfig(max_iter=40, cam_idxs=(0, 3, 6), lr_base=5e-3, lr_t=5e-3, lr_q=1e-5, weight_laplacian=40.0, init_texture='truth')
+    hp = dict(max_iter=40, cam_idxs=(0, 3, 6), lr_base=5e-3, lr_t=5e-3, lr_q=1e-5, weight_laplacian=40.0, init_texture='truth')
+    hp.update(kw)
+    cfg = fit.FitConfig(**hp)
     ft = fit.Fitter(sc, cfg, device='cuda', targets=targets)
     ft.init_near_truth(0.8)
     return ft
@@ -174,4 +181,134 @@ def test_a_caller_without_skip_out_still_learns_of_the_overflow(monkeypatch):
     assert math.isnan(run(skip_out=flag)) and float(flag) == 1.0
     h.frozen = False
     assert abs(run(skip_out=flag) - good) <= 1e-6 * abs(good) and float(flag) == 0.0
+    dr.clear_hints()
+
+
+def _short_step(ft, dr):
+    """One step whose pixel objective runs out of record slots: skipped on the device."""
+    h = _onepass_hints(dr)
+    h.poll()
+    h.slots, h.frozen = 1, True
+    bad = ft.step()
+    h.frozen = False
+    assert math.isnan(float(bad))
+
+
+def _lrs(ft, it, skipped):
+    """The group learning rates of iteration `it` in the run that never drew the `skipped` steps before it (reference fit.py:506-507)."""
+    cfg = ft.cfg
+    return [b * cfg.lr_ramp ** ((it - skipped) / cfg.max_iter) for b in ft.scheduler.base_lrs]
+
+
+def _checked_step(ft, ref, skipped, tol=2e-6):
+    """One step of the Fitter and the float64 reference's update from the gradients that step left on the parameters (the way
+    test_optimiser_steps_match_oracle (A) reads them); every parameter must be finite and equal the reference."""
+    it = ft.iteration
+    for p in ft.params:
+        p.grad = None
+    loss = float(ft.step())
+    assert math.isfinite(loss), (it, loss)
+    ref.update([p.grad.detach().clone() if p.grad is not None else None for p in ft.params], _lrs(ft, it, skipped))
+    for k, p in enumerate(ft.params):
+        assert bool(torch.isfinite(p).all()), f"iteration {it}: parameter {k} has non-finite values"
+        e = rel_l2(p, ref.p[k])
+        assert e <= tol, (it, k, e)
+    return loss
+
+
+def test_combined_mode_switch_after_a_skip_trains_the_learned_basis_from_its_own_step_count(tmp_path, monkeypatch):
+    """Combined mode (cfg5's) switches the learned basis m1 / m2 / m3 on half way (fit.py:603-608): their FIRST update comes after a step
+    skipped on the device.  Their own step counts hold no skip, so the update is Adam's first step for them -- the global skip count taken
+    off their counters made it a step count of 0 (infinite step size) and the parameters NaN.  After every step that was not skipped the
+    parameters equal the float64 reference of the run that never drew the skipped step; a checkpoint written between the skip and the
+    switch resumes into the same run."""
+    import fpc_diffrend_amd.ops as dr
+    dr.clear_hints()
+    monkeypatch.setattr(dr, "SMALL_BATCH_BINS", 0)
+    monkeypatch.setattr(dr, "RECORD_SLOT_MARGIN", 1)
+    ft = _make(mode='combined', max_iter=6)        # the learned basis receives its first gradient in iteration 5
+    ref = AdamRef(ft.params, renorm=RENORM)
+    for _ in range(2):
+        _checked_step(ft, ref, 0)
+    assert all(p.grad is None for p in ft.params[:3])
+    _short_step(ft, dr)                            # iteration 2
+    assert ft.skipped_steps == 1
+    _checked_step(ft, ref, 1)                      # iteration 3
+    ft.save_checkpoint(str(tmp_path / "before_switch.pt"))
+    for _ in range(4):                             # iterations 4 .. 7: the switch, the basis's first updates
+        _checked_step(ft, ref, 1)
+    assert ft.skipped_steps == 1
+    assert all(ref.step[k] == 3 for k in range(3)) and all(ref.step[k] == 7 for k in range(3, 10))
+    assert [int(ft.optimizer.state[p]['step']) for p in ft.params] == [3] * 3 + [8] * 7
+    assert ft.skipped_steps_per_tensor() == [0] * 3 + [1] * 7
+    # resumed from the checkpoint between the skip and the switch: the uninterrupted run
+    b = _make(targets=ft.targets, mode='combined', max_iter=6)
+    b.load_checkpoint(str(tmp_path / "before_switch.pt"))
+    assert b.skipped_steps == 1 and b.skipped_steps_per_tensor() == [0] * 3 + [1] * 7
+    for _ in range(4):
+        assert math.isfinite(float(b.step()))
+    assert b.iteration == ft.iteration and b.skipped_steps == 1
+    _close(ft, b, steps_apart=4)
+    dr.clear_hints()
+
+
+def test_checkpoint_without_per_tensor_skip_counts_loads_as_before(tmp_path, monkeypatch):
+    """A checkpoint written before the per-tensor skip counts (no 'skipped_per_tensor') takes the global count for every tensor with
+    optimiser state -- what the update kernel assumed then -- and continues exactly as the same checkpoint with the counts."""
+    import fpc_diffrend_amd.ops as dr
+    dr.clear_hints()
+    monkeypatch.setattr(dr, "SMALL_BATCH_BINS", 0)
+    monkeypatch.setattr(dr, "RECORD_SLOT_MARGIN", 1)
+    a = _make()
+    a.step()
+    _short_step(a, dr)
+    a.step()
+    a.save_checkpoint(str(tmp_path / "ck.pt"))
+    state = torch.load(str(tmp_path / "ck.pt"), weights_only=False)
+    assert state["skipped_steps"] == 1 and state["skipped_per_tensor"] == [0] * 3 + [1] * 7
+    del state["skipped_per_tensor"]
+    torch.save(state, str(tmp_path / "legacy.pt"))
+    new, old = _make(targets=a.targets), _make(targets=a.targets)
+    new.load_checkpoint(str(tmp_path / "ck.pt"))
+    old.load_checkpoint(str(tmp_path / "legacy.pt"))
+    assert old.skipped_steps == 1 and old.skipped_steps_per_tensor() == new.skipped_steps_per_tensor() == [0] * 3 + [1] * 7
+    want = [float(new.step()) for _ in range(3)]
+    got = [float(old.step()) for _ in range(3)]
+    assert np.allclose(got, want, rtol=1e-5), (got, want)
+    _close(old, new, steps_apart=3)
+    dr.clear_hints()
+
+
+@pytest.mark.parametrize("kind", ["hip_graph", "torch_adam"])
+def test_checkpoint_with_skips_into_an_optimiser_that_cannot_skip(tmp_path, monkeypatch, kind):
+    """A checkpoint of a run that skipped a step, loaded into a Fitter whose optimiser has no device skip counter (graph mode's capturable
+    GroupedAdam; torch.optim.Adam): the skipped step becomes one never drawn -- each tensor's step count loses its skips, the schedule
+    the total -- and the next step equals the float64 reference update of the checkpoint's state with that step's own gradients."""
+    import fpc_diffrend_amd.ops as dr
+    dr.clear_hints()
+    monkeypatch.setattr(dr, "SMALL_BATCH_BINS", 0)
+    monkeypatch.setattr(dr, "RECORD_SLOT_MARGIN", 1)
+    a = _make()
+    a.step()
+    _short_step(a, dr)
+    a.step()
+    a.step()
+    a.save_checkpoint(str(tmp_path / "ck.pt"))
+    state = torch.load(str(tmp_path / "ck.pt"), weights_only=False)
+    per, it = state["skipped_per_tensor"], state["iteration"]
+    assert state["skipped_steps"] == 1 and per == [0] * 3 + [1] * 7 and it == 4
+    monkeypatch.undo()                             # (the new Fitter runs with the default record pool)
+    dr.clear_hints()
+    b = _make(targets=a.targets, **(dict(hip_graph=True) if kind == "hip_graph" else dict(grouped_adam=False)))
+    b.load_checkpoint(str(tmp_path / "ck.pt"))
+    assert b.skipped_steps == 0 and b.scheduler.last_epoch == it - 1
+    ref = AdamRef(b.params, renorm=RENORM)
+    for k, p in enumerate(b.params):
+        st = state["optimizer"]["state"].get(k)
+        if st is not None:
+            ref.load(k, p, st["exp_avg"], st["exp_avg_sq"], int(st["step"]) - per[k])
+            assert int(b.optimizer.state[p]["step"]) == ref.step[k]
+    assert all(abs(float(g["lr"]) - lr) <= 1e-12 * lr for g, lr in zip(b.optimizer.param_groups, _lrs(b, it, 1)))
+    _checked_step(b, ref, 1)
+    assert [int(b.optimizer.state[p]["step"]) for p in b.params[3:]] == ref.step[3:] == [4] * 7
     dr.clear_hints()
