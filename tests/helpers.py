@@ -32,6 +32,14 @@ def scene_mvps(sc, cam_ids, frames=None):
     return torch.tensor(np.stack(out))
 
 
+def scene_cameras(sc, cam_ids):
+    """(proj [Nc,4,4], t_mv [Nc,4,4]) float32 of the scene's cameras, made as scene_mvps makes them (translation 170 included)."""
+    T = camera.translate(0.0, 170.0, 0.0)
+    proj = [camera.intrinsic_to_projection(sc.cams[c]['intr']) for c in cam_ids]
+    mv = [(camera.extrinsic_to_modelview(sc.cams[c]['rot'], sc.cams[c]['trans_calib']) @ T).astype(np.float32) for c in cam_ids]
+    return torch.tensor(np.stack(proj)), torch.tensor(np.stack(mv))
+
+
 def clip_positions(sc, cam_ids, frames=None, jitter=0.0, seed=0):
     """pos_clip [B,V,4] for the base mesh (+ blendshape ground truth per frame)."""
     mvps = scene_mvps(sc, cam_ids, frames)

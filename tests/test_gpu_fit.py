@@ -125,6 +125,13 @@ def test_pixel_loss_fused_equals_reference_chain():
     s, grad = fit.pixel_loss_fused(colour, rast, ref)
     assert abs(float(s[0]) / colour.numel() - float(loss)) < 1e-3 * float(loss)
     assert rel_l2(grad, colour.grad) < 1e-6
+    # the value as a long sum (tests/test_gpu_fitstep.py): against float64 on the CPU, in units of u = 2^-24 of the sum of the absolute
+    # values of its terms, at most 8 x the error of float32 torch on the CPU + 4
+    import fitstep_ref as R
+    r64 = R.pixel_loss(colour, rast[..., 3], ref)['sum']
+    r32 = R.pixel_loss(colour, rast[..., 3], ref, dtype=torch.float32)['sum']
+    e_gpu, e32 = R.measure(s.reshape(()), *r64)[0], R.measure(r32[0], *r64)[0]
+    assert e_gpu <= 8 * e32 + 4, (e_gpu, e32)
 
 
 def test_smoke_step_matches_oracle(oracle_ops):
@@ -304,7 +311,10 @@ def test_laplacian_gather_form_matches_dense():
 
 
 def test_laplacian_penalty_one_launch_matches_the_torch_chain():
-    """fit.laplacian_penalty (fpcdr_laplacian_penalty_fwd / _bwd: value by the last workgroup, transposed gather of the normalised
+    """(Both sides of this comparison run ring_sum() of csrc/clip.hip -- fit.mesh_laplacian_smoothing goes through fpcdr_laplacian_gather --
+    so it shows that two users of that function agree, not that the function is right: the independent check, against a float64 Laplacian
+    built from the face list, is tests/test_gpu_fitstep.py.)
+    fit.laplacian_penalty (fpcdr_laplacian_penalty_fwd / _bwd: value by the last workgroup, transposed gather of the normalised
     Laplacian) == weight * mean_f mesh_laplacian_smoothing(mesh f)^2 through the gather kernel and torch, value and gradient; with
     an upstream factor, with vertices whose Laplacian is exactly zero (a flat regular patch: torch's norm passes 0 there), for one
     mesh and for several, and twice in a row (the call leaves its accumulators zeroed)."""
@@ -783,7 +793,10 @@ def test_reference_run_shape_one_random_view_per_step(fused):
 def test_laplacian_penalty_eager_gradient_heavy_rings_and_second_stream():
     """(i) eager_grad=True (the gradient kernel runs with the value; backward() hands the buffer over, times the upstream scalar unless
     unit_upstream) == the lazy form, on the current stream and on a second one; (ii) a fan whose hub has 200 neighbours -- rings beyond
-    eight slots are finished by the whole wave, here in four rounds of 64 slots -- against the torch chain, value and gradient."""
+    eight slots are finished by the whole wave, here in four rounds of 64 slots -- against the torch chain, value and gradient.
+    (That chain, fit.mesh_laplacian_smoothing, runs the same ring_sum() of csrc/clip.hip through fpcdr_laplacian_gather: the fan case compares
+    two users of that function with each other.  The independent check of the whole-wave path, against a float64 Laplacian built from the
+    face list, is tests/test_gpu_fitstep.py.)"""
     from fpc_diffrend_amd import fit, scene
     sc = scene.cfg('cfg1', n_frames=3)
     topo = fit.MeshTopology(sc.pos_idx, sc.n_vertices, 'cuda')
