@@ -216,6 +216,10 @@ __device__ __forceinline__ void binlist_append_global(int32_t *__restrict__ bin_
         }
 }
 
+// A position that has been gathered stays gathered: the empty statement makes the four components live in vector registers HERE, so the
+// compiler can neither split the 16-byte load into the pieces each later use wants, nor sink it behind a branch, nor fetch it again.
+__device__ __forceinline__ void pin_loaded(float4 &v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
+
 // SIL: the thread also classifies its triangle's three edges for the antialias step (sil_bits.h) -- it holds the triangle's own three
 // vertices already, the three across the edges are gathered beside them (the stand-alone kernel, k_sil2, is 62 us at 288 x 30 k of
 // which this form leaves ~10: the same chain of index load -> position gather, walked once instead of twice).
@@ -249,29 +253,41 @@ __global__ void __launch_bounds__(256) k_setup(const float4 *__restrict__ pos, c
     if (t < T) {
         const size_t gid = img_slot + t;
         TriBox box = {1, 1, 0, 0};
-        int i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
-        bool ok = !(i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V);
+        // TWO ROUND TRIPS, NOT EIGHT (profiles/setup_load_chain.txt).  The kernel is a chain of dependent loads -- half its issue slots
+        // idle at full occupancy -- and the compiler, left alone, lengthens the chain: it fetched the adjacency triple only after the
+        // vertex triple had passed its test, x / y / w of the six vertices for the silhouette bits, w of the own three again for the
+        // w > 0 test, and sank each vertex's x, y, z into the iteration of setup_piece that uses it.  So: (1) both index triples at once
+        // -- t < T is all they need; (2) the six positions (three without SIL), each ONE 16-byte load, all in flight before the first
+        // use and pinned below so that none is split, sunk or fetched again.  A hoisted load runs for triangles the tests below reject:
+        // an index that is invalid or unused reads vertex 0, as in sil_classify -- no load ever leaves the table.
+        const int i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
+        int ad[3] = {-1, -1, -1};
+        if (SIL) { ad[0] = adj[3 * t]; ad[1] = adj[3 * t + 1]; ad[2] = adj[3 * t + 2]; }
+        // (index validity only decides the silhouette bits, as in sil_classify: `ok` may also carry the range test)
+        const bool vok = !(i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V);
+        bool ok = vok;
         if (ranges) {      // range mode: the image renders its own slice of the triangle list
             const long long first = ranges[2 * b], count = ranges[2 * b + 1];
             ok = ok && t >= first && t < first + count;
         }
-        if (SIL) {      // (index validity only decides, as in sil_classify: `ok` below may also carry the range test)
-            const bool vok = !(i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V);
-            unsigned int bits = 0;
-            if (vok) {
-                const int ad[3] = {adj[3 * t], adj[3 * t + 1], adj[3 * t + 2]};
-                const float4 *p = pos + (size_t)b * V;
-                const float4 o0 = ld32(p, (ad[0] >= 0 && ad[0] < V) ? (unsigned int)ad[0] : 0u);
-                const float4 o1 = ld32(p, (ad[1] >= 0 && ad[1] < V) ? (unsigned int)ad[1] : 0u);
-                const float4 o2 = ld32(p, (ad[2] >= 0 && ad[2] < V) ? (unsigned int)ad[2] : 0u);
-                bits = sil_bits_of(p[i0], p[i1], p[i2], o0, o1, o2, ad, V, 0.5f * (float)W, 0.5f * (float)H);
-            }
+        const float4 *p = pos + (size_t)b * V;
+        float4 v0 = ld32(p, vok ? (unsigned int)i0 : 0u);      // (kept as scalars: an array handed to the out-of-line clipper would
+        float4 v1 = ld32(p, vok ? (unsigned int)i1 : 0u);      //  live in scratch memory on the common path too)
+        float4 v2 = ld32(p, vok ? (unsigned int)i2 : 0u);
+        float4 o0 = v0, o1 = v0, o2 = v0;
+        if (SIL) {
+            o0 = ld32(p, (ad[0] >= 0 && ad[0] < V) ? (unsigned int)ad[0] : 0u);
+            o1 = ld32(p, (ad[1] >= 0 && ad[1] < V) ? (unsigned int)ad[1] : 0u);
+            o2 = ld32(p, (ad[2] >= 0 && ad[2] < V) ? (unsigned int)ad[2] : 0u);
+        }
+        pin_loaded(v0); pin_loaded(v1); pin_loaded(v2);
+        if (SIL) {
+            pin_loaded(o0); pin_loaded(o1); pin_loaded(o2);
+            const unsigned int bits = vok ? sil_bits_of(v0, v1, v2, o0, o1, o2, ad, V, 0.5f * (float)W, 0.5f * (float)H) : 0u;
             sil[(size_t)b * T + t] = (uint8_t)bits;
         }
         if (ok) {
-            const float4 *p = pos + (size_t)b * V;
-            const float4 v0 = p[i0], v1 = p[i1], v2 = p[i2];      // (kept as scalars: an array handed to the out-of-line clipper would
-            TriRec r;                                             // live in scratch memory on the common path too)
+            TriRec r;
             if (v0.w > 0.0f && v1.w > 0.0f && v2.w > 0.0f) {      // (R1) the usual case: the triangle as it is
                 const double vd[3][4] = {{(double)v0.x, (double)v0.y, (double)v0.z, (double)v0.w},
                                          {(double)v1.x, (double)v1.y, (double)v1.z, (double)v1.w},

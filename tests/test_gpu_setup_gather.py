@@ -1,0 +1,224 @@
+"""The set-up kernel's hoisted loads (rasterize.hip, k_setup): both index triples are read before any validity test and the six positions
+are gathered before the first use, so the loads run for triangles the earlier code never touched.  This file pins the guards: invalid
+vertex indices (-1 and V, one element outside the table), adjacency entries of -1, T + 5 and valid values, one triangle with a vertex at
+w <= 0, one image in range mode -- through fpcdr_rasterize_fwd and fpcdr_objective_fwd, by ctypes.  Every comparison is exact.
+
+The position table is a slice of a larger tensor whose tail holds visible, in-image vertices: a load that leaves the table by the
+offsets used here (element V of the last image, element T + 5) stays inside the allocation and returns a WRONG ANSWER, not a fault."""
+import ctypes
+
+import pytest
+import torch
+
+from helpers import decode_id_planes
+
+pytestmark = pytest.mark.gpu
+
+H, W, B, N = 64, 64, 2, 10
+RES = (H, W)
+BAD = {7: (0, -1), 50: (2, 'V'), 120: (0, -1), 199: (1, 'V')}      # triangle -> (corner, index); 120 gets a second one below
+RANGE = (40, 100)                                                  # image 1 of the range-mode call: triangles [40, 140)
+
+
+def _mesh():
+    """A jittered (N + 1)^2 grid of 2 N^2 = 200 triangles over the image, per-image depth and w, plus one triangle that crosses w = 0.
+    Returns CPU tensors: pos [B,V,4], tri [T,3] (with the invalid entries), adj [T,3] (corrupted likewise), valid [T] bool."""
+    g = torch.Generator().manual_seed(77)
+    n1 = N + 1
+    gy, gx = torch.meshgrid(torch.arange(n1, dtype=torch.float32), torch.arange(n1, dtype=torch.float32), indexing='ij')
+    xy = torch.stack([gx, gy], -1).reshape(-1, 2) / N * 1.7 - 0.85
+    xy = xy[None] + (torch.rand(B, n1 * n1, 2, generator=g) - 0.5) * 0.08
+    z = (torch.rand(B, n1 * n1, 1, generator=g) * 2 - 1) * 0.8
+    w = torch.rand(B, n1 * n1, 1, generator=g) * 1.5 + 0.5
+    grid = torch.cat([xy * w, z * w, w], -1)
+    # the crossing triangle: in front of the grid, its third vertex behind the camera
+    extra = torch.tensor([[-0.3, -0.2, -0.9, 1.0], [0.4, -0.3, -0.9, 1.0], [0.1, 0.6, 0.2, -0.5]]).expand(B, 3, 4)
+    pos = torch.cat([grid, extra], 1).contiguous()
+    V = pos.shape[1]
+    tris = []
+    for y in range(N):
+        for x in range(N):
+            a = y * n1 + x
+            tris += [[a, a + 1, a + n1], [a + 1, a + n1 + 1, a + n1]]
+    tris.append([V - 3, V - 2, V - 1])
+    tri = torch.tensor(tris, dtype=torch.int32)
+    T = tri.shape[0]
+    assert T == 201 and V == 124
+    return pos, tri, V, T
+
+
+def _inputs():
+    from fpc_diffrend_amd import ops as dr
+    dev = 'cuda'
+    pos, tri, V, T = _mesh()
+    adj = dr.antialias_construct_topology_hash(tri.to(dev)).cpu()      # of the intact mesh: -1 on the grid's border already
+    tri = tri.clone()
+    for t, (k, v) in BAD.items():
+        tri[t, k] = V if v == 'V' else v
+    tri[120, 2] = V
+    valid = ((tri >= 0) & (tri < V)).all(1)
+    assert int((~valid).sum()) == len(BAD)
+    # adjacency: -1, T + 5 (out of range for this V) and valid values, on valid and invalid triangles alike
+    assert T + 5 >= V
+    adj = adj.clone()
+    adj[3, 0], adj[7, 1], adj[60, 2], adj[121, 0] = -1, -1, -1, -1
+    adj[4, 1], adj[50, 0], adj[61, 2], adj[150, 1], adj[200, 2] = T + 5, T + 5, T + 5, T + 5, T + 5
+    assert int(((adj >= 0) & (adj < V)).sum()) > 400
+    # the table inside a larger allocation; behind it: visible vertices a load without its guard would pick up
+    g = torch.Generator().manual_seed(5)
+    store = torch.empty(B * V + T + 64, 4)
+    store[:, :2] = torch.rand(store.shape[0], 2, generator=g) * 1.6 - 0.8
+    store[:, 2] = -0.95
+    store[:, 3] = 1.0
+    store[:B * V] = pos.reshape(B * V, 4)
+    store = store.to(dev)
+    pos_d = store[:B * V].view(B, V, 4)
+    assert pos_d.is_contiguous() and pos_d.data_ptr() == store.data_ptr()
+    return dict(store=store, pos=pos_d, tri=tri.to(dev), adj=adj.to(dev), valid=valid, V=V, T=T)
+
+
+def _submesh(m):
+    """The same call with the invalid triangles removed: the table stays, triangle t becomes new_of_old[t]."""
+    keep = m['valid']
+    new_of_old = torch.cumsum(keep.long(), 0) - 1
+    new_of_old[~keep] = -1
+    kd = keep.to(m['tri'].device)
+    sub = dict(m, tri=m['tri'][kd].contiguous(), adj=m['adj'][kd].contiguous(), T=int(keep.sum()))
+    return sub, new_of_old
+
+
+def _renumber(ids, new_of_old):
+    """ids [.. ] (triangle + 1, 0 = empty) of the full mesh -> the sub-mesh's numbering; an invalid triangle that shows becomes -1."""
+    out = torch.zeros_like(ids)
+    hit = ids > 0
+    out[hit] = (new_of_old[(ids[hit] - 1).long()] + 1).to(ids.dtype)
+    out[hit & (out == 0)] = -1
+    return out
+
+
+def _rasterize_fwd(m, ranges=None):
+    from fpc_diffrend_amd import _lib
+    from fpc_diffrend_amd.ops import _ptr, _stream
+    lib = _lib.load()
+    dev = m['pos'].device
+    rast = torch.full((B, H, W, 4), -7.0, dtype=torch.float32, device=dev)
+    scratch = torch.empty(lib.fpcdr_rasterize_scratch_bytes(B, m['T']), dtype=torch.uint8, device=dev)
+    r = torch.tensor(ranges, dtype=torch.int32, device=dev) if ranges is not None else None
+    p = _lib.RasterizeFwd(pos=_ptr(m['pos']), tri=_ptr(m['tri']), B=B, V=m['V'], T=m['T'], H=H, W=W, scratch=_ptr(scratch), rast=_ptr(rast),
+                          rast_db=None, hint=None, ranges=_ptr(r))
+    _lib.call("fpcdr_rasterize_fwd", ctypes.byref(p), _stream())
+    torch.cuda.synchronize()
+    return rast.cpu()
+
+
+def _objective_fwd(m, bin_lists):
+    """fpcdr_objective_fwd, value only, records addressed by pixel, no launch hints -> (id planes [B, bins * 1024] int32, sil [B,T] uint8)."""
+    from fpc_diffrend_amd import _lib
+    from fpc_diffrend_amd.ops import _ptr, _stream
+    lib = _lib.load()
+    dev = m['pos'].device
+    T, V = m['T'], m['V']
+    u8 = lambda n: torch.zeros(n, dtype=torch.uint8, device=dev)
+    g = torch.Generator().manual_seed(3)
+    uv = torch.rand(V, 2, generator=g).to(dev)
+    uv_tri = m['tri'].clamp(0, V - 1).contiguous()
+    tri_uv = uv[uv_tri.long()].contiguous()
+    tex = (torch.rand(16, 16, 1, generator=g) * 0.5).to(dev)
+    ref = torch.randint(0, 141, (B, H, W), generator=g, dtype=torch.uint8).to(dev)
+    scratch = u8(lib.fpcdr_rasterize_scratch_bytes(B, T))
+    sil = torch.full((B * T,), 0xAA, dtype=torch.uint8, device=dev)
+    idp = u8(lib.fpcdr_idplane_bytes(B, H, W))
+    binlist = u8(lib.fpcdr_binlist_bytes(B, H, W)) if bin_lists else None
+    occ, cmask = u8(lib.fpcdr_occ_bytes(B, H, W)), u8(lib.fpcdr_objective_cmask_bytes(B, H, W))
+    ecol = torch.zeros(4, dtype=torch.float32, device=dev)
+    acc = torch.zeros(_lib.LOSS_SLOTS, dtype=torch.float64, device=dev)
+    n_rec = B * H * W
+    rec = torch.zeros(n_rec, 4, dtype=torch.float32, device=dev)
+    color = torch.zeros(n_rec, 1, dtype=torch.float32, device=dev)
+    g_aa = torch.zeros(n_rec, 1, dtype=torch.float32, device=dev)
+    p = _lib.Objective(pos=_ptr(m['pos']), tri=_ptr(m['tri']), adj=_ptr(m['adj']), B=B, V=V, T=T, H=H, W=W, scratch=_ptr(scratch), uv=_ptr(uv),
+                       uv_tri=_ptr(uv_tri), Vt=V, tri_uv=_ptr(tri_uv), tex=_ptr(tex), Ht=16, Wt=16, C=1, boundary_mode=_lib.BOUNDARY['wrap'],
+                       ref=_ptr(ref), bg=45.0 / 255.0, color_scale=255.0, grad_scale=1.0 / n_rec, sil=_ptr(sil), idp=_ptr(idp), occ=_ptr(occ),
+                       cmask=_ptr(cmask), empty_color=_ptr(ecol), loss_sum=_ptr(acc), grad_pos=None, grad_tex=None, binlist=_ptr(binlist),
+                       zero_outputs=1, rec=_ptr(rec), color=_ptr(color), grad_aa=_ptr(g_aa))
+    _lib.call("fpcdr_objective_fwd", ctypes.byref(p), _stream())
+    torch.cuda.synchronize()
+    return idp.view(torch.int32).reshape(B, -1).cpu(), sil.reshape(B, T).cpu()
+
+
+def _bits_of_planes(planes):
+    OY, OX = (H + 31) // 32, (W + 31) // 32
+    v = (planes.reshape(B, OY, OX, 32, 32) >> 24) & 0xff
+    return v.permute(0, 1, 3, 2, 4).reshape(B, OY * 32, OX * 32)[:, :H, :W].contiguous()
+
+
+def _oracle_ids(m_sub, ranges=None):
+    from oracle import ops as oracle_ops
+    oracle_ops.build()
+    pos, tri = m_sub['pos'].cpu(), m_sub['tri'].cpu()
+    if ranges is None:
+        return oracle_ops.rasterize_ids(pos, tri, RES)
+    out = []
+    for b, (first, count) in enumerate(ranges):
+        ids = oracle_ops.rasterize_ids(pos[b:b + 1], tri[first:first + count], RES)[0]
+        out.append(torch.where(ids > 0, ids + first, ids))
+    return torch.stack(out)
+
+
+def test_rasterize_fwd_with_invalid_indices_and_a_range_image():
+    m = _inputs()
+    sub, new_of_old = _submesh(m)
+    T = m['T']
+    # the range-mode image's slice in the sub-mesh's numbering: the valid triangles of [first, first + count)
+    f, c = RANGE
+    keep = m['valid']
+    f_sub, c_sub = int(keep[:f].sum()), int(keep[f:f + c].sum())
+    assert c_sub < c      # (an invalid triangle lies inside the range)
+    for ranges, ranges_sub in ((None, None), ([[0, T], [f, c]], [[0, sub['T']], [f_sub, c_sub]])):
+        full = _rasterize_fwd(m, ranges)
+        part = _rasterize_fwd(sub, ranges_sub)
+        ids_full, ids_part = full[..., 3].to(torch.int32), part[..., 3].to(torch.int32)
+        assert int((ids_part > 0).sum()) > 1000
+        assert torch.equal(_renumber(ids_full, new_of_old), ids_part), f"ranges={ranges}: ids change when the invalid triangles are removed"
+        # (u, v, z/w): bit for bit
+        assert torch.equal(full[..., :3].contiguous().view(torch.int32), part[..., :3].contiguous().view(torch.int32))
+        assert torch.equal(ids_part, _oracle_ids(sub, ranges_sub)), f"ranges={ranges}: ids of the valid sub-mesh differ from the oracle"
+        # the crossing triangle shows (rule R1 ran), under its own id
+        assert int((ids_full[0] == T).sum()) > 0
+    # (the range image shows nothing outside its slice)
+    shown = ids_full[1][ids_full[1] > 0] - 1
+    assert int(shown.min()) >= f and int(shown.max()) < f + c
+
+
+@pytest.mark.parametrize("bin_lists", [True, False])
+def test_objective_fwd_ids_and_silhouette_bits_with_invalid_indices(bin_lists):
+    from fpc_diffrend_amd import _lib
+    from fpc_diffrend_amd.ops import _ptr, _stream
+    m = _inputs()
+    sub, new_of_old = _submesh(m)
+    T, V = m['T'], m['V']
+    planes, sil = _objective_fwd(m, bin_lists)
+    planes_sub, sil_sub = _objective_fwd(sub, bin_lists)
+    ids, ids_sub = decode_id_planes(planes, B, H, W), decode_id_planes(planes_sub, B, H, W)
+    assert int((ids_sub > 0).sum()) > 1000
+    assert torch.equal(_renumber(ids, new_of_old), ids_sub), "id planes change when the invalid triangles are removed"
+    # outside the image the planes hold nothing, in both calls; inside, the same high bytes
+    assert torch.equal((planes >> 24) & 0xff, (planes_sub >> 24) & 0xff)
+    assert torch.equal(ids_sub, _oracle_ids(sub)), "ids of the valid sub-mesh differ from the oracle"
+    assert int((ids[0] == T).sum()) > 0
+    # silhouette bits against the stand-alone kernel
+    want = torch.full((B * T,), 0x55, dtype=torch.uint8, device=m['pos'].device)
+    _lib.call("fpcdr_silhouette_bits", _ptr(m['pos']), _ptr(m['tri']), _ptr(m['adj']), B, V, T, H, W, _ptr(want), _stream())
+    torch.cuda.synchronize()
+    want = want.reshape(B, T).cpu()
+    valid = m['valid']
+    assert torch.equal(sil[:, valid], want[:, valid]), "silhouette bits of the set-up kernel differ from fpcdr_silhouette_bits"
+    assert int(sil[:, ~valid].abs().sum()) == 0 and int(want[:, ~valid].abs().sum()) == 0, "bits of a triangle with an invalid index"
+    assert len(torch.unique(want[:, valid])) >= 3      # (the case is not trivial: several bit patterns occur)
+    assert torch.equal(sil_sub, sil[:, valid])
+    # ... and as the rasteriser handed them on: the id plane's high byte on covered pixels
+    bits = _bits_of_planes(planes)
+    covered = ids > 0
+    bsel = torch.nonzero(covered, as_tuple=True)[0]
+    assert torch.equal(bits[covered].to(torch.uint8), want[bsel, (ids[covered] - 1).long()])
+    assert int(bits[~covered].abs().sum()) == 0
