@@ -55,6 +55,16 @@ def load_reference_image(path):
     return np.flip(img, 0).astype(np.uint8).copy()
 
 
+def load_raw_image(path):
+    """The decoded image as it is -- no clip, no flip: uint8 [H,W] (the first channel of a multi-channel file, as scene.from_take
+    takes it).  What the reference's src/undistort.py hands to cv2.undistort.  Anything that is not 8 bit raises ValueError."""
+    from PIL import Image
+    img = np.array(Image.open(path))
+    if img.dtype != np.uint8 or img.ndim not in (2, 3):
+        raise ValueError(f"{path}: expected an 8-bit image, got dtype {img.dtype}, shape {img.shape}")
+    return np.ascontiguousarray(img if img.ndim == 2 else img[..., 0])
+
+
 def load_calibration(calibpath, camera_dirs):
     """Reference fit.py:514-521: calibration.json looked up by the second '_' field of each camera directory name."""
     with open(calibpath) as f:

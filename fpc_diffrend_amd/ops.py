@@ -28,7 +28,7 @@ import torch
 from . import _lib
 
 __all__ = ['RasterizeGLContext', 'RasterizeCudaContext', 'RasterizeHipContext', 'rasterize', 'interpolate', 'texture',
-           'texture_construct_mip', 'antialias', 'antialias_construct_topology_hash', 'render_textured', 'pixel_objective']
+           'texture_construct_mip', 'antialias', 'antialias_construct_topology_hash', 'render_textured', 'pixel_objective', 'undistort_images']
 
 
 def _stream():
@@ -688,6 +688,44 @@ def reference_background_sumsq(ref_u8, background=45.0 / 255.0):
     out = torch.zeros(ref_u8.shape[0], dtype=torch.float64, device=ref_u8.device)
     _lib.call("fpcdr_ref_bg_sumsq", _ptr(ref_u8), ref_u8.shape[0], ref_u8.shape[1] * ref_u8.shape[2], float(background) * 255.0,
               _ptr(out), _stream())
+    return out
+
+
+def undistort_images(images, intr, dist, clip_max=255, flip_rows=False):
+    """Lens undistortion of 8-bit images (the reference's src/undistort.py: cv2.undistort(image, intrinsic, dist), new camera matrix =
+    old one), by the rule of DESIGN.md 3 "Undistortion rule" (fpcdr_undistort_u8): OpenCV's five-coefficient model in double precision,
+    bilinear taps with a zero border, round half up, then min(., clip_max) and, with flip_rows, row i written to row H - 1 - i.
+
+      images  uint8 GPU tensor [N,H,W] or [F,Nc,H,W], contiguous; image n belongs to camera n % Nc
+      intr    [Nc,3,3] intrinsic matrices, dist [Nc,5] or [Nc,5,1] coefficients (k1, k2, p1, p2, k3): arrays or tensors; their values
+              (data.load_calibration holds float32) are widened to double
+
+    Returns a new uint8 tensor of the shape of `images`."""
+    _check_tensor('images', images, torch.uint8)
+    if images.dim() not in (3, 4):
+        raise ValueError(f"images must be [N,H,W] or [F,Nc,H,W] (got shape {tuple(images.shape)})")
+    if not images.is_contiguous():
+        raise ValueError("images must be contiguous")
+    intr = torch.as_tensor(intr).detach().to('cpu', torch.float64)
+    dist = torch.as_tensor(dist).detach().to('cpu', torch.float64)
+    if intr.dim() != 3 or tuple(intr.shape[1:]) != (3, 3):
+        raise ValueError(f"intr must be [Nc,3,3] (got shape {tuple(intr.shape)})")
+    Nc = intr.shape[0]
+    if tuple(dist.shape) not in ((Nc, 5), (Nc, 5, 1)):
+        raise ValueError(f"dist must be [Nc,5] or [Nc,5,1] with Nc = {Nc} (got shape {tuple(dist.shape)})")
+    if images.dim() == 4 and images.shape[1] != Nc:
+        raise ValueError(f"images [F,Nc,H,W] has {images.shape[1]} cameras, intr has {Nc}")
+    if Nc == 0 or images.numel() == 0:
+        raise ValueError("empty input")
+    if not 0 <= int(clip_max) <= 255:
+        raise ValueError("clip_max must be in [0, 255]")
+    H, W = images.shape[-2:]
+    table = torch.cat([torch.stack([intr[:, 0, 0], intr[:, 1, 1], intr[:, 0, 2], intr[:, 1, 2]], dim=1), dist.reshape(Nc, 5)], dim=1)
+    out = torch.empty_like(images)
+    with torch.cuda.device(images.device):
+        table = table.contiguous().to(images.device)
+        _lib.call("fpcdr_undistort_u8", _ptr(images), _ptr(out), _ptr(table), images.numel() // (H * W), H, W, Nc, int(clip_max),
+                  1 if flip_rows else 0, _stream())
     return out
 
 

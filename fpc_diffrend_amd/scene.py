@@ -186,7 +186,33 @@ def make_scene(mesh=MESH_1K, K=10, n_frames=4, resolution=(256, 256), texshape=(
                  cams=cams, resolution=tuple(resolution), weights_gt=w, t_gt=t, q_gt=q)
 
 
-def from_take(basemeshpath, localblpath, calibpath, imdir, texpath="", texshape=(1024, 1024, 1), seed=0):
+UNDISTORT_CHUNK_BYTES = 256 << 20     # device memory of one upload of raw images (and as much again for the kernel's output)
+
+
+def _undistorted_chunks(imdir, cams, lookup, n_frames, digits, device, clip_max, flip_rows):
+    """Yield (first frame, [f,Nc,H,W] uint8 host array) over a take: raw images read from disk, uploaded a chunk of whole frames at a
+    time -- device memory does not grow with the take's length -- passed through ops.undistort_images and copied back."""
+    import torch
+    dev = torch.device(device)
+    if dev.type != 'cuda' or not torch.cuda.is_available():
+        raise RuntimeError("undistortion runs on an MI355X (device='cuda'): the HIP path has no CPU fallback")
+    from . import ops
+    intr = np.stack([c['intr'] for c in lookup])
+    dist = np.stack([np.asarray(c['dist']).reshape(5) for c in lookup])
+    H, W = data.load_raw_image(os.path.join(imdir, cams[0], f"{cams[0]}_{0:0{digits}d}.tif")).shape
+    step = max(1, UNDISTORT_CHUNK_BYTES // (len(cams) * H * W))
+    for f0 in range(0, n_frames, step):
+        raw = np.empty((min(step, n_frames - f0), len(cams), H, W), dtype=np.uint8)
+        for c, cam in enumerate(cams):
+            for f in range(raw.shape[0]):
+                img = data.load_raw_image(os.path.join(imdir, cam, f"{cam}_{f0 + f:0{digits}d}.tif"))
+                assert img.shape == (H, W), f"{cam} frame {f0 + f}: {img.shape} differs from {(H, W)}"
+                raw[f, c] = img
+        out = ops.undistort_images(torch.from_numpy(raw).to(dev), intr, dist, clip_max=clip_max, flip_rows=flip_rows)
+        yield f0, out.cpu().numpy()
+
+
+def from_take(basemeshpath, localblpath, calibpath, imdir, texpath="", texshape=(1024, 1024, 1), seed=0, undistort=False, device='cuda'):
     """A take on disk in the reference's layout -> Scene (reference fit.py:415-439, 461, 514-533):
 
       basemeshpath  base mesh .obj (v / vt / f v/vt triangles)                       fit.py:424-432, data.py:7-39
@@ -198,19 +224,33 @@ def from_take(basemeshpath, localblpath, calibpath, imdir, texpath="", texshape=
 
     The reference decodes ONE image from disk per iteration; here every frame of every camera is read once (clipped to
     [0,140] and flipped like fit.py:531-532) so that the fit loop finds them resident in HBM as 8-bit.  Camera
-    directories are taken in sorted order (the reference uses os.listdir order, which is file-system dependent)."""
+    directories are taken in sorted order (the reference uses os.listdir order, which is file-system dependent).
+
+    undistort: the images are RAW captures.  The reference undistorts them in a preprocess of its own (src/undistort.py, "lens
+    distortion currently handled as preprocess in reference images", fit.py:540); here each chunk of frames goes through
+    ops.undistort_images on `device` with the calibration's five `distortion` coefficients -- before the clip and the flip, as there
+    -- and comes back into the Scene's host array.  It needs the GPU (RuntimeError without one).  Off by default: the reference's
+    shipped calibration has all-zero coefficients and its takes are undistorted already."""
     cams = sorted(os.listdir(imdir))
     n_frames, digits = data.assert_num_frames(cams, imdir)
     base = data.MeshData(basemeshpath)
     lookup = data.load_calibration(calibpath, cams)
-    first = data.load_reference_image(os.path.join(imdir, cams[0], f"{cams[0]}_{0:0{digits}d}.tif"))
-    H, W = first.shape[:2]
-    images = np.empty((n_frames, len(cams), H, W), dtype=np.uint8)
-    for c, cam in enumerate(cams):
-        for f in range(n_frames):
-            img = data.load_reference_image(os.path.join(imdir, cam, f"{cam}_{f:0{digits}d}.tif"))
-            assert img.shape[:2] == (H, W), f"{cam} frame {f}: {img.shape[:2]} differs from {(H, W)}"
-            images[f, c] = img if img.ndim == 2 else img[..., 0]
+    if undistort:
+        images = None
+        for f0, chunk in _undistorted_chunks(imdir, cams, lookup, n_frames, digits, device, clip_max=140, flip_rows=True):
+            if images is None:
+                H, W = chunk.shape[2:]
+                images = np.empty((n_frames, len(cams), H, W), dtype=np.uint8)
+            images[f0:f0 + chunk.shape[0]] = chunk
+    else:
+        first = data.load_reference_image(os.path.join(imdir, cams[0], f"{cams[0]}_{0:0{digits}d}.tif"))
+        H, W = first.shape[:2]
+        images = np.empty((n_frames, len(cams), H, W), dtype=np.uint8)
+        for c, cam in enumerate(cams):
+            for f in range(n_frames):
+                img = data.load_reference_image(os.path.join(imdir, cam, f"{cam}_{f:0{digits}d}.tif"))
+                assert img.shape[:2] == (H, W), f"{cam} frame {f}: {img.shape[:2]} differs from {(H, W)}"
+                images[f, c] = img if img.ndim == 2 else img[..., 0]
     if texpath:
         from PIL import Image
         tex = np.array(Image.open(texpath)) / 255.0                      # fit.py:434-436
@@ -222,11 +262,28 @@ def from_take(basemeshpath, localblpath, calibpath, imdir, texpath="", texshape=
                  texture=np.ascontiguousarray(tex, dtype=np.float32), cams=lookup, resolution=(H, W), images=images)
 
 
-def write_take(sc, directory, images, cam_idxs=None, blendshape_scale=1.0):
+def undistort_take(imdir, calibpath, out_dir, device='cuda'):
+    """The counterpart of the reference's src/undistort.py: every image of the raw take `imdir` undistorted with its camera's
+    calibration (ops.undistort_images, full 8-bit range, rows as they are) and written to `out_dir` under the same camera directory
+    and file names as 8-bit TIFF.  Undistort once, then read `out_dir` with the default from_take.  Returns out_dir."""
+    from PIL import Image
+    cams = sorted(os.listdir(imdir))
+    n_frames, digits = data.assert_num_frames(cams, imdir)
+    lookup = data.load_calibration(calibpath, cams)
+    for f0, chunk in _undistorted_chunks(imdir, cams, lookup, n_frames, digits, device, clip_max=255, flip_rows=False):
+        for c, cam in enumerate(cams):
+            os.makedirs(os.path.join(out_dir, cam), exist_ok=True)
+            for f in range(chunk.shape[0]):
+                Image.fromarray(chunk[f, c]).save(os.path.join(out_dir, cam, f"{cam}_{f0 + f:0{digits}d}.tif"))
+    return out_dir
+
+
+def write_take(sc, directory, images, cam_idxs=None, blendshape_scale=1.0, distortion=None):
     """Write a Scene + reference images [F,Nc,H,W] uint8 (row 0 = bottom) to `directory` in the layout `from_take`
     reads (the reference's, fit.py:415-432, 514-533): basemesh.obj, blendshapes/*.obj, calibration.json,
     images/cam_<name>/cam_<name>_<frame>.tif.  Returns the four paths.  (Test / example helper: the reference ships
-    no data.)"""
+    no data.)  distortion: optional [Nc,5] (k1, k2, p1, p2, k3), one row per camera of cam_idxs, written as each camera's
+    `distortion`; None writes zeros."""
     import json
     from PIL import Image
     cam_idxs = list(range(len(sc.cams))) if cam_idxs is None else list(cam_idxs)
@@ -249,9 +306,11 @@ def write_take(sc, directory, images, cam_idxs=None, blendshape_scale=1.0):
     for k in range(sc.blendshapes.shape[1]):
         write_obj(os.path.join(bldir, f"shape_{k:04d}.obj"), sc.v_base + blendshape_scale * sc.blendshapes[:, k])
     calib = {}
-    for c in cam_idxs:
+    distortion = np.zeros((len(cam_idxs), 5)) if distortion is None else np.asarray(distortion, dtype=np.float64)
+    assert distortion.shape == (len(cam_idxs), 5), f"distortion must be [{len(cam_idxs)},5], got {distortion.shape}"
+    for j, c in enumerate(cam_idxs):
         cam = sc.cams[c]
-        calib[cam['cam']] = {'intrinsic': np.asarray(cam['intr'], dtype=np.float64).tolist(), 'distortion': np.zeros((5, 1)).tolist(),
+        calib[cam['cam']] = {'intrinsic': np.asarray(cam['intr'], dtype=np.float64).tolist(), 'distortion': distortion[j].reshape(5, 1).tolist(),
                              'rotation': np.asarray(cam['rot'], dtype=np.float64).tolist(),
                              'translation': np.asarray(cam['trans_calib'], dtype=np.float64).reshape(3, 1).tolist()}
     calibpath = os.path.join(directory, "calibration.json")

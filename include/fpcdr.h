@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define FPCDR_ABI_VERSION 12
+#define FPCDR_ABI_VERSION 13
 
 enum {
     FPCDR_OK = 0,
@@ -505,6 +505,19 @@ typedef struct {
     double beta1_f64, beta2_f64;
 } fpcdr_adam_params;
 int fpcdr_adam_step(const fpcdr_adam_params *p, void *stream);
+
+/* ABI v13.  Lens undistortion of 8-bit images at ingest (reference src/undistort.py: cv2.undistort(image, intrinsic, dist) over every
+ * image of a take, the new camera matrix equal to the old one).  src, dst: [n_images, H, W] uint8 on the device, different buffers;
+ * image n belongs to camera n % n_cam (the [F, n_cam, H, W] layout).  cam_table: DEVICE [n_cam][9] doubles
+ * fx, fy, cx, cy, k1, k2, p1, p2, k3 (OpenCV's five-coefficient model).  For the output pixel at row i FROM THE TOP, column j, in
+ * unfused IEEE double ("Undistortion rule"):
+ *   x = (j - cx) / fx, y = (i - cy) / fy, r2 = x x + y y, rad = 1 + r2 (k1 + r2 (k2 + r2 k3)),
+ *   xd = x rad + ((2 p1)(x y) + p2 (r2 + 2 (x x))),  yd = y rad + (p1 (r2 + 2 (y y)) + (2 p2)(x y)),  u = fx xd + cx,  v = fy yd + cy,
+ *   bilinear over the four source pixels around (v, u) with a tap outside the image = 0 (top = t00 + a (t01 - t00), bot likewise,
+ *   val = top + b (bot - top)),  out = min(floor(val + 0.5), clip_max),
+ * written to row i, or to row H - 1 - i when flip_rows is set.  Any H, W. */
+int fpcdr_undistort_u8(const uint8_t *src, uint8_t *dst, const double *cam_table, int64_t n_images, int H, int W, int n_cam,
+                       int clip_max, int flip_rows, void *stream);
 
 #ifdef __cplusplus
 }
