@@ -107,7 +107,7 @@ constexpr int SCAN_K = FPCDR_SCAN_K;        // live chunks whose bounding boxes 
 // d + 0.0f turns -0.0 into +0.0, so that the integer order of the keys is the float order of the depths.
 __device__ __forceinline__ unsigned long long zpack(float d, int id) {
     unsigned int u = __float_as_uint(d + 0.0f);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    u ^= (unsigned int)((int)u >> 31) | 0x80000000u;   // sign set: ~u; sign clear: u | top bit
     return ((unsigned long long)u << 32) | (unsigned int)id;
 }
 constexpr unsigned long long Z_EMPTY = ~0ull;
@@ -861,25 +861,31 @@ __device__ __forceinline__ void bins_body(const int b, const int bxi, const int 
                     int R1 = __mul24(A1, Px - r.X2) + __mul24(B1, Py - r.Y2) - n1;
                     int R2 = __mul24(A2, Px - r.X0) + __mul24(B2, Py - r.Y0) - n2;
                     const int A0s = A0 * SUBPIX, A1s = A1 * SUBPIX, A2s = A2 * SUBPIX;
-                    const int rx0 = Px - r.X0;
-                    int ry = Py - r.Y0;
                     unsigned long long *zrow = &s_z[(y0 + part - bin_y0) * BIN + (x0 - bin_x0)];
                     const int bh = y1 - y0 + 1;
-                    // rows outside, columns inside: the inner trip is three additions and one test (the flattened loop that
-                    // this replaces spent two thirds of its instructions on wrap-around selects)
+                    // rows outside, columns inside (the flattened loop that this replaces spent two thirds of its instructions on
+                    // wrap-around selects).  A trip carries five running values: the three edge functions, the LDS address of the sample
+                    // -- whose comparison with the row's end is the loop test, no column counter beside it -- and the depth plane's x
+                    // offset AS A FLOAT: |Px - X0| and |Py - Y0| stay below 2^24 and move in steps of SUBPIX, so the float is the
+                    // integer's conversion bit for bit at every sample, for one addition instead of an addition and a conversion.
+                    // Listing: 6 vector instructions per sample + 2 for the inside test + 5 on a hit (profiles/bins_sample_loop.txt).
+                    static_assert(SMALL_EXTENT + HALFPIX + BIN * SUBPIX < (1 << 24), "the lane walk's running floats are exact");
                     const int B0s = B0 * SUBPIX * split, B1s = B1 * SUBPIX * split, B2s = B2 * SUBPIX * split;
+                    const float rxf0 = (float)(Px - r.X0);
+                    float ryf = (float)(Py - r.Y0);
                     for (int rr = part; rr < bh; rr += split) {
-                        int E0 = R0, E1 = R1, E2 = R2, rx = rx0;
-                        const float dzr = __fmaf_rn(r.zB, (float)ry, r.z0);
-                        for (int c = 0; c < bw; ++c) {
+                        int E0 = R0, E1 = R1, E2 = R2;
+                        float rxf = rxf0;
+                        const float dzr = __fmaf_rn(r.zB, ryf, r.z0);
+                        for (unsigned long long *zp = zrow, *const zend = zrow + bw; zp < zend; ++zp) {
                             if ((E0 | E1 | E2) >= 0) {
-                                const float d = __fmaf_rn(r.zA, (float)rx, dzr);
-                                if (d >= -1.0f && d <= 1.0f) atomicMin(&zrow[c], zpack(d, zkey));
+                                const float d = __fmaf_rn(r.zA, rxf, dzr);
+                                if (d >= -1.0f && d <= 1.0f) atomicMin(zp, zpack(d, zkey));
                             }
-                            E0 += A0s; E1 += A1s; E2 += A2s; rx += SUBPIX;
+                            E0 += A0s; E1 += A1s; E2 += A2s; rxf += (float)SUBPIX;
                         }
                         R0 += B0s; R1 += B1s; R2 += B2s;
-                        ry += SUBPIX * split;
+                        ryf += (float)(SUBPIX * split);
                         zrow += BIN * split;
                     }
                 } else if (part == 0) {
