@@ -28,7 +28,7 @@ import torch
 from . import _lib
 
 __all__ = ['RasterizeGLContext', 'RasterizeCudaContext', 'RasterizeHipContext', 'rasterize', 'interpolate', 'texture',
-           'texture_construct_mip', 'antialias', 'antialias_construct_topology_hash', 'render_textured', 'pixel_objective', 'undistort_images']
+           'texture_construct_mip', 'antialias', 'antialias_construct_topology_hash', 'render_textured', 'pixel_objective', 'undistort_images', 'compare_images']
 
 
 def _stream():
@@ -727,6 +727,58 @@ def undistort_images(images, intr, dist, clip_max=255, flip_rows=False):
         _lib.call("fpcdr_undistort_u8", _ptr(images), _ptr(out), _ptr(table), images.numel() // (H * W), H, W, Nc, int(clip_max),
                   1 if flip_rows else 0, _stream())
     return out
+
+
+def compare_images(img, ref, mode='colour', cols=(100, 1100), scale=255.0, flip_rows=False, want_rows=True):
+    """Rendered images against captures (the reference's comparisons.py: compareSequence's heat map and the integer differences behind
+    compareSequenceNumerical's row means), by the rule of DESIGN.md 3 "Comparison rule" (fpcdr_compare_u8).
+
+      img        GPU tensor [N,H,W] or [N,H,W,1], contiguous: uint8, or float32 quantised as clip(rint(img * scale), 0, 255) (NaN -> 0)
+      ref        uint8 GPU tensor [N,H,W], contiguous, top row first
+      mode       'colour' (d >= 0: (255, s, s), d < 0: (s, s, 255), s = max(255 - 2 |d|, 0)), 'grey' ((s, s, s)), or None: no heat map
+      cols       (col0, col1): the row sums run over the columns [col0, col1) inside the image
+      flip_rows  output row i compares img's row H - 1 - i (a raster has row 0 at the bottom) with ref's row i
+      want_rows  False: no row sums
+
+    Returns (heat uint8 [N,H,W,3] or None, row_sums int32 [N,H] or None): sums of |d|, exact; the means are the caller's."""
+    if mode not in ('colour', 'grey', None):
+        raise ValueError(f"mode must be 'colour', 'grey' or None (got {mode!r})")
+    if mode is None and not want_rows:
+        raise ValueError("neither a heat map (mode) nor row sums (want_rows) requested")
+    if not isinstance(img, torch.Tensor) or not isinstance(ref, torch.Tensor):
+        raise TypeError("img and ref must be torch.Tensors")
+    if not img.is_cuda or not ref.is_cuda:
+        raise ValueError(f"img and ref must be GPU tensors (got {img.device}, {ref.device}); the comparison has no CPU path")
+    if img.device != ref.device:
+        raise ValueError(f"img and ref are on different devices ({img.device}, {ref.device})")
+    if img.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"img must be float32 or uint8 (got {img.dtype})")
+    if ref.dtype != torch.uint8:
+        raise ValueError(f"ref must be uint8 (got {ref.dtype})")
+    if img.dim() == 4:
+        if img.shape[3] != 1:
+            raise ValueError(f"img must have one channel (got shape {tuple(img.shape)})")
+        img = img[..., 0]
+    if img.dim() != 3 or ref.dim() != 3:
+        raise ValueError(f"img must be [N,H,W] or [N,H,W,1] and ref [N,H,W] (got shapes {tuple(img.shape)}, {tuple(ref.shape)})")
+    if img.shape != ref.shape:
+        raise ValueError(f"img {tuple(img.shape)} and ref {tuple(ref.shape)} differ in shape")
+    if not img.is_contiguous() or not ref.is_contiguous():
+        raise ValueError("img and ref must be contiguous")
+    if img.numel() == 0:
+        raise ValueError("empty input")
+    N, H, W = img.shape
+    if 255 * W >= 2 ** 31:
+        raise ValueError("a row sum of 255 * W does not fit int32")
+    col0, col1 = (int(c) for c in cols)
+    lim = 2 ** 31 - 1
+    col0, col1 = max(min(col0, lim), -lim), max(min(col1, lim), -lim)
+    heat = torch.empty((N, H, W, 3), dtype=torch.uint8, device=img.device) if mode is not None else None
+    rows = torch.zeros((N, H), dtype=torch.int32, device=img.device) if want_rows else None
+    with torch.cuda.device(img.device):
+        _lib.call("fpcdr_compare_u8", _ptr(img), 1 if img.dtype == torch.float32 else 0, float(scale), _ptr(ref), _ptr(heat), _ptr(rows),
+                  N, H, W, col0, col1, 1 if mode == 'grey' else 0, 1 if flip_rows else 0, _stream())
+    return heat, rows
 
 
 def pixel_objective(glctx, pos, tri, uv, uv_tri, tex, ref_u8, resolution, n_total=None, background=45.0 / 255.0,

@@ -2,7 +2,9 @@
 Offline multi-camera re-render and numerical comparison of a finished fit -- forward-only consumers of the same
 operators.  Host-side mirror of the reference's src/torch/render_multicam.py:95-169
 (read result/{i}.obj + texture + pose.json, render every camera, tile 3 x 3) and comparisons.py:54-81
-(mean absolute difference over a crop, one CSV line per image).  The reference's mp4 / GLFW output is out of scope.
+(mean absolute difference over a crop, one CSV line per image).  compare_sequence / compare_result are the same comparison, plus
+the heat-map images of comparisons.py:21-50, on the GPU (ops.compare_images -> fpcdr_compare_u8; DESIGN.md 3, "Comparison rule").
+The reference's mp4 / GLFW output is out of scope.
 """
 import json
 import os
@@ -12,7 +14,7 @@ import torch
 
 from . import camera
 from . import ops as dr
-from .fit import render
+from .fit import BACKGROUND, render, render_from_clip
 
 
 def read_result_obj(path):
@@ -51,13 +53,8 @@ def make_img(arr, ncols=3):
     return arr.reshape(nrows, ncols, height, width, nc).swapaxes(1, 2).reshape(height * nrows, width * ncols, nc)
 
 
-@torch.no_grad()
-def render_multicam(glctx, vertices, pos_idx, uv, uv_idx, tex, cams, resolution, pose=None, modelview_offset=(0.0, 0.0, 0.0)):
-    """All cameras of the rig for one mesh: [Nc,H,W,C] in 0..255, top row first (reference render_multicam.py:131-158).
-
-    vertices [V,3] tensor; cams: calib_lookup entries; pose: optional (t [3], q [4]) rigid head pose applied like
-    `reproduce_pose` (render_multicam.py:146-150).  One batched launch per operator instead of one render per camera."""
-    dev = vertices.device
+def _camera_matrices(cams, modelview_offset, dev):
+    """(projection [Nc,4,4], modelview [Nc,4,4]) of calib_lookup entries on `dev` (reference render_multicam.py:131-145)."""
     mvps = []
     for c in cams:
         proj = camera.intrinsic_to_projection(c['intr'])
@@ -65,10 +62,25 @@ def render_multicam(glctx, vertices, pos_idx, uv, uv_idx, tex, cams, resolution,
         mvps.append((proj, mv))
     proj = torch.tensor(np.stack([p for p, _ in mvps]), dtype=torch.float32, device=dev)
     t_mv = torch.tensor(np.stack([m for _, m in mvps]), dtype=torch.float32, device=dev)
+    return proj, t_mv
+
+
+def _multicam_mvp(proj, t_mv, pose):
+    """Model-view-projection [Nc,4,4] with the optional rigid head pose (t [3], q [4]) applied (render_multicam.py:146-150)."""
     if pose is not None:
-        t, q = (torch.as_tensor(a, dtype=torch.float32, device=dev) for a in pose)
+        t, q = (torch.as_tensor(a, dtype=torch.float32, device=proj.device) for a in pose)
         t_mv = torch.matmul(camera.rigid_grad(t, camera.unitquat_to_rotmat(q))[None], t_mv)
-    mvp = torch.matmul(proj, t_mv)
+    return torch.matmul(proj, t_mv)
+
+
+@torch.no_grad()
+def render_multicam(glctx, vertices, pos_idx, uv, uv_idx, tex, cams, resolution, pose=None, modelview_offset=(0.0, 0.0, 0.0)):
+    """All cameras of the rig for one mesh: [Nc,H,W,C] in 0..255, top row first (reference render_multicam.py:131-158).
+
+    vertices [V,3] tensor; cams: calib_lookup entries; pose: optional (t [3], q [4]) rigid head pose applied like
+    `reproduce_pose` (render_multicam.py:146-150).  One batched launch per operator instead of one render per camera."""
+    dev = vertices.device
+    mvp = _multicam_mvp(*_camera_matrices(cams, modelview_offset, dev), pose)
     colour = render(glctx, mvp, vertices[None], pos_idx, uv, uv_idx, tex, resolution, False, 0) * 255.0
     return torch.flip(colour, dims=[1])      # row 0 = bottom in the raster -> top row first on disk
 
@@ -84,6 +96,16 @@ def mean_abs_diff(img, ref, rows=(200, 1401), cols=(100, 1100)):
     return float(row_means.mean()), row_means
 
 
+def _csv_line(m, rows):
+    """One image's line of numerical_clip.csv: 'image mean, row means...' (reference comparisons.py:79)."""
+    return f"{m}, {', '.join(str(x) for x in rows)}\n"
+
+
+def _csv_last_line(means):
+    """The file's last line, without a line end: the mean of the image means (reference comparisons.py:80)."""
+    return str(float(np.mean(means)))
+
+
 def compare_sequence_numerical(inferred, references, csv_path, **crop):
     """One CSV line per image 'mean, row means...' and the mean of means last (reference comparisons.py:56-80).
     inferred / references: sequences of arrays.  Returns the list of image means."""
@@ -93,8 +115,8 @@ def compare_sequence_numerical(inferred, references, csv_path, **crop):
         for img, ref in zip(inferred, references):
             m, rows = mean_abs_diff(img, ref, **crop)
             means.append(m)
-            f.write(f"{m}, {', '.join(str(x) for x in rows)}\n")
-        f.write(str(float(np.mean(means))))
+            f.write(_csv_line(m, rows))
+        f.write(_csv_last_line(means))
     return means
 
 
@@ -117,3 +139,142 @@ def rerender_result(result_dir, sc, device='cuda', frames=None, reproduce_pose=T
                                modelview_offset=(0.0, 170.0, 0.0))
         grid = make_img(imgs.cpu().numpy(), ncols=ncols)
         yield i, np.clip(np.rint(grid), 0, 255).astype(np.uint8)
+
+
+# ---- the same comparison on the GPU ------------------------------------------------------------------------------------------------
+def _crop(H, W, rows, cols):
+    """The crop clipped to the image, as mean_abs_diff clips it; an empty one has no mean."""
+    r0, r1 = max(rows[0], 0), min(rows[1], H)
+    c0, c1 = max(cols[0], 0), min(cols[1], W)
+    if r0 >= r1 or c0 >= c1:
+        raise ValueError(f"the crop rows {tuple(rows)}, cols {tuple(cols)} is empty on a {H} x {W} image")
+    return r0, r1, c0, c1
+
+
+def _means_of_row_sums(sums, crop):
+    """(image mean, per-row means) from one image's integer row sums [H] over the crop's columns: the second output of mean_abs_diff
+    is np.mean of an int32 row, i.e. exactly float64(sum) / columns, and the first is the same .mean() of the same float64 array."""
+    r0, r1, c0, c1 = crop
+    row_means = np.asarray(sums[r0:r1]).astype(np.float64) / (c1 - c0)
+    return float(row_means.mean()), row_means
+
+
+def _gpu(device):
+    dev = torch.device(device)
+    if dev.type != 'cuda' or not torch.cuda.is_available():
+        raise RuntimeError("the comparison runs on an MI355X (device='cuda'): the HIP path has no CPU fallback")
+    return dev
+
+
+def compare_sequence(inferred, references, out_dir, colour=True, heat=True, rows=(200, 1401), cols=(100, 1100), device='cuda', batch=16):
+    """compareSequenceNumerical and (heat=True) the heat-map images of compareSequence (reference comparisons.py:21-80) for a sequence
+    of image pairs, on the GPU: writes out_dir/numerical_clip.csv -- the text compare_sequence_numerical writes -- and
+    out_dir/colcomp_{i}.png (colour=False: the grey map).  inferred / references: sequences of uint8 arrays [H,W] of one shape, top row
+    first; they are uploaded `batch` pairs at a time and go through ops.compare_images.  Returns the list of image means."""
+    dev = _gpu(device)
+    n = len(inferred)
+    assert n == len(references), "as many inferred images as references"
+    os.makedirs(out_dir, exist_ok=True)
+    mode = ('colour' if colour else 'grey') if heat else None
+    means = []
+    with open(os.path.join(out_dir, "numerical_clip.csv"), "w") as f:
+        for b0 in range(0, n, batch):
+            img = torch.from_numpy(np.stack([np.asarray(a) for a in inferred[b0:b0 + batch]])).to(dev)
+            ref = torch.from_numpy(np.stack([np.asarray(a) for a in references[b0:b0 + batch]])).to(dev)
+            crop = _crop(img.shape[1], img.shape[2], rows, cols)
+            maps, sums = dr.compare_images(img, ref, mode=mode, cols=cols)
+            sums = sums.cpu().numpy()
+            maps = maps.cpu().numpy() if heat else None
+            for k in range(sums.shape[0]):
+                m, row_means = _means_of_row_sums(sums[k], crop)
+                means.append(m)
+                f.write(_csv_line(m, row_means))
+                if heat:
+                    _write_png(os.path.join(out_dir, f"colcomp_{b0 + k}.png"), maps[k])
+        f.write(_csv_last_line(means))
+    return means
+
+
+def _write_png(path, rgb):
+    from PIL import Image
+    Image.fromarray(rgb).save(path)
+
+
+def take_references(imdir):
+    """`references` of compare_result for a take on disk in the layout scene.from_take reads: frame -> [Nc,H,W] uint8, top row first,
+    unclipped (data.load_raw_image), the camera directories in sorted order as in from_take."""
+    from . import data
+    cams = sorted(os.listdir(imdir))
+    _, digits = data.assert_num_frames(cams, imdir)
+    return lambda frame: np.stack([data.load_raw_image(os.path.join(imdir, c, f"{c}_{frame:0{digits}d}.tif")) for c in cams])
+
+
+@torch.no_grad()
+def compare_result(result_dir, sc, references, out_dir, cams=None, frames=None, reproduce_pose=True, colour=True, heat=True,
+                   batch_frames=4, device='cuda', **crop):
+    """Re-render a directory written by Fitter.save() and compare it with the captures without the images leaving the GPU: the chosen
+    cameras of `batch_frames` frames are rendered at once, and the render's [0,1] output goes straight into ops.compare_images
+    (scale=255, flip_rows=True: the raster has row 0 at the bottom, the captures their top row first) -- what reaches the host is the
+    row sums and, with heat=True, the heat maps.
+
+      references  uint8 [F,Nc,H,W] indexed by frame number, top row first, or a callable frame -> [Nc,H,W] (take_references for a take
+                  on disk); camera axis in the order of `cams`
+      cams        indices into sc.cams (default: all); frames: frame numbers (default: every {i}.obj of the result)
+      crop        rows=, cols= as mean_abs_diff
+
+    Writes out_dir/numerical_clip_<cam>.csv per camera (<cam> = its index in sc.cams; one line per frame, in the format of
+    compare_sequence_numerical) and out_dir/colcomp_<cam>_<frame>.png.  Returns the image means as a float64 array [frames, cams]."""
+    dev = _gpu(device)
+    rows, cols = crop.pop('rows', (200, 1401)), crop.pop('cols', (100, 1100))
+    if crop:
+        raise TypeError(f"unknown arguments {sorted(crop)}")
+    cams = list(range(len(sc.cams))) if cams is None else [int(c) for c in cams]
+    if frames is None:
+        frames = range(len([f for f in os.listdir(result_dir) if f.endswith(".obj") and f[:-4].isdigit()]))
+    frames = list(frames)
+    H, W = sc.resolution
+    box = _crop(H, W, rows, cols)
+    os.makedirs(out_dir, exist_ok=True)
+    glctx = dr.RasterizeGLContext(device=dev)
+    pos_idx = torch.tensor(sc.pos_idx, dtype=torch.int32, device=dev)
+    uv = torch.tensor(sc.uv, dtype=torch.float32, device=dev)
+    uv_idx = torch.tensor(sc.uv_idx, dtype=torch.int32, device=dev)
+    tex = torch.tensor(read_texture(os.path.join(result_dir, "texture.png")), dtype=torch.float32, device=dev)
+    t_all, q_all = read_pose(result_dir) if reproduce_pose else (None, None)
+    proj, t_mv = _camera_matrices([sc.cams[c] for c in cams], (0.0, 170.0, 0.0), dev)
+    mode = ('colour' if colour else 'grey') if heat else None
+    Nc = len(cams)
+    means = np.empty((len(frames), Nc), dtype=np.float64)
+    lines = [[] for _ in cams]
+    for b0 in range(0, len(frames), batch_frames):
+        chunk = frames[b0:b0 + batch_frames]
+        clip, refs = [], []
+        for i in chunk:
+            verts = torch.tensor(read_result_obj(os.path.join(result_dir, f"{i}.obj")), device=dev)
+            # per frame exactly the matrices and the transform of render_multicam: the same clip-space positions, bit for bit
+            mvp = _multicam_mvp(proj, t_mv, (t_all[i], q_all[i]) if reproduce_pose else None)
+            clip.append(camera.transform_clip(mvp, verts[None]))
+            r = np.asarray(references(i) if callable(references) else references[i])
+            if r.dtype != np.uint8 or r.shape != (Nc, H, W):
+                raise ValueError(f"references of frame {i}: expected uint8 {(Nc, H, W)}, got {r.dtype} {r.shape}")
+            refs.append(r)
+        colour_img, rast = render_from_clip(glctx, torch.cat(clip), pos_idx, uv, uv_idx, tex, sc.resolution, False, 0)
+        if colour_img.shape[-1] != 1:
+            raise ValueError(f"the comparison is of one-channel images (the texture has {colour_img.shape[-1]} channels)")
+        colour_img = torch.where(rast[..., 3:] > 0, colour_img, torch.tensor(BACKGROUND, device=dev))
+        ref = torch.from_numpy(np.concatenate(refs)).to(dev)
+        maps, sums = dr.compare_images(colour_img.contiguous(), ref, mode=mode, cols=cols, scale=255.0, flip_rows=True)
+        sums = sums.cpu().numpy().reshape(len(chunk), Nc, H)
+        maps = maps.cpu().numpy().reshape(len(chunk), Nc, H, W, 3) if heat else None
+        for k, i in enumerate(chunk):
+            for j, c in enumerate(cams):
+                m, row_means = _means_of_row_sums(sums[k, j], box)
+                means[b0 + k, j] = m
+                lines[j].append(_csv_line(m, row_means))
+                if heat:
+                    _write_png(os.path.join(out_dir, f"colcomp_{c}_{i}.png"), maps[k, j])
+    for j, c in enumerate(cams):
+        with open(os.path.join(out_dir, f"numerical_clip_{c}.csv"), "w") as f:
+            f.writelines(lines[j])
+            f.write(_csv_last_line(means[:, j]))
+    return means

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define FPCDR_ABI_VERSION 13
+#define FPCDR_ABI_VERSION 14
 
 enum {
     FPCDR_OK = 0,
@@ -518,6 +518,24 @@ int fpcdr_adam_step(const fpcdr_adam_params *p, void *stream);
  * written to row i, or to row H - 1 - i when flip_rows is set.  Any H, W. */
 int fpcdr_undistort_u8(const uint8_t *src, uint8_t *dst, const double *cam_table, int64_t n_images, int H, int W, int n_cam,
                        int clip_max, int flip_rows, void *stream);
+
+/* ABI v14.  Comparison of re-rendered images with the captures (reference src/torch/comparisons.py: the per-pixel heat map of
+ * compareSequence, :36-48, and the integer differences behind the row means of compareSequenceNumerical, :64-75).
+ *   img       [n_images, H, W], one channel: float32 (img_is_float != 0) or uint8; device memory
+ *   ref       [n_images, H, W] uint8, top row first, as on disk
+ *   heat      [n_images, H, W, 3] uint8, fully overwritten; or NULL
+ *   row_sums  [n_images, H] int32, ACCUMULATED with integer atomics: the caller hands it in zero-filled; or NULL (not both NULL)
+ * For the output pixel at row i FROM THE TOP, column j ("Comparison rule"):
+ *   r = flip_rows ? H - 1 - i : i                    (the flip applies to img only: a raster has row 0 at the bottom)
+ *   q = img[n, r, j] if uint8; else x = img[n, r, j] * scale (one float32 multiply), NaN -> 0, else clip(rint(x), 0, 255), rint = round
+ *       half to even
+ *   d = q - ref[n, i, j],  s = max(255 - 2 |d|, 0)
+ *   heat[n, i, j, :] = mode 0 (colour): d >= 0 ? (255, s, s) : (s, s, 255);  mode 1 (grey): (s, s, s)
+ *   row_sums[n, i] += sum of |d| over the columns j in [col0, col1) that lie in [0, W)
+ * Integers throughout: the sums are exact and do not depend on the order of the adds.  Any H, W with 255 * W below 2^31; no buffer may
+ * overlap an output.  Row means, image means and the CSV text of the reference are the host's (float64(sum) / columns). */
+int fpcdr_compare_u8(const void *img, int img_is_float, float scale, const uint8_t *ref, uint8_t *heat, int32_t *row_sums,
+                     int64_t n_images, int H, int W, int col0, int col1, int mode, int flip_rows, void *stream);
 
 #ifdef __cplusplus
 }
