@@ -15,7 +15,7 @@ MAX_ATTR = 32
 MAX_MIP = 16
 LOSS_SLOTS = 256
 OCC_BIN = 32         # FPCDR_OCC_BIN
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 FILTER = {'nearest': 0, 'linear': 1, 'linear-mipmap-nearest': 2, 'linear-mipmap-linear': 3}
 BOUNDARY = {'wrap': 0, 'clamp': 1, 'zero': 2}
@@ -181,6 +181,8 @@ SYMBOLS = {
     "fpcdr_adam_step": (_int, [ctypes.POINTER(AdamParams), _p]),
     "fpcdr_undistort_u8": (_int, [_p, _p, _p, ctypes.c_int64, _i, _i, _i, _i, _i, _p]),
     "fpcdr_compare_u8": (_int, [_p, _int, ctypes.c_float, _p, _p, _p, ctypes.c_int64, _i, _i, _i, _i, _i, _i, _p]),
+    "fpcdr_overlay_u8": (_int, [_p, _int, ctypes.c_float, _p, _p, _p, _p, ctypes.c_int64, _i, _i, _int, _int, ctypes.c_float,
+                                ctypes.c_uint32, _int, _p]),
 }
 
 # the two-call form of the pixel objective + the fused render pair (include/fpcdr_twocall.h): exported by libfpcdr_twocall.so only

@@ -23,6 +23,7 @@ import ctypes
 import weakref
 from collections import OrderedDict
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -779,6 +780,84 @@ def compare_images(img, ref, mode='colour', cols=(100, 1100), scale=255.0, flip_
         _lib.call("fpcdr_compare_u8", _ptr(img), 1 if img.dtype == torch.float32 else 0, float(scale), _ptr(ref), _ptr(heat), _ptr(rows),
                   N, H, W, col0, col1, 1 if mode == 'grey' else 0, 1 if flip_rows else 0, _stream())
     return heat, rows
+
+
+def overlay_images(img, ref, rast=None, rast_db=None, weight=0.5, outside='render', wire=None, half_width=0.5, scale=255.0,
+                   flip_rows=False):
+    """Rendered images laid over the captures, optionally with the mesh's edges drawn (the reference's render_result_blended.py:149-154,
+    ref * 0.5 + img * 0.5 rounded and clipped; its wireframe variant paints the lines into a texture instead), by the rule of DESIGN.md 3
+    "Overlay rule" (fpcdr_overlay_u8).
+
+      img         GPU tensor [N,H,W] or [N,H,W,1], contiguous: uint8, or float32 quantised as clip(rint(img * scale), 0, 255) (NaN -> 0)
+      ref         uint8 GPU tensor [N,H,W], contiguous, top row first
+      rast        float32 [N,H,W,4] as rasterize returns it (u, v, z/w, triangle + 1), or None
+      rast_db     float32 [N,H,W,4], rasterize's second output (du/dX, du/dY, dv/dX, dv/dY), or None
+      weight      the render's share of the blend in [0, 1], taken to the nearest 1/256; the blend is rounded half to even
+      outside     'render': the blend everywhere, whatever background the caller put into img (the reference's behaviour);
+                  'capture': the capture unchanged where rast shows no triangle (needs rast)
+      wire        None, or the (r, g, b) bytes of the mesh lines (needs rast and rast_db): a covered pixel is painted where one of its
+                  triangle's barycentrics b has b * b < half_width^2 * |grad b|^2, i.e. lies within half_width pixels of an edge to
+                  first order; both triangles of a shared edge draw, so a line is 2 * half_width wide
+      flip_rows   output row i takes row H - 1 - i of img, rast and rast_db (a raster has row 0 at the bottom) and row i of ref
+
+    Returns uint8 [N,H,W,3].  rast is read only if outside='capture' or a wire asks for it, rast_db only for a wire."""
+    if outside not in ('render', 'capture'):
+        raise ValueError(f"outside must be 'render' or 'capture' (got {outside!r})")
+    tensors = [('img', img), ('ref', ref)] + [(k, v) for k, v in (('rast', rast), ('rast_db', rast_db)) if v is not None]
+    for name, t in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    for name, t in tensors:
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a GPU tensor (got {t.device}); the overlay has no CPU path")
+        if t.device != img.device:
+            raise ValueError(f"img and {name} are on different devices ({img.device}, {t.device})")
+    if img.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"img must be float32 or uint8 (got {img.dtype})")
+    if ref.dtype != torch.uint8:
+        raise ValueError(f"ref must be uint8 (got {ref.dtype})")
+    if img.dim() == 4:
+        if img.shape[3] != 1:
+            raise ValueError(f"img must have one channel (got shape {tuple(img.shape)})")
+        img = img[..., 0]
+    if img.dim() != 3 or ref.dim() != 3:
+        raise ValueError(f"img must be [N,H,W] or [N,H,W,1] and ref [N,H,W] (got shapes {tuple(img.shape)}, {tuple(ref.shape)})")
+    if img.shape != ref.shape:
+        raise ValueError(f"img {tuple(img.shape)} and ref {tuple(ref.shape)} differ in shape")
+    for name, t in tensors[2:]:
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32 (got {t.dtype})")
+        if tuple(t.shape) != tuple(img.shape) + (4,):
+            raise ValueError(f"{name} must be {tuple(img.shape) + (4,)} (got {tuple(t.shape)})")
+    if not img.is_contiguous() or not all(t.is_contiguous() for _, t in tensors[1:]):
+        raise ValueError("img, ref, rast and rast_db must be contiguous")
+    if img.numel() == 0:
+        raise ValueError("empty input")
+    weight = float(weight)
+    if not 0.0 <= weight <= 1.0:        # (false for a NaN)
+        raise ValueError(f"weight must lie in [0, 1] (got {weight})")
+    weight_256 = int(np.rint(weight * 256))
+    hw2, rgb = 0.0, 0
+    if wire is not None:
+        wire = tuple(wire)
+        if len(wire) != 3 or any(int(c) != c or not 0 <= int(c) <= 255 for c in wire):
+            raise ValueError(f"wire must be None or three bytes (r, g, b) (got {wire!r})")
+        if rast is None or rast_db is None:
+            raise ValueError("wire needs rast and rast_db (rasterize's two outputs)")
+        with np.errstate(over='ignore'):
+            hw2 = np.float32(half_width) * np.float32(half_width)
+        if not (np.isfinite(hw2) and float(half_width) >= 0.0):
+            raise ValueError(f"half_width must be finite and >= 0 (got {half_width})")
+        hw2 = float(hw2)
+        rgb = int(wire[0]) | int(wire[1]) << 8 | int(wire[2]) << 16
+    if outside == 'capture' and rast is None:
+        raise ValueError("outside='capture' needs rast")
+    N, H, W = img.shape
+    out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=img.device)
+    with torch.cuda.device(img.device):
+        _lib.call("fpcdr_overlay_u8", _ptr(img), 1 if img.dtype == torch.float32 else 0, float(scale), _ptr(ref), _ptr(rast), _ptr(rast_db),
+                  _ptr(out), N, H, W, weight_256, 1 if outside == 'capture' else 0, hw2, rgb, 1 if flip_rows else 0, _stream())
+    return out
 
 
 def pixel_objective(glctx, pos, tri, uv, uv_tri, tex, ref_u8, resolution, n_total=None, background=45.0 / 255.0,

@@ -4,6 +4,8 @@ operators.  Host-side mirror of the reference's s
 (read result/{i}.obj + texture + pose.json, render every camera, tile 3 x 3) and comparisons.py:54-81
 (mean absolute difference over a crop, one CSV line per image).  compare_sequence / compare_result are the same comparison, plus
 the heat-map images of comparisons.py:21-50, on the GPU (ops.compare_images -> fpcdr_compare_u8; DESIGN.md 3, "Comparison rule").
+overlay_sequence / overlay_result are the pictures of render_result_blended.py -- the re-render laid half-transparent over the capture,
+and the mesh's edges drawn over it -- on the GPU (ops.overlay_images -> fpcdr_overlay_u8; DESIGN.md 3, "Overlay rule").
 The reference's mp4 / GLFW output is out of scope.
 """
 import json
@@ -278,3 +280,82 @@ def compare_result(result_dir, sc, references, out_dir, cams=None, frames=None, 
             f.writelines(lines[j])
             f.write(_csv_last_line(means[:, j]))
     return means
+
+
+# ---- the re-render over the capture ------------------------------------------------------------------------------------------------
+def overlay_sequence(inferred, references, out_dir, weight=0.5, device='cuda', batch=16):
+    """The blended images of the reference's render_result_blended.py:149-154 -- np.clip(np.rint(ref * 0.5 + img * 0.5), 0, 255) at the
+    default weight -- for a sequence of image pairs, on the GPU: writes out_dir/overlay_{i}.png (grey, three equal channels).
+    inferred / references: sequences of uint8 arrays [H,W] of one shape, top row first; they are uploaded `batch` pairs at a time and go
+    through ops.overlay_images."""
+    dev = _gpu(device)
+    n = len(inferred)
+    assert n == len(references), "as many inferred images as references"
+    os.makedirs(out_dir, exist_ok=True)
+    for b0 in range(0, n, batch):
+        img = torch.from_numpy(np.stack([np.asarray(a) for a in inferred[b0:b0 + batch]])).to(dev)
+        ref = torch.from_numpy(np.stack([np.asarray(a) for a in references[b0:b0 + batch]])).to(dev)
+        out = dr.overlay_images(img, ref, weight=weight).cpu().numpy()
+        for k in range(out.shape[0]):
+            _write_png(os.path.join(out_dir, f"overlay_{b0 + k}.png"), out[k])
+
+
+@torch.no_grad()
+def overlay_result(result_dir, sc, references, out_dir, cams=None, frames=None, reproduce_pose=True, wireframe=True,
+                   wire_colour=(0, 255, 0), half_width=0.5, weight=0.5, outside='capture', batch_frames=4, device='cuda'):
+    """Re-render a directory written by Fitter.save() and lay it over the captures, with the mesh's edges drawn (wireframe=True), without
+    a float image leaving the GPU: the picture to look at first to see whether a fit sits on the face (the reference's
+    render_result_blended.py; its wireframe variant needs a painted texture, this one draws the edges from the rasteriser's
+    barycentrics and their screen derivatives).  Arguments and batching as compare_result; every frame's matrices and clip-space
+    positions are formed the same way, and the colour comes from the same unfused operator sequence as render_from_clip, so it equals
+    compare_result's bit for bit.
+
+      references   uint8 [F,Nc,H,W] indexed by frame number, top row first, or a callable frame -> [Nc,H,W]
+      wire_colour  (r, g, b) bytes of the lines; half_width: half a line's width in pixels (a line is drawn from both sides of an edge)
+      weight       the render's share of the blend; outside: 'capture' shows the capture unchanged off the mesh, 'render' blends the
+                   background colour in as the reference does
+
+    Writes out_dir/overlay_<cam>_<frame>.png (<cam> = the camera's index in sc.cams)."""
+    dev = _gpu(device)
+    cams = list(range(len(sc.cams))) if cams is None else [int(c) for c in cams]
+    if frames is None:
+        frames = range(len([f for f in os.listdir(result_dir) if f.endswith(".obj") and f[:-4].isdigit()]))
+    frames = list(frames)
+    H, W = sc.resolution
+    os.makedirs(out_dir, exist_ok=True)
+    glctx = dr.RasterizeGLContext(device=dev)
+    pos_idx = torch.tensor(sc.pos_idx, dtype=torch.int32, device=dev)
+    uv = torch.tensor(sc.uv, dtype=torch.float32, device=dev)
+    uv_idx = torch.tensor(sc.uv_idx, dtype=torch.int32, device=dev)
+    tex = torch.tensor(read_texture(os.path.join(result_dir, "texture.png")), dtype=torch.float32, device=dev)
+    t_all, q_all = read_pose(result_dir) if reproduce_pose else (None, None)
+    proj, t_mv = _camera_matrices([sc.cams[c] for c in cams], (0.0, 170.0, 0.0), dev)
+    Nc = len(cams)
+    for b0 in range(0, len(frames), batch_frames):
+        chunk = frames[b0:b0 + batch_frames]
+        clip, refs = [], []
+        for i in chunk:
+            verts = torch.tensor(read_result_obj(os.path.join(result_dir, f"{i}.obj")), device=dev)
+            # per frame exactly the matrices and the transform of render_multicam: the same clip-space positions, bit for bit
+            mvp = _multicam_mvp(proj, t_mv, (t_all[i], q_all[i]) if reproduce_pose else None)
+            clip.append(camera.transform_clip(mvp, verts[None]))
+            r = np.asarray(references(i) if callable(references) else references[i])
+            if r.dtype != np.uint8 or r.shape != (Nc, H, W):
+                raise ValueError(f"references of frame {i}: expected uint8 {(Nc, H, W)}, got {r.dtype} {r.shape}")
+            refs.append(r)
+        # the unfused operator sequence of render_from_clip, keeping the rasteriser's second output
+        pos_clip = torch.cat(clip)
+        rast, rast_db = dr.rasterize(glctx, pos_clip, pos_idx, resolution=(sc.resolution[0], sc.resolution[1]))
+        texc, _ = dr.interpolate(uv[None, ...], rast, uv_idx)
+        colour_img = dr.antialias(dr.texture(tex[None, ...], texc, filter_mode='linear'), rast, pos_clip, pos_idx)
+        if colour_img.shape[-1] != 1:
+            raise ValueError(f"the overlay is of one-channel images (the texture has {colour_img.shape[-1]} channels)")
+        colour_img = torch.where(rast[..., 3:] > 0, colour_img, torch.tensor(BACKGROUND, device=dev))
+        ref = torch.from_numpy(np.concatenate(refs)).to(dev)
+        out = dr.overlay_images(colour_img.contiguous(), ref, rast=rast.contiguous(), rast_db=rast_db.contiguous(), weight=weight,
+                                outside=outside, wire=tuple(wire_colour) if wireframe else None, half_width=half_width, scale=255.0,
+                                flip_rows=True)
+        out = out.cpu().numpy().reshape(len(chunk), Nc, H, W, 3)
+        for k, i in enumerate(chunk):
+            for j, c in enumerate(cams):
+                _write_png(os.path.join(out_dir, f"overlay_{c}_{i}.png"), out[k, j])

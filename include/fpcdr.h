@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define FPCDR_ABI_VERSION 14
+#define FPCDR_ABI_VERSION 15
 
 enum {
     FPCDR_OK = 0,
@@ -536,6 +536,31 @@ int fpcdr_undistort_u8(const uint8_t *src, uint8_t *dst, const double *cam_table
  * overlap an output.  Row means, image means and the CSV text of the reference are the host's (float64(sum) / columns). */
 int fpcdr_compare_u8(const void *img, int img_is_float, float scale, const uint8_t *ref, uint8_t *heat, int32_t *row_sums,
                      int64_t n_images, int H, int W, int col0, int col1, int mode, int flip_rows, void *stream);
+
+/* ABI v15.  Overlay of re-rendered images on the captures, with the mesh's edges drawn from the rasteriser's output (reference
+ * src/torch/render_result_blended.py:149-154: ref * 0.5 + img * 0.5, rounded and clipped; its wireframe variant, :58, :68-69, draws
+ * the lines from a painted texture instead).
+ *   img       [n_images, H, W], one channel: float32 (img_is_float != 0) or uint8; device memory
+ *   ref       [n_images, H, W] uint8, top row first, as on disk
+ *   rast      [n_images, H, W, 4] float32 (u, v, z/w, triangle + 1) as fpcdr_rasterize_fwd writes it, or NULL
+ *   rast_db   [n_images, H, W, 4] float32 (du/dX, du/dY, dv/dX, dv/dY), or NULL; wire_hw2 > 0 needs both, outside_capture needs rast
+ *   out       [n_images, H, W, 3] uint8, fully overwritten, every byte once; overlaps no input
+ *   weight_256  the render's weight in 1/256, in [0, 256];  wire_hw2: squared half width of a line in pixels, finite, 0 = no wire
+ *   wire_rgb  r | g << 8 | b << 16
+ * For the output pixel at row i FROM THE TOP, column j ("Overlay rule"):
+ *   r   = flip_rows ? H - 1 - i : i                  (the flip applies to img, rast and rast_db: a raster has row 0 at the bottom)
+ *   q   = the Comparison rule's q of img[n, r, j];  c = ref[n, i, j]
+ *   t   = weight_256 q + (256 - weight_256) c;  m = t / 256 rounded half to EVEN, in integers
+ *   cov = rast ? rast[n, r, j, 3] > 0 : true;  if (rast && outside_capture && !cov) m = c
+ *   out[n, i, j, :] = (m, m, m)
+ *   if (wire_hw2 > 0 && cov):  (u, v) = rast[n, r, j, 0..1], (ux, uy, vx, vy) = rast_db[n, r, j, :], s = (1 - u) - v,
+ *       b2 = s < 0 ? 0 : s, gx = ux + vx, gy = uy + vy, on(b, x, y) := b b < wire_hw2 ((x x) + (y y)) in unfused float32;
+ *       if (on(u, ux, uy) || on(v, vx, vy) || on(b2, gx, gy)) out[n, i, j, :] = wire_rgb
+ * rast is not read when neither a wire nor outside_capture asks for it, rast_db only for covered pixels of a call with a wire.  Any H,
+ * W; float buffers 4-byte aligned (16-byte accesses where the addresses allow). */
+int fpcdr_overlay_u8(const void *img, int img_is_float, float scale, const uint8_t *ref, const float *rast, const float *rast_db,
+                     uint8_t *out, int64_t n_images, int H, int W, int weight_256, int outside_capture, float wire_hw2,
+                     uint32_t wire_rgb, int flip_rows, void *stream);
 
 #ifdef __cplusplus
 }
