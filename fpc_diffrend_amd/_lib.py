@@ -15,7 +15,7 @@ MAX_ATTR = 32
 MAX_MIP = 16
 LOSS_SLOTS = 256
 OCC_BIN = 32         # FPCDR_OCC_BIN
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 FILTER = {'nearest': 0, 'linear': 1, 'linear-mipmap-nearest': 2, 'linear-mipmap-linear': 3}
 BOUNDARY = {'wrap': 0, 'clamp': 1, 'zero': 2}
@@ -118,6 +118,12 @@ class PixelLoss(ctypes.Structure):
                 ("loss_sum", _p), ("grad_color", _p)]
 
 
+class BlurLoss(ctypes.Structure):
+    _fields_ = [("color", _p), ("rast", _p), ("ref", _p), ("B", _i), ("H", _i), ("W", _i), ("C", _i),
+                ("bg", ctypes.c_float), ("color_scale", ctypes.c_float), ("grad_scale", ctypes.c_float), ("radius", _i),
+                ("taps", ctypes.c_float * 64), ("tmp", _p), ("blurred", _p), ("loss_sum", _p), ("grad_color", _p)]
+
+
 ADAM_MAX_TENSORS = 16     # FPCDR_ADAM_MAX_TENSORS
 
 
@@ -178,6 +184,8 @@ SYMBOLS = {
     "fpcdr_rig_weights_fwd": (_int, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "fpcdr_rig_weights_bwd": (_int, [_p, _p, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p]),
     "fpcdr_pixel_loss": (_int, [ctypes.POINTER(PixelLoss), _p]),
+    "fpcdr_blur_loss_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "fpcdr_blur_loss": (_int, [ctypes.POINTER(BlurLoss), _p]),
     "fpcdr_adam_step": (_int, [ctypes.POINTER(AdamParams), _p]),
     "fpcdr_undistort_u8": (_int, [_p, _p, _p, ctypes.c_int64, _i, _i, _i, _i, _i, _p]),
     "fpcdr_compare_u8": (_int, [_p, _int, ctypes.c_float, _p, _p, _p, ctypes.c_int64, _i, _i, _i, _i, _i, _i, _p]),

@@ -274,6 +274,14 @@ def pixel_loss_fused(colour, rast_out, ref_u8, n_total=None):
     return acc, grad
 
 
+def pixel_loss_blurred(colour, rast_out, ref_u8, taps, n_total=None):
+    """pixel_loss_fused with the residual Gaussian-blurred before it is squared ("Blurred loss rule"; fpcdr_blur_loss):
+    returns (sum E^2 [1] f64 tensor, d mean / d colour [B,H,W,C]) with mean over n_total elements."""
+    n_total = n_total or colour.numel()
+    acc, grad, _ = dr.blur_loss_call(colour, rast_out, ref_u8, taps, 1.0 / n_total, BACKGROUND)
+    return acc, grad
+
+
 class _mvp_func(torch.autograd.Function):
     """Model-view-projection matrices of a minibatch in one kernel each way (fpcdr_mvp_fwd / _bwd)."""
 
@@ -731,6 +739,13 @@ class FitConfig:
                                     # the reference's one-image steps, 1.6 -> 0.9 ms; not the 288-image batch)
     shading: str = "texture"        # 'texture' = reference render(); 'vertex' = rasterize + interpolate of a per-vertex
                                     # grey only (BASELINE.json configs[1]: "raster+interp only, no texture")
+    blur_sigma: float = 0.0         # > 0: the pixel term is the mean square of the Gaussian-BLURRED residual (fit.pixel_loss_blurred;
+                                    # DESIGN.md 3, "Blurred loss rule") on the operator path: every pixel within the kernel's radius of a
+                                    # silhouette pulls on it, so a start several pixels off converges.  0 = off: nothing changes
+    blur_sigma_end: Optional[float] = None   # with a value: sigma goes geometrically from blur_sigma to it over the blurred iterations
+    blur_kernel_size: int = 31      # odd, 3 .. 63 (the reference's GaussianBlur(kernel_size=(31, 31)), fit.py:506)
+    blur_iters: int = 0             # 0 = every iteration is blurred; n = iterations i < n, then the run continues on the path the other
+                                    # flags select (the one-pass objective by default)
     log_interval: int = 0           # every n steps one JSON line {it, loss, lr, frames_per_s} (reference print, fit.py:621-623)
     reg_log_interval: int = 500     # every n steps the regulariser breakdown MEL / LAP / MNC (reference fit.py:597-601)
     log_path: Optional[str] = None  # JSON-lines file (appended); None with log_interval > 0 = stdout
@@ -820,6 +835,15 @@ class Fitter:
                   {"params": self.maps_intermediate['local'], 'lr': cfg.lr_base}, {"params": self.t_opt, 'lr': cfg.lr_t},
                   {"params": self.q_opt, 'lr': cfg.lr_q}, {"params": self.per_frame_t, 'lr': cfg.lr_t},
                   {"params": self.per_frame_q, 'lr': cfg.lr_q}, {"params": self.tex_opt, 'lr': cfg.lr_base * cfg.lr_tex_coef}]
+        if cfg.blur_sigma > 0:
+            if not cfg.fused_loss:
+                raise ValueError("FitConfig.blur_sigma > 0 needs fused_loss=True: the blurred loss replaces pixel_loss_fused")
+            if cfg.hip_graph:
+                raise ValueError("FitConfig.blur_sigma > 0 cannot be combined with hip_graph: sigma and the switch back to the one-pass "
+                                 "objective change from one iteration to the next")
+            dr.gaussian_taps(cfg.blur_kernel_size, cfg.blur_sigma)                       # (raises for a bad kernel size or sigma)
+            if cfg.blur_sigma_end is not None:
+                dr.gaussian_taps(cfg.blur_kernel_size, cfg.blur_sigma_end)
         if cfg.hip_graph == 'auto':
             self.use_graph = self.auto_graph((cfg.frames_per_step or (self.frame_hi - self.frame_lo)) * (cfg.views_per_step or len(self.cam_idxs)),
                                              self.resolution)
@@ -1066,6 +1090,19 @@ class Fitter:
             for m in (self.m1, self.m2, self.m3):
                 m.requires_grad = True
 
+    def blur_taps(self, i=None):
+        """The taps of the blurred pixel loss at iteration i (default: the current one), or None when that iteration is not blurred.
+        A function of the iteration alone, so a resumed run continues on the right side of the switch."""
+        cfg = self.cfg
+        i = self.iteration if i is None else i
+        if not cfg.blur_sigma > 0 or (cfg.blur_iters and i >= cfg.blur_iters):
+            return None
+        sigma = float(cfg.blur_sigma)
+        if cfg.blur_sigma_end is not None:
+            n = cfg.blur_iters or cfg.max_iter
+            sigma = sigma * (float(cfg.blur_sigma_end) / sigma) ** (min(i, n - 1) / max(n - 1, 1))
+        return dr.gaussian_taps(cfg.blur_kernel_size, sigma)
+
     def loss_and_backward(self, frame_ids, view_ids=None, validate=True):
         """Forward + backward of fit.py:556-611 for a batch of frames x cameras (view_ids: see mvp).  Returns the loss (tensor).
         validate: check a caller's index tensors on the host first (check_indices); step() passes False for its own draws."""
@@ -1080,6 +1117,9 @@ class Fitter:
         # (the mip branch of the reference's render(), fit.py:153-155, runs inside the same kernels)
         one_shot = (cfg.fused_objective and cfg.fused_render and cfg.fused_loss and C in (1, 3, 4) and cfg.shading == 'texture'
                     and (not cfg.enable_mip or cfg.sparse_objective))
+        blur_taps = self.blur_taps(i) if cfg.blur_sigma > 0 else None
+        if blur_taps is not None:
+            one_shot = False           # the blurred loss needs the image in memory: the operator path
         # one flat buffer for the small accumulators of this step's backward kernels, zero-filled by the objective's first kernel; the
         # pool around it goes to the functions whose backward takes views of it
         zero_buf, pool = None, None
@@ -1193,7 +1233,10 @@ class Fitter:
                     main_stream.wait_stream(self._side_stream)
                 loss = loss + lap.detach()
         elif cfg.fused_loss:
-            sum_sq, g_colour = pixel_loss_fused(colour, rast_out, ref, n_total)
+            if blur_taps is not None:
+                sum_sq, g_colour = pixel_loss_blurred(colour, rast_out, ref, blur_taps, n_total)
+            else:
+                sum_sq, g_colour = pixel_loss_fused(colour, rast_out, ref, n_total)
             roots, seeds = [colour], [g_colour]
             for term in (reg, lap):
                 if term is not None and term.requires_grad:

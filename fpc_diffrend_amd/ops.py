@@ -29,7 +29,8 @@ import torch
 from . import _lib
 
 __all__ = ['RasterizeGLContext', 'RasterizeCudaContext', 'RasterizeHipContext', 'rasterize', 'interpolate', 'texture',
-           'texture_construct_mip', 'antialias', 'antialias_construct_topology_hash', 'render_textured', 'pixel_objective', 'undistort_images', 'compare_images']
+           'texture_construct_mip', 'antialias', 'antialias_construct_topology_hash', 'render_textured', 'pixel_objective', 'undistort_images', 'compare_images',
+           'gaussian_taps', 'blurred_pixel_loss']
 
 
 def _stream():
@@ -690,6 +691,73 @@ def reference_background_sumsq(ref_u8, background=45.0 / 255.0):
     _lib.call("fpcdr_ref_bg_sumsq", _ptr(ref_u8), ref_u8.shape[0], ref_u8.shape[1] * ref_u8.shape[2], float(background) * 255.0,
               _ptr(out), _stream())
     return out
+
+
+def gaussian_taps(kernel_size, sigma):
+    """The taps of the blurred pixel loss ("Blurred loss rule"): g_i = exp(-((i - r) / sigma)^2 / 2), r = (k - 1) / 2, in
+    float64, divided by their sum, rounded to float32 -- a CPU tensor [k].  (torchvision's GaussianBlur kernel as recalled; torchvision
+    draws sigma at random per call when none is given, here it is always explicit.  Parity with torchvision is not pinned by a test.)"""
+    k = int(kernel_size)
+    if k != kernel_size or k % 2 == 0 or not 3 <= k <= 63:
+        raise ValueError(f"kernel_size must be odd and in 3 .. 63 (got {kernel_size})")
+    if not float(sigma) > 0.0:
+        raise ValueError(f"sigma must be positive (got {sigma})")
+    x = (np.arange(k, dtype=np.float64) - (k - 1) // 2) / float(sigma)
+    g = np.exp(-0.5 * x * x)
+    return torch.from_numpy((g / g.sum()).astype(np.float32))
+
+
+def blur_loss_call(colour, rast, ref_u8, taps, grad_scale, background=45.0 / 255.0, want_grad=True):
+    """One fpcdr_blur_loss call: -> (sum E^2 [1] f64, grad_scale * d sum / d colour [B,H,W,C] or None, E [B,H,W,C])."""
+    _check_tensor('colour', colour, torch.float32, 4)
+    _check_tensor('rast', rast, torch.float32, 4)
+    _check_tensor('ref_u8', ref_u8, torch.uint8, 3)
+    B, H, W, C = colour.shape
+    if tuple(rast.shape) != (B, H, W, 4) or tuple(ref_u8.shape) != (B, H, W):
+        raise ValueError(f"rast must be [B,H,W,4] and ref_u8 [B,H,W] for colour {tuple(colour.shape)}")
+    taps = torch.as_tensor(taps, dtype=torch.float32).detach().cpu().reshape(-1)
+    k = taps.numel()
+    if k % 2 == 0 or not 3 <= k <= 63:
+        raise ValueError(f"the number of taps must be odd and in 3 .. 63 (got {k})")
+    r = (k - 1) // 2
+    if r >= min(H, W):
+        raise ValueError(f"reflected borders need (kernel_size - 1) / 2 < min(H, W) (got kernel size {k} for {H} x {W})")
+    colour, rast, ref_u8 = colour.detach().contiguous(), rast.detach().contiguous(), ref_u8.contiguous()
+    with torch.cuda.device(colour.device):
+        acc = torch.zeros(1, dtype=torch.float64, device=colour.device)
+        tmp, blurred = torch.empty_like(colour), torch.empty_like(colour)
+        grad = torch.empty_like(colour) if want_grad else None
+        p = _lib.BlurLoss(color=_ptr(colour), rast=_ptr(rast), ref=_ptr(ref_u8), B=B, H=H, W=W, C=C, bg=float(background),
+                          color_scale=255.0, grad_scale=float(grad_scale), radius=r, tmp=_ptr(tmp), blurred=_ptr(blurred),
+                          loss_sum=_ptr(acc), grad_color=_ptr(grad))
+        for t in range(k):
+            p.taps[t] = float(taps[t])
+        _lib.call("fpcdr_blur_loss", ctypes.byref(p), _stream())
+    return acc, grad, blurred
+
+
+class _blurred_pixel_loss_func(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, colour, rast, ref_u8, taps, n_total, background):
+        acc, grad, _ = blur_loss_call(colour, rast, ref_u8, taps, 1.0 / n_total, background, want_grad=True)
+        ctx.save_for_backward(grad)
+        return (acc[0] / n_total).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        return grad * upstream, None, None, None, None, None
+
+
+def blurred_pixel_loss(colour, rast, ref_u8, sigma=None, kernel_size=31, n_total=None, background=45.0 / 255.0, taps=None):
+    """mean over n_total elements (default: all of colour) of E^2, E = the Gaussian-blurred residual ref - 255 * (rast.w > 0 ? colour :
+    background) with reflected borders ("Blurred loss rule"; fpcdr_blur_loss) -- a float32 scalar whose backward is the
+    closed-form gradient the same call computed, times the upstream scalar.  taps= (odd, 3 .. 63 entries) overrides sigma and kernel_size."""
+    if taps is None:
+        if sigma is None:
+            raise ValueError("blurred_pixel_loss needs sigma (or taps)")
+        taps = gaussian_taps(kernel_size, sigma)
+    return _blurred_pixel_loss_func.apply(colour, rast, ref_u8, taps, float(n_total or colour.numel()), background)
 
 
 def undistort_images(images, intr, dist, clip_max=255, flip_rows=False):
