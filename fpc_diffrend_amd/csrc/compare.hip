@@ -4,29 +4,14 @@
 // uint8: as it is), flip ITS rows if asked, difference against the capture, heat-map colour from the difference, and the sum of
 // |difference| of every row over a column crop -- integers throughout, bit for bit the numpy statement of tests/compare_ref.py.
 //
-// One thread owns 16 consecutive pixels of one output row: one 16-byte load of the capture, four 16-byte loads of a float image (one of
-// a uint8 image), and the 48 heat-map bytes as THREE 16-byte stores where the address allows (16-byte stores reach
-// 5-6 TB/s, 4- and 8-byte ones 1-1.7); a row tail (W not a multiple of 16) or an unaligned row goes in and out element by element.
+// One thread owns 16 consecutive pixels of one output row, read and written in the two forms of u8_chunk.h: one 16-byte load of the
+// capture, four of a float image (one of a uint8 image), the 48 heat-map bytes as three 16-byte stores.
 // Row sums: the 256 chunks of a workgroup are consecutive in (row, column) order, so they span at most 256 rows: an LDS table of those
 // rows takes one integer ds_add per thread with something to add, and is flushed with ONE global integer atomic per touched row and
 // workgroup.  Integer adds commute: the sums do not depend on the order of arrival.  No private segment.
-#include "common.h"
+#include "u8_chunk.h"
 
 namespace {
-
-// float -> 8 bit by the rule: x = v * scale in float32 (the library is built with -ffp-contract=off, and there is nothing to fuse with);
-// NaN -> 0; rintf is round-half-to-even (v_rndne_f32); +-inf clip like any other value
-__device__ __forceinline__ uint32_t quantise(float v, float scale) {
-    const float x = v * scale;
-    float y = rintf(x);
-    y = y < 0.0f ? 0.0f : y;
-    y = y > 255.0f ? 255.0f : y;
-    y = x != x ? 0.0f : y;
-    return (uint32_t)y;
-}
-__device__ __forceinline__ uint32_t quantise4(float4 v, float scale) {
-    return quantise(v.x, scale) | quantise(v.y, scale) << 8 | quantise(v.z, scale) << 16 | quantise(v.w, scale) << 24;
-}
 
 // four pixels (bytes of q and r) -> their |d| inside the crop added to `sum`, their 12 heat-map bytes in w0..w2
 template <int MODE>
@@ -66,58 +51,16 @@ __global__ void __launch_bounds__(256) k_compare_u8(const void *__restrict__ img
 
     int sum = 0;
     if (live) {
-        // ---- the capture: row i ----
+        // the capture: row i.  The rendered image: row i, or H - 1 - i of a raster with row 0 at the bottom.  Pixels past W stay 0 in
+        // both: d = 0
         uint32_t rw[4] = {0u, 0u, 0u, 0u}, qw[4] = {0u, 0u, 0u, 0u};
-        const uint8_t *rp = ref + (n * H + i) * W + j0;
-        if (whole && ((size_t)rp & 15) == 0) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(rp);
-            rw[0] = v.x; rw[1] = v.y; rw[2] = v.z; rw[3] = v.w;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                if (j0 + k < W) rw[k >> 2] |= (uint32_t)rp[k] << (8 * (k & 3));
-        }
-        // ---- the rendered image: row i, or H - 1 - i of a raster with row 0 at the bottom.  Pixels past W stay 0 in both: d = 0 ----
-        const long long ioff = (n * H + (flip_rows ? H - 1 - i : i)) * W + j0;
-        if (IS_FLOAT) {
-            const float *ip = static_cast<const float *>(img_) + ioff;
-            if (whole && ((size_t)ip & 15) == 0) {
-                const float4 *ip4 = reinterpret_cast<const float4 *>(ip);
-                const float4 a = ip4[0], b = ip4[1], c = ip4[2], d = ip4[3];
-                qw[0] = quantise4(a, scale); qw[1] = quantise4(b, scale); qw[2] = quantise4(c, scale); qw[3] = quantise4(d, scale);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 16; ++k)
-                    if (j0 + k < W) qw[k >> 2] |= quantise(ip[k], scale) << (8 * (k & 3));
-            }
-        } else {
-            const uint8_t *ip = static_cast<const uint8_t *>(img_) + ioff;
-            if (whole && ((size_t)ip & 15) == 0) {
-                const uint4 v = *reinterpret_cast<const uint4 *>(ip);
-                qw[0] = v.x; qw[1] = v.y; qw[2] = v.z; qw[3] = v.w;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 16; ++k)
-                    if (j0 + k < W) qw[k >> 2] |= (uint32_t)ip[k] << (8 * (k & 3));
-            }
-        }
+        load_chunk_u8(ref + (n * H + i) * W + j0, whole, j0, W, rw);
+        load_chunk_render<IS_FLOAT>(img_, (n * H + (flip_rows ? H - 1 - i : i)) * W + j0, scale, whole, j0, W, qw);
         // ---- differences, heat-map bytes ----
         uint32_t w[12];
 #pragma unroll
         for (int g = 0; g < 4; ++g) compare4<MODE>(qw[g], rw[g], j0 + 4 * g, c0, c1, sum, w[3 * g], w[3 * g + 1], w[3 * g + 2]);
-        if (heat) {
-            uint8_t *hp = heat + ((n * H + i) * W + j0) * 3;
-            if (whole && ((size_t)hp & 15) == 0) {
-                uint4 *hp4 = reinterpret_cast<uint4 *>(hp);
-                hp4[0] = make_uint4(w[0], w[1], w[2], w[3]);
-                hp4[1] = make_uint4(w[4], w[5], w[6], w[7]);
-                hp4[2] = make_uint4(w[8], w[9], w[10], w[11]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 48; ++k)
-                    if (j0 + k / 3 < W) hp[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-            }
-        }
+        if (heat) store_chunk_rgb(heat + ((n * H + i) * W + j0) * 3, whole, j0, W, w);
     }
     // ---- row sums: LDS table of the rows this workgroup's chunks span, one global atomic per touched row ----
     if (row_sums) {        // (uniform: the barriers are reached by every thread or by none)
@@ -128,12 +71,6 @@ __global__ void __launch_bounds__(256) k_compare_u8(const void *__restrict__ img
         const int v = rows_lds[threadIdx.x];     // (slot k = row i_first + k; a slot past the workgroup's last row was never added to)
         if (v != 0) atomicAdd(row_sums + n * H + i_first + (int)threadIdx.x, v);
     }
-}
-
-// [a, a + na) and [b, b + nb) share a byte
-inline bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a != nullptr && b != nullptr && x < y + nb && y < x + na;
 }
 
 }  // namespace
@@ -157,11 +94,10 @@ extern "C" int fpcdr_compare_u8(const void *img, int img_is_float, float scale, 
     const unsigned bx = (unsigned)fpcdr_cdiv((long long)H * Wc, 256);
     auto kern = img_is_float ? (mode == 0 ? k_compare_u8<true, 0> : k_compare_u8<true, 1>)
                              : (mode == 0 ? k_compare_u8<false, 0> : k_compare_u8<false, 1>);
-    for (int64_t n0 = 0; n0 < n_images; n0 += 65535) {      // (gridDim.y)
-        const int64_t ny = n_images - n0 < 65535 ? n_images - n0 : 65535;
-        hipLaunchKernelGGL(kern, dim3(bx, (unsigned)ny), dim3(256), 0, (hipStream_t)stream, img, scale, ref, heat, row_sums, (long long)n0,
-                           H, W, by_wc, c0, c1, flip_rows ? 1 : 0);
-    }
+    for_image_batches(n_images, [&](long long n0, unsigned ny) {
+        hipLaunchKernelGGL(kern, dim3(bx, ny), dim3(256), 0, (hipStream_t)stream, img, scale, ref, heat, row_sums, n0, H, W, by_wc, c0, c1,
+                           flip_rows ? 1 : 0);
+    });
     FPCDR_CHECK_LAUNCH();
     return FPCDR_OK;
 }

@@ -7,10 +7,9 @@
 // tests/overlay_ref.py.
 //
 // Two decompositions of the same 16-pixel chunks meet in one kernel, because the inputs come in two widths:
-//   * img, ref and out are 4, 1 and 3 bytes a pixel.  As in k_compare_u8 one thread OWNS 16 consecutive pixels of one output row: four
-//     16-byte loads of a float render (one of a uint8 one), one 16-byte load of the capture and the 48 output bytes as THREE 16-byte
-//     stores where the address allows (16-byte stores reach 5-6 TB/s, 4- and 8-byte ones 1-1.7); a row tail (W not a
-//     multiple of 16) or an unaligned row goes in and out element by element.
+//   * img, ref and out are 4, 1 and 3 bytes a pixel.  As in k_compare_u8 one thread OWNS 16 consecutive pixels of one output row, read
+//     and written in the two forms of u8_chunk.h: four 16-byte loads of a float render (one of a uint8 one), one 16-byte load of the
+//     capture and the 48 output bytes as three 16-byte stores.
 //   * rast and rast_db are 16 bytes a pixel.  A thread that read them for its own 16 pixels would put the lanes of one load 256 bytes
 //     apart.  Instead the wave walks its 64 chunks four at a time: in trip k lane l takes pixel l & 15 of chunk 4 k + (l >> 4), so the 16
 //     lanes of a chunk read 256 consecutive bytes in one instruction (1 KiB a wave where the four chunks lie in one row).  The lane
@@ -22,22 +21,9 @@
 // What is read is decided by template arguments and uniform branches, not by lanes: RAST = 0 reads neither raster input (no wire, and
 // nothing to keep off the mesh), RAST = 1 reads rast only (outside_capture without a wire), RAST = 2 reads rast and, for covered
 // pixels, rast_db.  Every output byte is written once with a plain store; no atomics, no LDS, no private segment.
-#include "common.h"
+#include "u8_chunk.h"
 
 namespace {
-
-// float -> 8 bit by the Comparison rule: x = v * scale in float32, NaN -> 0, rintf = round half to even, +-inf clip like any value
-__device__ __forceinline__ uint32_t quantise(float v, float scale) {
-    const float x = v * scale;
-    float y = rintf(x);
-    y = y < 0.0f ? 0.0f : y;
-    y = y > 255.0f ? 255.0f : y;
-    y = x != x ? 0.0f : y;
-    return (uint32_t)y;
-}
-__device__ __forceinline__ uint32_t quantise4(float4 v, float scale) {
-    return quantise(v.x, scale) | quantise(v.y, scale) << 8 | quantise(v.z, scale) << 16 | quantise(v.w, scale) << 24;
-}
 
 // four floats at p: one 16-byte load, or four 4-byte ones where the base is not 16-byte aligned (`aligned` is uniform)
 __device__ __forceinline__ float4 load4(const float *p, bool aligned) {
@@ -132,64 +118,17 @@ __global__ void __launch_bounds__(256) k_overlay_u8(const void *__restrict__ img
     const int i = (int)fpcdr_divide(t, by_wc);
     const int j0 = (int)(t - (unsigned)i * Wc) * 16;
     const bool whole = j0 + 16 <= W;
-    // ---- the capture: row i ----
+    // the capture: row i.  The rendered image: row i, or H - 1 - i of a raster with row 0 at the bottom.  Pixels past W are not written
     uint32_t cw[4] = {0u, 0u, 0u, 0u}, qw[4] = {0u, 0u, 0u, 0u};
-    const uint8_t *cp = ref + (n * H + i) * W + j0;
-    if (whole && ((size_t)cp & 15) == 0) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(cp);
-        cw[0] = v.x; cw[1] = v.y; cw[2] = v.z; cw[3] = v.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 16; ++k)
-            if (j0 + k < W) cw[k >> 2] |= (uint32_t)cp[k] << (8 * (k & 3));
-    }
-    // ---- the rendered image: row i, or H - 1 - i of a raster with row 0 at the bottom.  Pixels past W are not written ----
-    const long long ioff = (n * H + (flip_rows ? H - 1 - i : i)) * W + j0;
-    if (IS_FLOAT) {
-        const float *ip = static_cast<const float *>(img_) + ioff;
-        if (whole && ((size_t)ip & 15) == 0) {
-            const float4 *ip4 = reinterpret_cast<const float4 *>(ip);
-            const float4 a = ip4[0], b = ip4[1], c = ip4[2], d = ip4[3];
-            qw[0] = quantise4(a, scale); qw[1] = quantise4(b, scale); qw[2] = quantise4(c, scale); qw[3] = quantise4(d, scale);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                if (j0 + k < W) qw[k >> 2] |= quantise(ip[k], scale) << (8 * (k & 3));
-        }
-    } else {
-        const uint8_t *ip = static_cast<const uint8_t *>(img_) + ioff;
-        if (whole && ((size_t)ip & 15) == 0) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(ip);
-            qw[0] = v.x; qw[1] = v.y; qw[2] = v.z; qw[3] = v.w;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                if (j0 + k < W) qw[k >> 2] |= (uint32_t)ip[k] << (8 * (k & 3));
-        }
-    }
+    load_chunk_u8(ref + (n * H + i) * W + j0, whole, j0, W, cw);
+    load_chunk_render<IS_FLOAT>(img_, (n * H + (flip_rows ? H - 1 - i : i)) * W + j0, scale, whole, j0, W, qw);
     // ---- blend, coverage, wire: the 48 output bytes ----
     uint32_t w[12];
 #pragma unroll
     for (int g = 0; g < 4; ++g)
         overlay4<RAST>(qw[g], cw[g], weight, covbits >> (4 * g), wirebits >> (4 * g), outside_capture != 0, wire_rgb, w[3 * g], w[3 * g + 1],
                        w[3 * g + 2]);
-    uint8_t *op = out + ((n * H + i) * W + j0) * 3;
-    if (whole && ((size_t)op & 15) == 0) {
-        uint4 *op4 = reinterpret_cast<uint4 *>(op);
-        op4[0] = make_uint4(w[0], w[1], w[2], w[3]);
-        op4[1] = make_uint4(w[4], w[5], w[6], w[7]);
-        op4[2] = make_uint4(w[8], w[9], w[10], w[11]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 48; ++k)
-            if (j0 + k / 3 < W) op[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-    }
-}
-
-// [a, a + na) and [b, b + nb) share a byte
-inline bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a != nullptr && b != nullptr && x < y + nb && y < x + na;
+    store_chunk_rgb(out + ((n * H + i) * W + j0) * 3, whole, j0, W, w);
 }
 
 template <bool IS_FLOAT>
@@ -222,11 +161,10 @@ extern "C" int fpcdr_overlay_u8(const void *img, int img_is_float, float scale, 
     const fpcdr_div by_wc = fpcdr_make_div((uint32_t)Wc);
     const unsigned bx = (unsigned)fpcdr_cdiv((long long)H * Wc, 256);
     auto kern = img_is_float ? pick<true>(rast_mode) : pick<false>(rast_mode);
-    for (int64_t n0 = 0; n0 < n_images; n0 += 65535) {      // (gridDim.y)
-        const int64_t ny = n_images - n0 < 65535 ? n_images - n0 : 65535;
-        hipLaunchKernelGGL(kern, dim3(bx, (unsigned)ny), dim3(256), 0, (hipStream_t)stream, img, scale, ref, rast, rast_db, out,
-                           (long long)n0, H, W, by_wc, weight_256, outside_capture ? 1 : 0, wire_hw2, wire_rgb, flip_rows ? 1 : 0);
-    }
+    for_image_batches(n_images, [&](long long n0, unsigned ny) {
+        hipLaunchKernelGGL(kern, dim3(bx, ny), dim3(256), 0, (hipStream_t)stream, img, scale, ref, rast, rast_db, out, n0, H, W, by_wc,
+                           weight_256, outside_capture ? 1 : 0, wire_hw2, wire_rgb, flip_rows ? 1 : 0);
+    });
     FPCDR_CHECK_LAUNCH();
     return FPCDR_OK;
 }

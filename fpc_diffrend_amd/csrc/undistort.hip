@@ -6,7 +6,7 @@
 // One thread produces 16 consecutive output bytes of one row and writes them with ONE 16-byte store where the address allows (DESIGN.md
 // 4.2: 16-byte stores reach 5-6 TB/s, 4- and 8-byte ones 1-1.7); a row tail (W not a multiple of 16) or an unaligned row goes out byte
 // by byte.  No private segment, no LDS.
-#include "common.h"
+#include "u8_chunk.h"
 
 namespace {
 
@@ -97,11 +97,10 @@ extern "C" int fpcdr_undistort_u8(const uint8_t *src, uint8_t *dst, const double
     const int Wc = fpcdr_cdiv(W, 16);
     FPCDR_REQUIRE((long long)H * Wc <= (1LL << 31) - 256, "image too large");
     const unsigned bx = (unsigned)fpcdr_cdiv((long long)H * Wc, 256);
-    for (int64_t n0 = 0; n0 < n_images; n0 += 65535) {      // (gridDim.y)
-        const int64_t ny = n_images - n0 < 65535 ? n_images - n0 : 65535;
-        hipLaunchKernelGGL(k_undistort_u8, dim3(bx, (unsigned)ny), dim3(256), 0, (hipStream_t)stream, src, dst, cam_table, (long long)n0, H, W,
-                           Wc, n_cam, clip_max, flip_rows);
-    }
+    for_image_batches(n_images, [&](long long n0, unsigned ny) {
+        hipLaunchKernelGGL(k_undistort_u8, dim3(bx, ny), dim3(256), 0, (hipStream_t)stream, src, dst, cam_table, n0, H, W, Wc, n_cam, clip_max,
+                           flip_rows);
+    });
     FPCDR_CHECK_LAUNCH();
     return FPCDR_OK;
 }

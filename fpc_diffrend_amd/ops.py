@@ -798,28 +798,20 @@ def undistort_images(images, intr, dist, clip_max=255, flip_rows=False):
     return out
 
 
-def compare_images(img, ref, mode='colour', cols=(100, 1100), scale=255.0, flip_rows=False, want_rows=True):
-    """Rendered images against captures (the reference's comparisons.py: compareSequence's heat map and the integer differences behind
-    compareSequenceNumerical's row means), by the rule of DESIGN.md 3 "Comparison rule" (fpcdr_compare_u8).
-
-      img        GPU tensor [N,H,W] or [N,H,W,1], contiguous: uint8, or float32 quantised as clip(rint(img * scale), 0, 255) (NaN -> 0)
-      ref        uint8 GPU tensor [N,H,W], contiguous, top row first
-      mode       'colour' (d >= 0: (255, s, s), d < 0: (s, s, 255), s = max(255 - 2 |d|, 0)), 'grey' ((s, s, s)), or None: no heat map
-      cols       (col0, col1): the row sums run over the columns [col0, col1) inside the image
-      flip_rows  output row i compares img's row H - 1 - i (a raster has row 0 at the bottom) with ref's row i
-      want_rows  False: no row sums
-
-    Returns (heat uint8 [N,H,W,3] or None, row_sums int32 [N,H] or None): sums of |d|, exact; the means are the caller's."""
-    if mode not in ('colour', 'grey', None):
-        raise ValueError(f"mode must be 'colour', 'grey' or None (got {mode!r})")
-    if mode is None and not want_rows:
-        raise ValueError("neither a heat map (mode) nor row sums (want_rows) requested")
-    if not isinstance(img, torch.Tensor) or not isinstance(ref, torch.Tensor):
-        raise TypeError("img and ref must be torch.Tensors")
-    if not img.is_cuda or not ref.is_cuda:
-        raise ValueError(f"img and ref must be GPU tensors (got {img.device}, {ref.device}); the comparison has no CPU path")
-    if img.device != ref.device:
-        raise ValueError(f"img and ref are on different devices ({img.device}, {ref.device})")
+def _check_image_pair(what, img, ref, others=()):
+    """The (render, capture) pair of compare_images / overlay_images (`what`: the operator's noun for the messages): img a float32 or
+    uint8 GPU tensor [N,H,W] or [N,H,W,1], ref a uint8 one [N,H,W] on the same device, both contiguous and not empty.  others: further
+    (name, tensor) inputs of the call, which must be tensors on that device too -- the rest about them is the caller's.  Returns img as
+    [N,H,W]."""
+    tensors = [('img', img), ('ref', ref)] + list(others)
+    for name, t in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    for name, t in tensors:
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a GPU tensor (got {t.device}); the {what} has no CPU path")
+        if t.device != img.device:
+            raise ValueError(f"img and {name} are on different devices ({img.device}, {t.device})")
     if img.dtype not in (torch.float32, torch.uint8):
         raise ValueError(f"img must be float32 or uint8 (got {img.dtype})")
     if ref.dtype != torch.uint8:
@@ -836,6 +828,26 @@ def compare_images(img, ref, mode='colour', cols=(100, 1100), scale=255.0, flip_
         raise ValueError("img and ref must be contiguous")
     if img.numel() == 0:
         raise ValueError("empty input")
+    return img
+
+
+def compare_images(img, ref, mode='colour', cols=(100, 1100), scale=255.0, flip_rows=False, want_rows=True):
+    """Rendered images against captures (the reference's comparisons.py: compareSequence's heat map and the integer differences behind
+    compareSequenceNumerical's row means), by the rule of DESIGN.md 3 "Comparison rule" (fpcdr_compare_u8).
+
+      img        GPU tensor [N,H,W] or [N,H,W,1], contiguous: uint8, or float32 quantised as clip(rint(img * scale), 0, 255) (NaN -> 0)
+      ref        uint8 GPU tensor [N,H,W], contiguous, top row first
+      mode       'colour' (d >= 0: (255, s, s), d < 0: (s, s, 255), s = max(255 - 2 |d|, 0)), 'grey' ((s, s, s)), or None: no heat map
+      cols       (col0, col1): the row sums run over the columns [col0, col1) inside the image
+      flip_rows  output row i compares img's row H - 1 - i (a raster has row 0 at the bottom) with ref's row i
+      want_rows  False: no row sums
+
+    Returns (heat uint8 [N,H,W,3] or None, row_sums int32 [N,H] or None): sums of |d|, exact; the means are the caller's."""
+    if mode not in ('colour', 'grey', None):
+        raise ValueError(f"mode must be 'colour', 'grey' or None (got {mode!r})")
+    if mode is None and not want_rows:
+        raise ValueError("neither a heat map (mode) nor row sums (want_rows) requested")
+    img = _check_image_pair('comparison', img, ref)
     N, H, W = img.shape
     if 255 * W >= 2 ** 31:
         raise ValueError("a row sum of 255 * W does not fit int32")
@@ -871,36 +883,15 @@ def overlay_images(img, ref, rast=None, rast_db=None, weight=0.5, outside='rende
     Returns uint8 [N,H,W,3].  rast is read only if outside='capture' or a wire asks for it, rast_db only for a wire."""
     if outside not in ('render', 'capture'):
         raise ValueError(f"outside must be 'render' or 'capture' (got {outside!r})")
-    tensors = [('img', img), ('ref', ref)] + [(k, v) for k, v in (('rast', rast), ('rast_db', rast_db)) if v is not None]
-    for name, t in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-    for name, t in tensors:
-        if not t.is_cuda:
-            raise ValueError(f"{name} must be a GPU tensor (got {t.device}); the overlay has no CPU path")
-        if t.device != img.device:
-            raise ValueError(f"img and {name} are on different devices ({img.device}, {t.device})")
-    if img.dtype not in (torch.float32, torch.uint8):
-        raise ValueError(f"img must be float32 or uint8 (got {img.dtype})")
-    if ref.dtype != torch.uint8:
-        raise ValueError(f"ref must be uint8 (got {ref.dtype})")
-    if img.dim() == 4:
-        if img.shape[3] != 1:
-            raise ValueError(f"img must have one channel (got shape {tuple(img.shape)})")
-        img = img[..., 0]
-    if img.dim() != 3 or ref.dim() != 3:
-        raise ValueError(f"img must be [N,H,W] or [N,H,W,1] and ref [N,H,W] (got shapes {tuple(img.shape)}, {tuple(ref.shape)})")
-    if img.shape != ref.shape:
-        raise ValueError(f"img {tuple(img.shape)} and ref {tuple(ref.shape)} differ in shape")
-    for name, t in tensors[2:]:
+    rasters = [(k, v) for k, v in (('rast', rast), ('rast_db', rast_db)) if v is not None]
+    img = _check_image_pair('overlay', img, ref, rasters)
+    for name, t in rasters:
         if t.dtype != torch.float32:
             raise ValueError(f"{name} must be float32 (got {t.dtype})")
         if tuple(t.shape) != tuple(img.shape) + (4,):
             raise ValueError(f"{name} must be {tuple(img.shape) + (4,)} (got {tuple(t.shape)})")
-    if not img.is_contiguous() or not all(t.is_contiguous() for _, t in tensors[1:]):
-        raise ValueError("img, ref, rast and rast_db must be contiguous")
-    if img.numel() == 0:
-        raise ValueError("empty input")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
     weight = float(weight)
     if not 0.0 <= weight <= 1.0:        # (false for a NaN)
         raise ValueError(f"weight must lie in [0, 1] (got {weight})")

@@ -16,7 +16,7 @@ import torch
 
 from . import camera
 from . import ops as dr
-from .fit import BACKGROUND, render, render_from_clip
+from .fit import BACKGROUND, render
 
 
 def read_result_obj(path):
@@ -122,23 +122,35 @@ def compare_sequence_numerical(inferred, references, csv_path, **crop):
     return means
 
 
+def _load_result(result_dir, sc, dev, reproduce_pose, frames=None, cams=None):
+    """A directory written by Fitter.save() on `dev`, with what the reference re-reads from the take taken from sc.  Returns
+      mesh    (pos_idx, uv, uv_idx, tex), in the order render_multicam and fit.render_from_clip take them
+      pose    the saved (translations [F,3], rotations [F,4]) of pose.json, or None with reproduce_pose=False (_pose_of takes a frame's)
+      frames  the frame numbers as a list (default: every {i}.obj of the result)
+      cams    indices into sc.cams as a list (default: all)"""
+    mesh = (torch.tensor(sc.pos_idx, dtype=torch.int32, device=dev), torch.tensor(sc.uv, dtype=torch.float32, device=dev),
+            torch.tensor(sc.uv_idx, dtype=torch.int32, device=dev),
+            torch.tensor(read_texture(os.path.join(result_dir, "texture.png")), dtype=torch.float32, device=dev))
+    pose = read_pose(result_dir) if reproduce_pose else None
+    if frames is None:
+        frames = range(len([f for f in os.listdir(result_dir) if f.endswith(".obj") and f[:-4].isdigit()]))
+    return mesh, pose, list(frames), list(range(len(sc.cams))) if cams is None else [int(c) for c in cams]
+
+
+def _pose_of(pose, i):
+    return (pose[0][i], pose[1][i]) if pose is not None else None
+
+
 @torch.no_grad()
 def rerender_result(result_dir, sc, device='cuda', frames=None, reproduce_pose=True, ncols=3):
     """Re-render a directory written by Fitter.save(): yields (frame index, grid image uint8 [3H,3W,C]).
     sc supplies what the reference re-reads from the take (index buffers, uv, cameras, resolution)."""
     dev = torch.device(device)
     glctx = dr.RasterizeGLContext(device=dev)
-    pos_idx = torch.tensor(sc.pos_idx, dtype=torch.int32, device=dev)
-    uv = torch.tensor(sc.uv, dtype=torch.float32, device=dev)
-    uv_idx = torch.tensor(sc.uv_idx, dtype=torch.int32, device=dev)
-    tex = torch.tensor(read_texture(os.path.join(result_dir, "texture.png")), dtype=torch.float32, device=dev)
-    t_all, q_all = read_pose(result_dir) if reproduce_pose else (None, None)
-    n = len([f for f in os.listdir(result_dir) if f.endswith(".obj") and f[:-4].isdigit()])
-    for i in (frames if frames is not None else range(n)):
+    mesh, pose, frames, _ = _load_result(result_dir, sc, dev, reproduce_pose, frames)
+    for i in frames:
         verts = torch.tensor(read_result_obj(os.path.join(result_dir, f"{i}.obj")), device=dev)
-        pose = (t_all[i], q_all[i]) if reproduce_pose else None
-        imgs = render_multicam(glctx, verts, pos_idx, uv, uv_idx, tex, sc.cams, sc.resolution, pose=pose,
-                               modelview_offset=(0.0, 170.0, 0.0))
+        imgs = render_multicam(glctx, verts, *mesh, sc.cams, sc.resolution, pose=_pose_of(pose, i), modelview_offset=(0.0, 170.0, 0.0))
         grid = make_img(imgs.cpu().numpy(), ncols=ncols)
         yield i, np.clip(np.rint(grid), 0, 255).astype(np.uint8)
 
@@ -168,21 +180,25 @@ def _gpu(device):
     return dev
 
 
+def _pair_batches(inferred, references, batch, dev):
+    """(number of the first pair, inferred [n,H,W], references [n,H,W]) on `dev`, `batch` pairs at a time."""
+    for b0 in range(0, len(inferred), batch):
+        yield (b0, torch.from_numpy(np.stack([np.asarray(a) for a in inferred[b0:b0 + batch]])).to(dev),
+               torch.from_numpy(np.stack([np.asarray(a) for a in references[b0:b0 + batch]])).to(dev))
+
+
 def compare_sequence(inferred, references, out_dir, colour=True, heat=True, rows=(200, 1401), cols=(100, 1100), device='cuda', batch=16):
     """compareSequenceNumerical and (heat=True) the heat-map images of compareSequence (reference comparisons.py:21-80) for a sequence
     of image pairs, on the GPU: writes out_dir/numerical_clip.csv -- the text compare_sequence_numerical writes -- and
     out_dir/colcomp_{i}.png (colour=False: the grey map).  inferred / references: sequences of uint8 arrays [H,W] of one shape, top row
     first; they are uploaded `batch` pairs at a time and go through ops.compare_images.  Returns the list of image means."""
     dev = _gpu(device)
-    n = len(inferred)
-    assert n == len(references), "as many inferred images as references"
+    assert len(inferred) == len(references), "as many inferred images as references"
     os.makedirs(out_dir, exist_ok=True)
     mode = ('colour' if colour else 'grey') if heat else None
     means = []
     with open(os.path.join(out_dir, "numerical_clip.csv"), "w") as f:
-        for b0 in range(0, n, batch):
-            img = torch.from_numpy(np.stack([np.asarray(a) for a in inferred[b0:b0 + batch]])).to(dev)
-            ref = torch.from_numpy(np.stack([np.asarray(a) for a in references[b0:b0 + batch]])).to(dev)
+        for b0, img, ref in _pair_batches(inferred, references, batch, dev):
             crop = _crop(img.shape[1], img.shape[2], rows, cols)
             maps, sums = dr.compare_images(img, ref, mode=mode, cols=cols)
             sums = sums.cpu().numpy()
@@ -211,6 +227,37 @@ def take_references(imdir):
     return lambda frame: np.stack([data.load_raw_image(os.path.join(imdir, c, f"{c}_{frame:0{digits}d}.tif")) for c in cams])
 
 
+def _frame_batches(result_dir, sc, loaded, references, batch_frames, dev, what):
+    """The re-renders of a saved result (loaded = _load_result's tuple) beside their captures, its cameras of `batch_frames` frames
+    at a time.  Yields (the chunk's place b0 in the frame list, its frame numbers, colour [n,H,W,1] float in [0,1] with the background
+    composited, contiguous, rast, rast_db, captures uint8 [n,H,W] on `dev`), n = frames x cameras, every raster with row 0 at the
+    bottom.  The colour is fit.render_from_clip's unfused non-mip operator sequence with the rasteriser's second output kept.
+    what: the caller's noun for the one-channel check's message."""
+    glctx = dr.RasterizeGLContext(device=dev)
+    (pos_idx, uv, uv_idx, tex), pose, frames, cams = loaded
+    proj, t_mv = _camera_matrices([sc.cams[c] for c in cams], (0.0, 170.0, 0.0), dev)
+    shape = (len(cams),) + tuple(sc.resolution)
+    for b0 in range(0, len(frames), batch_frames):
+        chunk = frames[b0:b0 + batch_frames]
+        clip, refs = [], []
+        for i in chunk:
+            verts = torch.tensor(read_result_obj(os.path.join(result_dir, f"{i}.obj")), device=dev)
+            # per frame exactly the matrices and the transform of render_multicam: the same clip-space positions, bit for bit
+            clip.append(camera.transform_clip(_multicam_mvp(proj, t_mv, _pose_of(pose, i)), verts[None]))
+            r = np.asarray(references(i) if callable(references) else references[i])
+            if r.dtype != np.uint8 or r.shape != shape:
+                raise ValueError(f"references of frame {i}: expected uint8 {shape}, got {r.dtype} {r.shape}")
+            refs.append(r)
+        pos_clip = torch.cat(clip)
+        rast, rast_db = dr.rasterize(glctx, pos_clip, pos_idx, resolution=(sc.resolution[0], sc.resolution[1]))
+        texc, _ = dr.interpolate(uv[None, ...], rast, uv_idx)
+        colour_img = dr.antialias(dr.texture(tex[None, ...], texc, filter_mode='linear'), rast, pos_clip, pos_idx)
+        if colour_img.shape[-1] != 1:
+            raise ValueError(f"the {what} is of one-channel images (the texture has {colour_img.shape[-1]} channels)")
+        colour_img = torch.where(rast[..., 3:] > 0, colour_img, torch.tensor(BACKGROUND, device=dev))
+        yield b0, chunk, colour_img.contiguous(), rast, rast_db, torch.from_numpy(np.concatenate(refs)).to(dev)
+
+
 @torch.no_grad()
 def compare_result(result_dir, sc, references, out_dir, cams=None, frames=None, reproduce_pose=True, colour=True, heat=True,
                    batch_frames=4, device='cuda', **crop):
@@ -230,42 +277,17 @@ def compare_result(result_dir, sc, references, out_dir, cams=None, frames=None, 
     rows, cols = crop.pop('rows', (200, 1401)), crop.pop('cols', (100, 1100))
     if crop:
         raise TypeError(f"unknown arguments {sorted(crop)}")
-    cams = list(range(len(sc.cams))) if cams is None else [int(c) for c in cams]
-    if frames is None:
-        frames = range(len([f for f in os.listdir(result_dir) if f.endswith(".obj") and f[:-4].isdigit()]))
-    frames = list(frames)
     H, W = sc.resolution
     box = _crop(H, W, rows, cols)
-    os.makedirs(out_dir, exist_ok=True)
-    glctx = dr.RasterizeGLContext(device=dev)
-    pos_idx = torch.tensor(sc.pos_idx, dtype=torch.int32, device=dev)
-    uv = torch.tensor(sc.uv, dtype=torch.float32, device=dev)
-    uv_idx = torch.tensor(sc.uv_idx, dtype=torch.int32, device=dev)
-    tex = torch.tensor(read_texture(os.path.join(result_dir, "texture.png")), dtype=torch.float32, device=dev)
-    t_all, q_all = read_pose(result_dir) if reproduce_pose else (None, None)
-    proj, t_mv = _camera_matrices([sc.cams[c] for c in cams], (0.0, 170.0, 0.0), dev)
-    mode = ('colour' if colour else 'grey') if heat else None
+    loaded = _load_result(result_dir, sc, dev, reproduce_pose, frames, cams)
+    _, _, frames, cams = loaded
     Nc = len(cams)
+    os.makedirs(out_dir, exist_ok=True)
+    mode = ('colour' if colour else 'grey') if heat else None
     means = np.empty((len(frames), Nc), dtype=np.float64)
     lines = [[] for _ in cams]
-    for b0 in range(0, len(frames), batch_frames):
-        chunk = frames[b0:b0 + batch_frames]
-        clip, refs = [], []
-        for i in chunk:
-            verts = torch.tensor(read_result_obj(os.path.join(result_dir, f"{i}.obj")), device=dev)
-            # per frame exactly the matrices and the transform of render_multicam: the same clip-space positions, bit for bit
-            mvp = _multicam_mvp(proj, t_mv, (t_all[i], q_all[i]) if reproduce_pose else None)
-            clip.append(camera.transform_clip(mvp, verts[None]))
-            r = np.asarray(references(i) if callable(references) else references[i])
-            if r.dtype != np.uint8 or r.shape != (Nc, H, W):
-                raise ValueError(f"references of frame {i}: expected uint8 {(Nc, H, W)}, got {r.dtype} {r.shape}")
-            refs.append(r)
-        colour_img, rast = render_from_clip(glctx, torch.cat(clip), pos_idx, uv, uv_idx, tex, sc.resolution, False, 0)
-        if colour_img.shape[-1] != 1:
-            raise ValueError(f"the comparison is of one-channel images (the texture has {colour_img.shape[-1]} channels)")
-        colour_img = torch.where(rast[..., 3:] > 0, colour_img, torch.tensor(BACKGROUND, device=dev))
-        ref = torch.from_numpy(np.concatenate(refs)).to(dev)
-        maps, sums = dr.compare_images(colour_img.contiguous(), ref, mode=mode, cols=cols, scale=255.0, flip_rows=True)
+    for b0, chunk, colour_img, _, _, ref in _frame_batches(result_dir, sc, loaded, references, batch_frames, dev, 'comparison'):
+        maps, sums = dr.compare_images(colour_img, ref, mode=mode, cols=cols, scale=255.0, flip_rows=True)
         sums = sums.cpu().numpy().reshape(len(chunk), Nc, H)
         maps = maps.cpu().numpy().reshape(len(chunk), Nc, H, W, 3) if heat else None
         for k, i in enumerate(chunk):
@@ -289,12 +311,9 @@ def overlay_sequence(inferred, references, out_dir, weight=0.5, device='cuda', b
     inferred / references: sequences of uint8 arrays [H,W] of one shape, top row first; they are uploaded `batch` pairs at a time and go
     through ops.overlay_images."""
     dev = _gpu(device)
-    n = len(inferred)
-    assert n == len(references), "as many inferred images as references"
+    assert len(inferred) == len(references), "as many inferred images as references"
     os.makedirs(out_dir, exist_ok=True)
-    for b0 in range(0, n, batch):
-        img = torch.from_numpy(np.stack([np.asarray(a) for a in inferred[b0:b0 + batch]])).to(dev)
-        ref = torch.from_numpy(np.stack([np.asarray(a) for a in references[b0:b0 + batch]])).to(dev)
+    for b0, img, ref in _pair_batches(inferred, references, batch, dev):
         out = dr.overlay_images(img, ref, weight=weight).cpu().numpy()
         for k in range(out.shape[0]):
             _write_png(os.path.join(out_dir, f"overlay_{b0 + k}.png"), out[k])
@@ -307,8 +326,7 @@ def overlay_result(result_dir, sc, references, out_dir, cams=None, frames=None, 
     a float image leaving the GPU: the picture to look at first to see whether a fit sits on the face (the reference's
     render_result_blended.py; its wireframe variant needs a painted texture, this one draws the edges from the rasteriser's
     barycentrics and their screen derivatives).  Arguments and batching as compare_result; every frame's matrices and clip-space
-    positions are formed the same way, and the colour comes from the same unfused operator sequence as render_from_clip, so it equals
-    compare_result's bit for bit.
+    positions are formed the same way and the colour by the same operators (_frame_batches), so it equals compare_result's bit for bit.
 
       references   uint8 [F,Nc,H,W] indexed by frame number, top row first, or a callable frame -> [Nc,H,W]
       wire_colour  (r, g, b) bytes of the lines; half_width: half a line's width in pixels (a line is drawn from both sides of an edge)
@@ -317,44 +335,14 @@ def overlay_result(result_dir, sc, references, out_dir, cams=None, frames=None, 
 
     Writes out_dir/overlay_<cam>_<frame>.png (<cam> = the camera's index in sc.cams)."""
     dev = _gpu(device)
-    cams = list(range(len(sc.cams))) if cams is None else [int(c) for c in cams]
-    if frames is None:
-        frames = range(len([f for f in os.listdir(result_dir) if f.endswith(".obj") and f[:-4].isdigit()]))
-    frames = list(frames)
+    loaded = _load_result(result_dir, sc, dev, reproduce_pose, frames, cams)
+    cams = loaded[3]
+    Nc = len(cams)
     H, W = sc.resolution
     os.makedirs(out_dir, exist_ok=True)
-    glctx = dr.RasterizeGLContext(device=dev)
-    pos_idx = torch.tensor(sc.pos_idx, dtype=torch.int32, device=dev)
-    uv = torch.tensor(sc.uv, dtype=torch.float32, device=dev)
-    uv_idx = torch.tensor(sc.uv_idx, dtype=torch.int32, device=dev)
-    tex = torch.tensor(read_texture(os.path.join(result_dir, "texture.png")), dtype=torch.float32, device=dev)
-    t_all, q_all = read_pose(result_dir) if reproduce_pose else (None, None)
-    proj, t_mv = _camera_matrices([sc.cams[c] for c in cams], (0.0, 170.0, 0.0), dev)
-    Nc = len(cams)
-    for b0 in range(0, len(frames), batch_frames):
-        chunk = frames[b0:b0 + batch_frames]
-        clip, refs = [], []
-        for i in chunk:
-            verts = torch.tensor(read_result_obj(os.path.join(result_dir, f"{i}.obj")), device=dev)
-            # per frame exactly the matrices and the transform of render_multicam: the same clip-space positions, bit for bit
-            mvp = _multicam_mvp(proj, t_mv, (t_all[i], q_all[i]) if reproduce_pose else None)
-            clip.append(camera.transform_clip(mvp, verts[None]))
-            r = np.asarray(references(i) if callable(references) else references[i])
-            if r.dtype != np.uint8 or r.shape != (Nc, H, W):
-                raise ValueError(f"references of frame {i}: expected uint8 {(Nc, H, W)}, got {r.dtype} {r.shape}")
-            refs.append(r)
-        # the unfused operator sequence of render_from_clip, keeping the rasteriser's second output
-        pos_clip = torch.cat(clip)
-        rast, rast_db = dr.rasterize(glctx, pos_clip, pos_idx, resolution=(sc.resolution[0], sc.resolution[1]))
-        texc, _ = dr.interpolate(uv[None, ...], rast, uv_idx)
-        colour_img = dr.antialias(dr.texture(tex[None, ...], texc, filter_mode='linear'), rast, pos_clip, pos_idx)
-        if colour_img.shape[-1] != 1:
-            raise ValueError(f"the overlay is of one-channel images (the texture has {colour_img.shape[-1]} channels)")
-        colour_img = torch.where(rast[..., 3:] > 0, colour_img, torch.tensor(BACKGROUND, device=dev))
-        ref = torch.from_numpy(np.concatenate(refs)).to(dev)
-        out = dr.overlay_images(colour_img.contiguous(), ref, rast=rast.contiguous(), rast_db=rast_db.contiguous(), weight=weight,
-                                outside=outside, wire=tuple(wire_colour) if wireframe else None, half_width=half_width, scale=255.0,
-                                flip_rows=True)
+    for _, chunk, colour_img, rast, rast_db, ref in _frame_batches(result_dir, sc, loaded, references, batch_frames, dev, 'overlay'):
+        out = dr.overlay_images(colour_img, ref, rast=rast.contiguous(), rast_db=rast_db.contiguous(), weight=weight, outside=outside,
+                                wire=tuple(wire_colour) if wireframe else None, half_width=half_width, scale=255.0, flip_rows=True)
         out = out.cpu().numpy().reshape(len(chunk), Nc, H, W, 3)
         for k, i in enumerate(chunk):
             for j, c in enumerate(cams):
