@@ -191,6 +191,9 @@ SYMBOLS = {
     "fpcdr_compare_u8": (_int, [_p, _int, ctypes.c_float, _p, _p, _p, ctypes.c_int64, _i, _i, _i, _i, _i, _i, _p]),
     "fpcdr_overlay_u8": (_int, [_p, _int, ctypes.c_float, _p, _p, _p, _p, ctypes.c_int64, _i, _i, _int, _int, ctypes.c_float,
                                 ctypes.c_uint32, _int, _p]),
+    "fpcdr_bake_accumulate_u8": (_int, [_p, _p, _p, _p, ctypes.c_int64, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "fpcdr_bake_resolve": (_int, [_p, _p, _p, _i, _i, ctypes.c_double, ctypes.c_uint64, _p]),
+    "fpcdr_bake_dilate": (_int, [_p, _p, _p, _p, _i, _i, _p]),
 }
 
 # the two-call form of the pixel objective + the fused render pair (include/fpcdr_twocall.h): exported by libfpcdr_twocall.so only

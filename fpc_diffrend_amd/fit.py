@@ -718,7 +718,8 @@ class FitConfig:
                                     # iteration (fit.py:525-526)
     seed: int = 0
     optimize_texture: bool = True
-    init_texture: str = "truth"     # 'truth' | 'random' (reference: np.random.uniform when no texpath, fit.py:438)
+    init_texture: str = "truth"     # 'truth' | 'random' (reference: np.random.uniform when no texpath, fit.py:438) | 'bake': drawn as for
+                                    # 'random', then replaced by Fitter.bake_texture() over the shard's frames and the selected cameras
     fused_loss: bool = True         # False = reference-style torch.where + torch.mean chain
     fused_render: bool = True       # rasterize + interpolate + texture as one kernel pair (non-mip); False = four separate ops
     fused_objective: bool = True    # with fused_render and fused_loss: the whole pixel term as three kernels (ops.pixel_objective)
@@ -907,6 +908,8 @@ class Fitter:
         t = self.targets
         self.target_bg_sumsq = dr.reference_background_sumsq(t.reshape(-1, *self.resolution), BACKGROUND).reshape(t.shape[:2])
         self._bg_sum_key = None      # (the cached sum over the whole shard, loss_and_backward)
+        if cfg.init_texture == 'bake':
+            self.bake_texture()
 
     # ------------------------------------------------------------------------------------------
     @staticmethod
@@ -983,6 +986,59 @@ class Fitter:
         if self.cfg.mode == 'free':
             return blend_batched(self.v_base, self.m3, basis_t, pool)
         return out + 0.5 * blend_batched(None, self.m3, basis_t, pool)    # learned_coefficient=0.5, fit.py:562
+
+    @torch.no_grad()
+    def bake_texture(self, frame_ids=None, view_ids=None, interior_only=False, dilate=8, assign=True, reduce=None, chunk=4):
+        """A start texture from the captures at the CURRENT parameters ("Bake rule"): every covered pixel of the chosen
+        targets splats its capture into the four texels the forward would read for it; a texel is the weighted mean of what landed on
+        it, texels next to filled ones take their neighbours' mean (`dilate` passes), the rest 0.5.  A noise texture (the reference's
+        start without a texpath, fit.py:438) leaves the first thousands of steps without a usable pose or shape gradient.
+
+          frame_ids      frames of this rank's shard (None: all of them), a sequence or an integer tensor
+          view_ids       positions in cam_idxs (None: every selected camera)
+          interior_only  leave out silhouette pixels, whose capture holds background
+          assign         copy the result into tex_opt (Adam's moments stay as they are: call it before the first step)
+          reduce         reduce(acc) -> acc sums the int64 accumulator over the ranks; None: one all_reduce(SUM) when world > 1 and
+                         torch.distributed is initialised.  Integer sums: every rank resolves the same bits, whatever the sharding
+          chunk          frames rasterised at a time
+
+        Returns (tex [Ht,Wt,C] float32, filled [Ht,Wt] bool: the texels a capture reached)."""
+        dev = self.device
+        H, W = self.resolution
+        Ht, Wt, C = self.tex_opt.shape
+        if frame_ids is None:
+            frames = torch.arange(self.frame_lo, self.frame_hi, device=dev)
+        else:
+            frames = torch.as_tensor(frame_ids).to(dev).reshape(-1)
+        views = None if view_ids is None else torch.as_tensor(view_ids).to(dev).reshape(-1)
+        self.check_indices(frames, views)
+        frames = frames.long()
+        views = None if views is None else views.long()
+        glctx = dr.RasterizeGLContext(output_db=False, device=dev)
+        targets = self.targets.reshape(-1, H, W)
+        n_cam_all = self.targets.shape[1]
+        acc = torch.zeros(Ht, Wt, 2, dtype=torch.int64, device=dev)
+        for lo in range(0, int(frames.shape[0]), max(1, int(chunk))):
+            ids = frames[lo:lo + max(1, int(chunk))].contiguous()
+            verts = self.vertices(ids, validate=False).reshape(int(ids.shape[0]), -1, 3)
+            pos_clip = transform_clip_batched(self.mvp(ids, views, validate=False), verts)
+            rast, _ = dr.rasterize(glctx, pos_clip, self.pos_idx, resolution=(H, W))
+            texc, _ = dr.interpolate(self.uv[None, ...], rast, self.uv_idx)
+            cams = torch.arange(n_cam_all, device=dev) if views is None else views
+            sel = ((ids - self.frame_lo)[:, None] * n_cam_all + cams[None, :]).reshape(-1)
+            # (the targets' row 0 is the bottom row, as the raster's: no flip)
+            dr.bake_accumulate(texc, rast, targets.index_select(0, sel), acc, interior_only=interior_only)
+        if reduce is not None:
+            acc = reduce(acc)
+        elif self.world > 1:
+            import torch.distributed as tdist
+            if tdist.is_available() and tdist.is_initialized():
+                tdist.all_reduce(acc, op=tdist.ReduceOp.SUM)
+        plane, filled = dr.bake_resolve(acc, color_scale=255.0, dilate=dilate)
+        tex = plane[..., None].expand(Ht, Wt, C).contiguous()
+        if assign:
+            self.tex_opt.copy_(tex)
+        return tex, filled
 
     @torch.no_grad()
     def render_targets(self, chunk=4):

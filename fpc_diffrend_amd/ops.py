@@ -30,7 +30,7 @@ from . import _lib
 
 __all__ = ['RasterizeGLContext', 'RasterizeCudaContext', 'RasterizeHipContext', 'rasterize', 'interpolate', 'texture',
            'texture_construct_mip', 'antialias', 'antialias_construct_topology_hash', 'render_textured', 'pixel_objective', 'undistort_images', 'compare_images',
-           'gaussian_taps', 'blurred_pixel_loss']
+           'gaussian_taps', 'blurred_pixel_loss', 'bake_accumulate', 'bake_resolve']
 
 
 def _stream():
@@ -917,6 +917,94 @@ def overlay_images(img, ref, rast=None, rast_db=None, weight=0.5, outside='rende
         _lib.call("fpcdr_overlay_u8", _ptr(img), 1 if img.dtype == torch.float32 else 0, float(scale), _ptr(ref), _ptr(rast), _ptr(rast_db),
                   _ptr(out), N, H, W, weight_256, 1 if outside == 'capture' else 0, hw2, rgb, 1 if flip_rows else 0, _stream())
     return out
+
+
+def bake_accumulate(texc, rast, ref_u8, acc, boundary_mode='wrap', interior_only=False, flip_rows=False):
+    """Splat captures into a texture accumulator by the rule of DESIGN.md 3 "Bake rule" (fpcdr_bake_accumulate_u8): every covered pixel
+    adds its capture into the four texels texture(filter_mode='linear') would read for it, with the bilinear weights in 1/256 per axis.
+
+      texc           float32 GPU tensor [N,H,W,2], as interpolate returns it;  rast  float32 [N,H,W,4], only .w is read (> 0: covered)
+      ref_u8         uint8 [N,H,W]; row i belongs to raster row i, or with flip_rows to raster row H - 1 - i
+      acc            int64 [Ht,Wt,2], (num, den) per texel, the bits of unsigned 64-bit sums; ADDED to: torch.zeros for a new bake
+      boundary_mode  'wrap' or 'clamp', as for texture
+      interior_only  leave out covered pixels with an uncovered neighbour (up, down, left, right) inside the image: their capture
+                     holds background the antialias operator blended in
+
+    All contiguous, on one device.  Integer sums: the result does not depend on the order of the calls or on how the images are shared out
+    over calls and ranks.  Returns acc."""
+    tensors = [('texc', texc), ('rast', rast), ('ref_u8', ref_u8), ('acc', acc)]
+    for name, t in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    for name, t in tensors:
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a GPU tensor (got {t.device}); the bake has no CPU path")
+        if t.device != texc.device:
+            raise ValueError(f"texc and {name} are on different devices ({texc.device}, {t.device})")
+    for name, t, dtype in (('texc', texc, torch.float32), ('rast', rast, torch.float32), ('ref_u8', ref_u8, torch.uint8), ('acc', acc, torch.int64)):
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must be {dtype} (got {t.dtype})")
+    if boundary_mode not in ('wrap', 'clamp'):
+        raise ValueError(f"boundary_mode must be 'wrap' or 'clamp' (got {boundary_mode!r})")
+    if texc.dim() != 4 or texc.shape[3] != 2:
+        raise ValueError(f"texc must be [N,H,W,2] (got shape {tuple(texc.shape)})")
+    N, H, W, _ = texc.shape
+    if tuple(rast.shape) != (N, H, W, 4):
+        raise ValueError(f"rast must be {(N, H, W, 4)} (got {tuple(rast.shape)})")
+    if tuple(ref_u8.shape) != (N, H, W):
+        raise ValueError(f"ref_u8 must be {(N, H, W)} (got {tuple(ref_u8.shape)})")
+    if acc.dim() != 3 or acc.shape[2] != 2:
+        raise ValueError(f"acc must be [Ht,Wt,2] (got shape {tuple(acc.shape)})")
+    if not all(t.is_contiguous() for _, t in tensors):
+        raise ValueError("texc, rast, ref_u8 and acc must be contiguous")
+    if texc.numel() == 0 or acc.numel() == 0:
+        raise ValueError("empty input")
+    with torch.cuda.device(texc.device):
+        _lib.call("fpcdr_bake_accumulate_u8", _ptr(texc), _ptr(rast), _ptr(ref_u8), _ptr(acc), N, H, W, acc.shape[0], acc.shape[1],
+                  _lib.BOUNDARY[boundary_mode], 1 if interior_only else 0, 1 if flip_rows else 0, _stream())
+    return acc
+
+
+def bake_resolve(acc, color_scale=255.0, min_weight=0.0, dilate=8, hole_value=0.5):
+    """The texture of an accumulator of bake_accumulate (DESIGN.md 3 "Bake rule": fpcdr_bake_resolve, fpcdr_bake_dilate).
+
+      acc          int64 GPU tensor [Ht,Wt,2], contiguous
+      color_scale  the captures' unit: tex = num / (den * color_scale), 255 as in the pixel loss
+      min_weight   a texel is filled when its summed weight reaches it, in pixels (1 = one pixel centred on the texel); every texel
+                   with any weight at all for 0: min_den = max(1, round(min_weight * 65536))
+      dilate       passes that give an unfilled texel next to filled ones the mean of those neighbours: the gutter a UV chart needs,
+                   because bilinear taps at its border read texels no pixel landed on
+      hole_value   the value of the texels that are still unfilled afterwards
+
+    Returns (tex [Ht,Wt] float32, filled [Ht,Wt] bool: which texels the captures reached, BEFORE the dilation)."""
+    _check_tensor('acc', acc, torch.int64, 3)
+    if acc.shape[2] != 2 or acc.numel() == 0:
+        raise ValueError(f"acc must be [Ht,Wt,2] and not empty (got shape {tuple(acc.shape)})")
+    if not acc.is_contiguous():
+        raise ValueError("acc must be contiguous")
+    color_scale, min_weight, dilate = float(color_scale), float(min_weight), int(dilate)
+    if not (color_scale > 0.0 and np.isfinite(color_scale)):
+        raise ValueError(f"color_scale must be positive and finite (got {color_scale})")
+    if not 0.0 <= min_weight < 2.0 ** 40:       # (false for a NaN)
+        raise ValueError(f"min_weight must lie in [0, 2^40) (got {min_weight})")
+    if dilate < 0:
+        raise ValueError(f"dilate must be >= 0 (got {dilate})")
+    min_den = max(1, int(round(min_weight * 65536)))
+    Ht, Wt = acc.shape[:2]
+    dev = acc.device
+    tex = torch.empty((Ht, Wt), dtype=torch.float32, device=dev)
+    filled = torch.empty((Ht, Wt), dtype=torch.bool, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("fpcdr_bake_resolve", _ptr(acc), _ptr(tex), _ptr(filled), Ht, Wt, color_scale, min_den, _stream())
+        cur, cur_f = tex, filled
+        if dilate > 0:
+            cur_f = filled.clone()          # (the returned mask stays as the resolve left it)
+            nxt, nxt_f = torch.empty_like(tex), torch.empty_like(filled)
+            for _ in range(dilate):
+                _lib.call("fpcdr_bake_dilate", _ptr(cur), _ptr(cur_f), _ptr(nxt), _ptr(nxt_f), Ht, Wt, _stream())
+                cur, cur_f, nxt, nxt_f = nxt, nxt_f, cur, cur_f
+    out = torch.where(cur_f, cur, torch.tensor(float(hole_value), dtype=torch.float32, device=dev))
+    return out, filled
 
 
 def pixel_objective(glctx, pos, tri, uv, uv_tri, tex, ref_u8, resolution, n_total=None, background=45.0 / 255.0,

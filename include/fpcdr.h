@@ -596,6 +596,40 @@ struct fpcdr_blur_loss_params {
 size_t fpcdr_blur_loss_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t C);
 int fpcdr_blur_loss(const fpcdr_blur_loss_params *p, void *stream);
 
+/* A start texture baked from the captures (the reference starts from uniform noise when a take has no texture, src/torch/fit.py:438).
+ * Pure additions: FPCDR_ABI_VERSION stays 16, no existing entry or struct changes.  DESIGN.md 3, "Bake rule": the diagonal
+ * least-squares solution of the 'linear' texture lookup's own sampling, in integers.
+ *
+ * fpcdr_bake_accumulate_u8:
+ *   texc  [n_images, H, W, 2] float32, the interpolated texture coordinates;  rast [n_images, H, W, 4] float32, only .w is read
+ *   ref   [n_images, H, W] uint8;  acc [Ht, Wt, 2] unsigned 64-bit (num, den) per texel, ACCUMULATED: the caller zero-fills it
+ * For the pixel at raster row i (row 0 at the bottom), column j of image n:
+ *   cov(i, j) = rast[n, i, j, 3] > 0  (a NaN is not covered);  (u, v) = texc[n, i, j, :]
+ *   the pixel contributes if cov(i, j), u and v are finite and, with interior_only, cov holds at each of (i +- 1, j), (i, j +- 1)
+ *   that lies inside the image
+ *   c = ref[n, flip_rows ? H - 1 - i : i, j]                      (the flip applies to ref only)
+ *   the four texels and the fractions fx, fy are those of the 'linear' lookup under boundary_mode (wrap or clamp), in its float32
+ *   arithmetic;  ax = (int)floor(fx * 256), ay likewise, in 0..256
+ *   w00 = (256 - ax)(256 - ay), w10 = ax (256 - ay), w01 = (256 - ax) ay, w11 = ax ay              (integers, sum 65536)
+ *   for each tap k with w_k > 0:  acc[t_k].num += w_k c,  acc[t_k].den += w_k     (clamp: two taps may name one texel; both add)
+ * Integer atomics: the sums do not depend on the order of the adds, of the calls or of the images.
+ *
+ * fpcdr_bake_resolve:  filled = den >= min_den;  tex = filled ? (float)((double)num / ((double)den * color_scale)) : 0
+ *   tex [Ht, Wt] float32, filled [Ht, Wt] bytes 0 / 1, both fully overwritten.
+ *
+ * fpcdr_bake_dilate: one Jacobi pass.  An unfilled texel with a filled one among its eight neighbours inside the texture (no wrap)
+ *   becomes the float32 sum of those neighbours, added in the order dy = -1, 0, 1 (outer), dx = -1, 0, 1 (inner) from 0, divided by
+ *   (float)count, and is marked filled in filled_out; every other texel and mark is copied.  The pass reads tex_in / filled_in only.
+ *
+ * Errors, before any launch: a NULL pointer, sizes <= 0, a boundary mode other than wrap / clamp, an acc that is not 8-byte aligned,
+ * min_den == 0, an output that overlaps an input.  texc and rast may sit at any 4-byte aligned address, ref at any address (wider
+ * accesses are used where the addresses allow). */
+int fpcdr_bake_accumulate_u8(const float *texc, const float *rast, const uint8_t *ref, uint64_t *acc, int64_t n_images, int H, int W,
+                             int Ht, int Wt, int boundary_mode, int interior_only, int flip_rows, void *stream);
+int fpcdr_bake_resolve(const uint64_t *acc, float *tex, uint8_t *filled, int Ht, int Wt, double color_scale, uint64_t min_den,
+                       void *stream);
+int fpcdr_bake_dilate(const float *tex_in, const uint8_t *filled_in, float *tex_out, uint8_t *filled_out, int Ht, int Wt, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
