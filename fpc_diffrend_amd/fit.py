@@ -418,50 +418,30 @@ def mesh_laplacian_smoothing(verts, topo, per_mesh=False):
 class _laplacian_penalty(torch.autograd.Function):
     """weight * mean_f (mean_v ||(L x_f)_v||)^2 in one launch each way (fpcdr_laplacian_penalty_fwd / _bwd).
     eager: the gradient kernel runs in forward() already (the term depends on the vertices only), backward() hands the buffer over --
-    times the upstream scalar, or as it is with unit (the caller guarantees d loss / d value = 1).  stream: both launches go to that
-    stream (forked from the current one here, joined in backward()): the autograd node itself stays on
-    the current stream, so the engine inserts no cross-stream synchronisation of its own."""
+    times the upstream scalar, or as it is with unit (the caller guarantees d loss / d value = 1)."""
 
     @staticmethod
-    def forward(ctx, verts, nbr32, inv_deg, weight, eager=False, unit=False, stream=None, acc=None):
+    def forward(ctx, verts, nbr32, inv_deg, weight, eager=False, unit=False, acc=None):
         if not verts.is_cuda:
             raise RuntimeError("the mesh regularisers run on the GPU only (fpcdr_laplacian_penalty_fwd); there is no CPU fallback")
         x = verts.contiguous()
         F, V, _ = x.shape
         eager = bool(eager and ctx.needs_input_grad[0])
-        main = torch.cuda.current_stream(x.device)
-        if stream is not None:
-            stream.wait_stream(main)
-        with torch.cuda.stream(stream if stream is not None else main):
-            st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-            lap = torch.empty_like(x)
-            # acc: F + 1 doubles, zero on entry -- and the call leaves them zero again, so a caller that hands over its own buffer (the
-            # Fitter: one per instance) saves the fill launch of a fresh one per step
-            if acc is None:
-                acc = torch.zeros(F + 1, dtype=torch.float64, device=x.device)
-            assert acc.dtype == torch.float64 and acc.numel() >= F + 1 and acc.is_contiguous()
-            per = torch.empty(F, dtype=torch.float32, device=x.device)
-            out = torch.empty((), dtype=torch.float32, device=x.device)
-            _lib.call("fpcdr_laplacian_penalty_fwd", _ptr(x), _ptr(nbr32), _ptr(inv_deg), _ptr(lap), _ptr(acc), _ptr(per), _ptr(out),
-                      float(weight), F, V, nbr32.shape[0], st)
-            gx = None
-            if eager:
-                gx = torch.empty_like(lap)
-                _lib.call("fpcdr_laplacian_penalty_bwd", _ptr(lap), _ptr(nbr32), _ptr(inv_deg), _ptr(per), _ptr(_unit_scalar(x.device)),
-                          _ptr(gx), float(weight), F, V, nbr32.shape[0], st)
-        ctx.event = None
-        if stream is not None:
-            ctx.event = torch.cuda.Event()
-            ctx.event.record(stream)
-            x.record_stream(stream)
-            # allocated on `stream`, consumed on the current one (out, gx; lap and per by a non-eager backward(), which reads them on the
-            # stream of ITS caller after wait_event: without the record the caching allocator may hand their blocks to a new side-stream
-            # allocation while that kernel is still reading them)
-            for t in (out, gx) if eager else (out, lap, per):
-                if t is not None:
-                    t.record_stream(main)
-            for t in (nbr32, inv_deg):   # the caller's tensors, read on `stream`
-                t.record_stream(stream)
+        lap = torch.empty_like(x)
+        # acc: F + 1 doubles, zero on entry -- and the call leaves them zero again, so a caller that hands over its own buffer (the
+        # Fitter: one per instance) saves the fill launch of a fresh one per step
+        if acc is None:
+            acc = torch.zeros(F + 1, dtype=torch.float64, device=x.device)
+        assert acc.dtype == torch.float64 and acc.numel() >= F + 1 and acc.is_contiguous()
+        per = torch.empty(F, dtype=torch.float32, device=x.device)
+        out = torch.empty((), dtype=torch.float32, device=x.device)
+        _lib.call("fpcdr_laplacian_penalty_fwd", _ptr(x), _ptr(nbr32), _ptr(inv_deg), _ptr(lap), _ptr(acc), _ptr(per), _ptr(out),
+                  float(weight), F, V, nbr32.shape[0], _stream())
+        gx = None
+        if eager:
+            gx = torch.empty_like(lap)
+            _lib.call("fpcdr_laplacian_penalty_bwd", _ptr(lap), _ptr(nbr32), _ptr(inv_deg), _ptr(per), _ptr(_unit_scalar(x.device)),
+                      _ptr(gx), float(weight), F, V, nbr32.shape[0], _stream())
         if eager:
             ctx.save_for_backward(gx)
         else:
@@ -471,17 +451,15 @@ class _laplacian_penalty(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.event is not None:
-            torch.cuda.current_stream(g.device).wait_event(ctx.event)
         if ctx.eager:
             gx, = ctx.saved_tensors
-            return (gx if ctx.unit else gx * g.to(torch.float32)), None, None, None, None, None, None, None
+            return (gx if ctx.unit else gx * g.to(torch.float32)), None, None, None, None, None, None
         lap, nbr32, inv_deg, per = ctx.saved_tensors
         F, V, _ = lap.shape
         gx = torch.empty_like(lap)
         _lib.call("fpcdr_laplacian_penalty_bwd", _ptr(lap), _ptr(nbr32), _ptr(inv_deg), _ptr(per), _ptr(g.to(torch.float32).contiguous()),
                   _ptr(gx), ctx.weight, F, V, nbr32.shape[0], _stream())
-        return gx, None, None, None, None, None, None, None
+        return gx, None, None, None, None, None, None
 
 
 _unit_scalars = {}
@@ -495,12 +473,12 @@ def _unit_scalar(dev):
     return t
 
 
-def laplacian_penalty(verts, topo, weight, eager_grad=False, unit_upstream=False, stream=None, acc=None):
+def laplacian_penalty(verts, topo, weight, eager_grad=False, unit_upstream=False, acc=None):
     """weight * mean over the meshes of verts [F,V,3] of mesh_laplacian_smoothing(mesh)^2 -- the reference's term (fit.py:581 squares
     the value of the ONE mesh of its step) -- as two launches per step instead of a gather and fifteen torch kernels.
     eager_grad: the gradient is computed with the value (backward() only multiplies by the upstream scalar, or not at all with
-    unit_upstream); stream: run both launches on that stream beside the caller's (the backward() joins; a caller that never runs backward() waits for the stream itself)."""
-    return _laplacian_penalty.apply(verts, topo.nbr32, topo.inv_deg, weight, eager_grad, unit_upstream, stream, acc)
+    unit_upstream).  acc: see _laplacian_penalty.forward."""
+    return _laplacian_penalty.apply(verts, topo.nbr32, topo.inv_deg, weight, eager_grad, unit_upstream, acc)
 
 
 def mesh_normal_consistency(verts, topo):
@@ -725,9 +703,6 @@ class FitConfig:
     fused_objective: bool = True    # with fused_render and fused_loss: the whole pixel term as three kernels (ops.pixel_objective)
     grouped_adam: bool = True       # all ten Adam groups + the quaternion division as one launch (False: torch.optim.Adam(fused=True))
     sparse_objective: bool = True   # the three kernels skip image regions far from any geometry (same result)
-    overlap_regularisers: bool = False  # fused path: mesh regularisers on a second stream beside the pixel objective.  Off since the
-                                        # Laplacian term is two short launches (r4): the cross-stream waits cost what the overlap hides
-                                        # (profiles/r04_stream_overlap.txt); worth switching on with the torch-chain terms (edge, normals)
     one_pass: bool = True           # fused path without mip: value AND gradient of the pixel term from one call (fpcdr_objective_fwd: the
                                     # kernel that shades a pixel chains its gradient back; False: forward call + backward call)
     queued_backward: bool = True    # fused path: the backward kernel runs over the list of occupied bins the forward left (with launch
@@ -868,10 +843,12 @@ class Fitter:
         # that did happen (lr_skip_gain = lr(i - 1) / lr(i) of LambdaLR's lr_ramp^(i / max_iter), fit.py:506-507)
         self._skip_flag = torch.zeros(1, dtype=torch.float32, device=dev)
         self._skip_cur = None
-        if isinstance(self.optimizer, GroupedAdam) and not self.optimizer.capturable:
+        self._grouped = isinstance(self.optimizer, GroupedAdam)      # (decided here, once: the optimiser is never replaced)
+        if self._grouped and not self.optimizer.capturable:
             self.optimizer.enable_skips(lr_skip_gain=float(cfg.lr_ramp) ** (-1.0 / float(cfg.max_iter)))
         self._graphs, self._graph_key, self._frame_idx, self._view_idx = None, None, None, None
-        self._side_stream = torch.cuda.Stream(device=dev)
+        self._stage_dev = None       # (graph mode: the fixed device buffer of a step's inputs, _stage_inputs)
+        self._targets_f32 = None     # (the reference torch chain's float copy of the targets, made by its first step)
         self._one = torch.ones((), dtype=torch.float32, device=dev)
         self._zero = torch.zeros((), dtype=torch.float32, device=dev)
         self._background = torch.tensor(BACKGROUND, device=dev)     # (a device scalar made once: no host copy inside a HIP-graph capture)
@@ -969,6 +946,21 @@ class Fitter:
             return t[ids] if dim == 0 else t[:, ids]
         return t.index_select(dim, ids)
 
+    def _target_rows(self, frame_ids, view_ids=None):
+        """The rows of the flat [F_local * n_cam, H, W] view of `targets` (and of target_bg_sumsq, flattened) that a batch names: frame numbers
+        of the take (a slice or an index tensor) x positions in cam_idxs (None: every camera).  A contiguous range of frames with every
+        camera is a slice -- a view, no launch --, anything else ONE row tensor for index_select, frame-major as the batch is."""
+        n_cam = self.targets.shape[1]
+        if isinstance(frame_ids, slice):
+            lo, hi = frame_ids.start - self.frame_lo, frame_ids.stop - self.frame_lo
+            if view_ids is None:
+                return slice(lo * n_cam, hi * n_cam)
+            f_idx = torch.arange(lo, hi, device=self.device)
+        else:
+            f_idx = frame_ids - self.frame_lo if self.frame_lo else frame_ids
+        cams = torch.arange(n_cam, device=self.device) if view_ids is None else view_ids
+        return (f_idx[:, None] * n_cam + cams[None, :]).reshape(-1)
+
     def vertices(self, frame_ids, iteration=None, pool=None, validate=True):
         """Blended vertex buffers [Fb,3V] for a batch of frames (fit.py:555-562).  The reference multiplies by a
         one-hot frame vector (fit.py:536, 115-116); M e_f is column f of M, so the batch selects columns
@@ -1016,7 +1008,6 @@ class Fitter:
         views = None if views is None else views.long()
         glctx = dr.RasterizeGLContext(output_db=False, device=dev)
         targets = self.targets.reshape(-1, H, W)
-        n_cam_all = self.targets.shape[1]
         acc = torch.zeros(Ht, Wt, 2, dtype=torch.int64, device=dev)
         for lo in range(0, int(frames.shape[0]), max(1, int(chunk))):
             ids = frames[lo:lo + max(1, int(chunk))].contiguous()
@@ -1024,10 +1015,8 @@ class Fitter:
             pos_clip = transform_clip_batched(self.mvp(ids, views, validate=False), verts)
             rast, _ = dr.rasterize(glctx, pos_clip, self.pos_idx, resolution=(H, W))
             texc, _ = dr.interpolate(self.uv[None, ...], rast, self.uv_idx)
-            cams = torch.arange(n_cam_all, device=dev) if views is None else views
-            sel = ((ids - self.frame_lo)[:, None] * n_cam_all + cams[None, :]).reshape(-1)
             # (the targets' row 0 is the bottom row, as the raster's: no flip)
-            dr.bake_accumulate(texc, rast, targets.index_select(0, sel), acc, interior_only=interior_only)
+            dr.bake_accumulate(texc, rast, targets.index_select(0, self._target_rows(ids, views)), acc, interior_only=interior_only)
         if reduce is not None:
             acc = reduce(acc)
         elif self.world > 1:
@@ -1096,8 +1085,8 @@ class Fitter:
         n_local = self.frame_hi - self.frame_lo
         kf = self.cfg.frames_per_step if 0 < self.cfg.frames_per_step < n_local else 0
         kv = self.cfg.views_per_step if 0 < self.cfg.views_per_step < len(self.cam_idxs) else 0
-        cap = isinstance(self.optimizer, GroupedAdam) and self.optimizer.capturable
-        if getattr(self, "_stage_dev", None) is None:
+        cap = self._grouped and self.optimizer.capturable
+        if self._stage_dev is None:
             n = kf + kv + _lib.ADAM_MAX_TENSORS          # int64 words; the table's 2 x ADAM_MAX_TENSORS floats are ADAM_MAX_TENSORS of them
             self._stage_dev = torch.zeros(n, dtype=torch.int64, device=self.device)
             self._stage_ring = []
@@ -1187,22 +1176,12 @@ class Fitter:
         vtx_pos = self.vertices(frame_ids, pool=pool, validate=False)                 # [Fb,3V]
         vtx_pos_split = vtx_pos.reshape(Fb, -1, 3)
         mvp = self.mvp(frame_ids, view_ids, pool, validate=False)
-        ref = None
         n_img_global = Fb * Nc * self.world
-        local = slice(frame_ids.start - self.frame_lo, frame_ids.stop - self.frame_lo) if isinstance(frame_ids, slice) \
-            else (frame_ids - self.frame_lo if self.frame_lo else frame_ids)
         # the step's reference images.  A random (frame, view) subset is ONE gather of the images it names from the flat [F * Nc, H, W]
         # table (the reference's run shape draws one image per step: selecting the frame's nine images first and the view second copied
         # 17 MB for 1.9 MB -- 39 of the step's ~330 us of kernels)
-        flat_sel = None
-        if view_ids is None:
-            ref = self.targets[local]
-        else:
-            n_cam_all = self.targets.shape[1]
-            f_idx = torch.arange(local.start, local.stop, device=self.device) if isinstance(local, slice) else local
-            flat_sel = (f_idx[:, None] * n_cam_all + view_ids[None, :]).reshape(-1)
-            ref = self.targets.reshape(-1, *self.resolution).index_select(0, flat_sel)
-        ref = ref.reshape(Fb * Nc, *self.resolution)
+        rows = self._target_rows(frame_ids, view_ids)
+        ref = self._take(self.targets.reshape(-1, *self.resolution), 0, rows)
         n_total = n_img_global * self.resolution[0] * self.resolution[1] * C
         pos_clip = transform_clip_batched(mvp, vtx_pos_split, pool)  # camera.transform_clip (camera.py:11-23), batched
         if cfg.shading == 'vertex':
@@ -1211,18 +1190,10 @@ class Fitter:
         elif not one_shot:
             colour, rast_out = render_from_clip(self.glctx, pos_clip, self.pos_idx, self.uv, self.uv_idx, self.tex_opt,
                                                 self.resolution, cfg.enable_mip, cfg.max_mip_level, cfg.fused_render)
-        # regularisers (fit.py:578-595): evaluated on this rank's meshes, averaged over all ranks.  They depend on the
-        # vertices only, so in the fused path they run on a second stream beside the pixel objective (forward here; autograd
-        # replays each backward on the stream of its forward): their ~25 small launches hide behind the raster kernels.
-        main_stream = torch.cuda.current_stream()
-        overlap = one_shot and cfg.overlap_regularisers and not self.use_graph
+        # regularisers (fit.py:578-595): evaluated on this rank's meshes, averaged over all ranks
         chain_terms = bool(cfg.weight_meshedge or cfg.weight_normalconsistency or (cfg.weight_laplacian and not cfg.fused_loss)
                            or (cfg.regularize_correctives and cfg.mode == 'combined' and i > cfg.max_iter / 2)
                            or (cfg.regularize_prior and cfg.mode == 'prior'))
-        side = self._side_stream if (overlap and chain_terms) else None
-        if side is not None:
-            side.wait_stream(main_stream)
-            torch.cuda.set_stream(side)
         reg = self._zero
         if cfg.weight_meshedge:
             reg = reg + cfg.weight_meshedge * mesh_edge_loss(vtx_pos_split, self.topo, 0.1)
@@ -1239,30 +1210,25 @@ class Fitter:
             reg = reg + torch.mean(mi ** 2)
         if self.world > 1 and chain_terms:
             reg = reg / self.world
-        if side is not None:
-            torch.cuda.set_stream(main_stream)
-            vtx_pos_split.record_stream(side)
         # the Laplacian term as two launches, its gradient computed with the value (it depends on the vertices only): backward() hands the
-        # buffer over.  Its weight carries the 1 / world, so that d loss / d term = 1 exactly.  (On the second stream with
-        # overlap_regularisers; on the main stream the two launches are ~25 us in front of the objective.)
+        # buffer over.  Its weight carries the 1 / world, so that d loss / d term = 1 exactly.  (The two launches are ~25 us in front of
+        # the objective.)
         lap = None
         if cfg.weight_laplacian and cfg.fused_loss:
             lap = laplacian_penalty(vtx_pos_split, self.topo, cfg.weight_laplacian / self.world, eager_grad=True, unit_upstream=True,
-                                    stream=self._side_stream if overlap else None, acc=self._lap_acc)
+                                    acc=self._lap_acc)
         self.optimizer.zero_grad(set_to_none=True)
         if one_shot:
             bg_sum = None
             if cfg.sparse_objective:
-                if isinstance(local, slice) and view_ids is None:      # the whole shard, every view: the same number every step
-                    key = (local.start, local.stop)
-                    if getattr(self, "_bg_sum_key", None) != key:
-                        self._bg_sum_key, self._bg_sum_all = key, self.target_bg_sumsq[local].sum()
+                bg = self.target_bg_sumsq.reshape(-1)
+                if isinstance(rows, slice):      # the whole shard, every view: the same number every step
+                    if self._bg_sum_key != rows:
+                        self._bg_sum_key, self._bg_sum_all = rows, bg[rows].sum()
                     bg_sum = self._bg_sum_all
-                elif flat_sel is not None:
-                    bg = self.target_bg_sumsq.reshape(-1).index_select(0, flat_sel)
-                    bg_sum = bg.reshape(()) if bg.numel() == 1 else bg.sum()
                 else:
-                    bg_sum = self.target_bg_sumsq[local].sum()
+                    bg = bg.index_select(0, rows)
+                    bg_sum = bg.reshape(()) if bg.numel() == 1 else bg.sum()
             self._skip_cur = self._skip_target() if (cfg.one_pass and cfg.sparse_objective) else None
             pix = dr.pixel_objective(self.glctx, pos_clip, self.pos_idx, self.uv, self.uv_idx, self.tex_opt, ref, self.resolution,
                                      n_total, BACKGROUND, sparse=cfg.sparse_objective, ref_bg_sumsq=bg_sum,
@@ -1270,47 +1236,40 @@ class Fitter:
                                      queued_backward=cfg.queued_backward and not self.use_graph,
                                      one_pass=cfg.one_pass, unit_upstream=True, zero_extra=zero_buf,      # (the seeds below are 1)
                                      skip_out=self._skip_cur)
-            # d loss / d pix = d loss / d reg = 1, handed over as a cached device scalar: `(pix + reg).backward()` would put an add and
-            # a fill between the forward and the backward kernel; the sum is formed after the backward pass has been enqueued
-            roots, seeds = [pix], [self._one]
-            for term in (reg, lap):
-                if term is not None and term.requires_grad:
-                    roots.append(term)
-                    seeds.append(self._one)
-            torch.autograd.backward(roots, seeds)
-            if side is not None:
-                main_stream.wait_stream(side)    # the regularisers' forward and backward ran on the side stream
-                reg.record_stream(main_stream)
+            self._backward(pix, self._one, reg, lap)
             loss = pix.detach()
             if chain_terms:
                 loss = loss + reg.detach()
             if lap is not None:
-                if not lap.requires_grad and overlap:      # (no backward(), which joins the side stream: join here)
-                    main_stream.wait_stream(self._side_stream)
                 loss = loss + lap.detach()
         elif cfg.fused_loss:
             if blur_taps is not None:
                 sum_sq, g_colour = pixel_loss_blurred(colour, rast_out, ref, blur_taps, n_total)
             else:
                 sum_sq, g_colour = pixel_loss_fused(colour, rast_out, ref, n_total)
-            roots, seeds = [colour], [g_colour]
-            for term in (reg, lap):
-                if term is not None and term.requires_grad:
-                    roots.append(term)
-                    seeds.append(self._one)
-            torch.autograd.backward(roots, seeds)
+            self._backward(colour, g_colour, reg, lap)
             loss = sum_sq[0].to(torch.float32) / n_total + reg.detach() + (lap.detach() if lap is not None else 0.0)
         else:
             col = torch.where(rast_out[..., 3:] > 0, colour, self._background)
             # the reference holds its target image as float32 on the GPU (fit.py:531-532); the 8-bit batch is converted once
-            if getattr(self, "_targets_f32", None) is None:
+            if self._targets_f32 is None:
                 self._targets_f32 = self.targets.to(torch.float32)
-            ref_f = self._targets_f32[local] if view_ids is None else self._targets_f32[local].index_select(1, view_ids)
-            ref_f = ref_f.reshape(Fb * Nc, *self.resolution, 1)
+            ref_f = self._take(self._targets_f32.reshape(-1, *self.resolution), 0, rows).reshape(Fb * Nc, *self.resolution, 1)
             loss = torch.mean((ref_f - col * 255) ** 2) / self.world + reg + (lap if lap is not None else 0.0)
             loss.backward()
         self._store_result(frame_ids, vtx_pos.detach())
         return loss.detach()
+
+    def _backward(self, root, seed, *terms):
+        """The step's backward pass: `root` seeded with `seed`, and every regulariser term that has a graph with d loss / d term = 1,
+        handed over as a cached device scalar (`(pix + reg).backward()` would put an add and a fill between the forward and the backward
+        kernel: the loss's value is summed after the pass has been enqueued)."""
+        roots, seeds = [root], [seed]
+        for term in terms:
+            if term is not None and term.requires_grad:
+                roots.append(term)
+                seeds.append(self._one)
+        torch.autograd.backward(roots, seeds)
 
     @property
     def result(self):
@@ -1338,8 +1297,8 @@ class Fitter:
     def _skip_target(self):
         """Where this step's pixel objective writes its "my results are invalid" flag (None: the optimiser cannot skip): the gradient
         bucket's extra element when the reducer has one (dist.GradBucket.flag -- summed over the ranks with the gradients), else the
-        Fitter's own float (all-reduced on its own in step() when there are other ranks)."""
-        if not isinstance(self.optimizer, GroupedAdam) or self.optimizer.skipped is None:
+        Fitter's own float (all-reduced on its own in _eager_step() when there are other ranks)."""
+        if not self._grouped or self.optimizer.skipped is None:
             return None
         flag = getattr(self.reduce_fn, "flag", None) if self.reduce_fn is not None else None
         return flag if flag is not None else self._skip_flag
@@ -1357,16 +1316,33 @@ class Fitter:
         return [int(v) for v in sk[:len(self.params)].tolist()] if sk is not None else [0] * len(self.params)
 
     def _update(self, prepared=False):
-        if isinstance(self.optimizer, GroupedAdam) and self.optimizer.capturable and not prepared:
-            self.optimizer.prepare()      # (an eager step of a graph-mode Fitter: warm-up, or a new set of trainable tensors)
-        if isinstance(self.optimizer, GroupedAdam):
-            self.optimizer.skip_flag = self._skip_cur
-        self.optimizer.step()
-        if isinstance(self.optimizer, GroupedAdam):     # (the division of fit.py:616-618 happened inside the launch)
+        if not self._grouped:
+            self.optimizer.step()
+            with torch.no_grad():   # fit.py:616-618 (Q3: whole-tensor norm)
+                self.q_opt /= torch.sum(self.q_opt ** 2) ** 0.5
+                self.per_frame_q /= torch.sum(self.per_frame_q ** 2) ** 0.5
             return
-        with torch.no_grad():   # fit.py:616-618 (Q3: whole-tensor norm)
-            self.q_opt /= torch.sum(self.q_opt ** 2) ** 0.5
-            self.per_frame_q /= torch.sum(self.per_frame_q ** 2) ** 0.5
+        if self.optimizer.capturable and not prepared:
+            self.optimizer.prepare()      # (an eager step of a graph-mode Fitter: warm-up, or a new set of trainable tensors)
+        self.optimizer.skip_flag = self._skip_cur
+        self.optimizer.step()             # (the division of fit.py:616-618 happens inside the launch)
+
+    def _eager_step(self, frame_ids, view_ids, prepared):
+        """Forward + backward, gradient all-reduce and update as plain launches: a step outside graph mode, and a graph-mode Fitter's
+        warm-up steps and the one step after its set of trainable tensors has changed."""
+        loss = self.loss_and_backward(frame_ids, view_ids, validate=False)
+        if self.reduce_fn is not None:
+            self.reduce_fn(self.params)
+        # the skip flag of this step's objective, on its way to the update.  Inert in graph mode: an optimiser made for replay has no skip
+        # counters (__init__ enables them for a GroupedAdam that is not capturable only), so _skip_target() gave loss_and_backward None
+        if self._skip_cur is not None and getattr(self.reduce_fn, "flag", None) is not None:
+            self._skip_cur = self.reduce_fn.flag      # (the bucket lays itself out anew when the set of trainable tensors changes)
+        if self.world > 1 and self._skip_cur is self._skip_flag:      # (a reducer without a flag element: the flag travels alone)
+            import torch.distributed as tdist
+            if tdist.is_initialized():
+                tdist.all_reduce(self._skip_flag, op=tdist.ReduceOp.SUM)
+        self._update(prepared)
+        return loss
 
     def step(self):
         """One Adam step (fit.py:524-618): forward, backward, gradient all-reduce, update, schedule, renormalise."""
@@ -1380,16 +1356,7 @@ class Fitter:
         if self.use_graph and self.iteration >= self.GRAPH_WARMUP:
             loss = self._step_graphed(frame_ids, view_ids, prepared)
         else:
-            loss = self.loss_and_backward(frame_ids, view_ids, validate=False)
-            if self.reduce_fn is not None:
-                self.reduce_fn(self.params)
-                if self._skip_cur is not None and getattr(self.reduce_fn, "flag", None) is not None:
-                    self._skip_cur = self.reduce_fn.flag      # (the bucket lays itself out anew when the set of trainable tensors changes)
-            if self.world > 1 and self._skip_cur is self._skip_flag:      # (a reducer without a flag element: the flag travels alone)
-                import torch.distributed as tdist
-                if tdist.is_initialized():
-                    tdist.all_reduce(self._skip_flag, op=tdist.ReduceOp.SUM)
-            self._update(prepared)
+            loss = self._eager_step(frame_ids, view_ids, prepared)
         self.scheduler.step()
         if self.cfg.log_interval:
             self._log_step(frame_ids, loss)
@@ -1448,12 +1415,8 @@ class Fitter:
         if self._graph_key != key:
             # new set of trainable tensors: one eager step first, so that Adam creates their state outside a capture
             self._graph_key, self._graphs = key, None
-            loss = self.loss_and_backward(frame_ids, view_ids, validate=False)
-            if self.reduce_fn is not None:
-                self.reduce_fn(self.params)
-            self._update(prepared)
-            return loss
-        cap_adam = isinstance(self.optimizer, GroupedAdam) and self.optimizer.capturable
+            return self._eager_step(frame_ids, view_ids, prepared)
+        cap_adam = self._grouped and self.optimizer.capturable
         if self._graphs is None:
             if _lib.TIMER is not None:
                 raise RuntimeError("per-kernel timing (KernelTimer) cannot be recorded inside a HIP graph")

@@ -111,8 +111,13 @@ class no_region_hints:
         region_hints = self._old
 
 
+def _n_bins(B, H, W):
+    """32 x 32-pixel bins of a batch of B images."""
+    return B * ((H + _lib.OCC_BIN - 1) // _lib.OCC_BIN) * ((W + _lib.OCC_BIN - 1) // _lib.OCC_BIN)
+
+
 def _hint_bytes(B, H, W):
-    return 2 * B * ((H + _lib.OCC_BIN - 1) // _lib.OCC_BIN) * ((W + _lib.OCC_BIN - 1) // _lib.OCC_BIN)     # FPCDR_HINT_BYTES
+    return 2 * _n_bins(B, H, W)     # FPCDR_HINT_BYTES
 
 
 # ----------------------------------------------------------------------------------------------
@@ -426,9 +431,7 @@ class _pixel_objective_func(torch.autograd.Function):
         # mip_levels = n: the reference's enable_mip branch inside the same kernels (the chain is built here, box filter as texture())
         chain = _build_mips(tex[None], mip_levels)[1:] if mip_levels is not None else []
         if mip_levels is not None:
-            p.mip, p.n_levels = 1, len(chain)
-            for l, t in enumerate(chain):
-                p.tex_mip[l] = _ptr(t)
+            _wire_mips(p, chain)
         g_aa = torch.empty_like(color)
         sil = torch.empty(B, T, dtype=torch.uint8, device=dev)
         nflag = lib.fpcdr_antialias_flags_bytes(B, H, W) // 8
@@ -449,8 +452,7 @@ class _pixel_objective_func(torch.autograd.Function):
             if hints is not None:
                 # (the counts are read back after the BACKWARD call has been enqueued: the copy would otherwise sit between the
                 # two large kernels on the stream)
-                nb = B * ((H + _lib.OCC_BIN - 1) // _lib.OCC_BIN) * ((W + _lib.OCC_BIN - 1) // _lib.OCC_BIN)
-                off = (4 * nb + 3) // 4 * 4                       # FPCDR_OCC_COUNTS_OFFSET
+                off = (4 * _n_bins(B, H, W) + 3) // 4 * 4                       # FPCDR_OCC_COUNTS_OFFSET
                 ctx.hint_update = (hints, occ[off:off + 16].view(torch.int32))
         else:
             _lib.call("fpcdr_render_fwd", ctypes.byref(p), _stream())
@@ -496,41 +498,16 @@ class _pixel_objective_func(torch.autograd.Function):
                              grad_tex=_ptr(g_tex), tri_uv=_ptr(tri_uv), upstream=_ptr(g),    # g: applied inside the kernel
                              queued=ctx.queued, cap_bwd=ctx.cap_bwd, binflags=1 if occ is not None else 0)
         if ctx.mip:
-            p.mip, p.n_levels = 1, len(chain)
-            for l, t in enumerate(chain):
-                p.tex_mip[l] = _ptr(t)
-                if g_chain:
-                    p.grad_tex_mip[l] = _ptr(g_chain[l])
+            _wire_mips(p, chain, g_chain)
         _lib.call("fpcdr_render_aa_bwd", ctypes.byref(p), _stream())
-        if g_chain:      # fold the levels' gradients into the texture's (the box filter's backward, coarse to fine)
-            g_all = [g_tex[None]] + g_chain
-            for l in range(len(chain), 0, -1):
-                _, h, w, _ = g_all[l - 1].shape
-                _lib.call("fpcdr_mip_downsample_bwd", _ptr(g_all[l]), _ptr(g_all[l - 1]), 1, h, w, C, _stream())
+        if g_chain:
+            _fold_mip_grads([g_tex[None]] + g_chain)
         if ctx.hint_update is not None:
             ctx.hint_update[0].update(ctx.hint_update[1])
             ctx.hint_update = None
         if not ctx.needs_input_grad[0]:
             g_pos = None
         return (g_pos, g_tex) + (None,) * 16
-
-
-_side_streams = {}
-
-
-# The silhouette bits of the one-pass objective on a second stream, beside the rasteriser's set-up kernel (fpcdr_objective_params.sil_ready /
-# sil_event)?  Off: at cfg3 the ~60 us the overlap hides are what the set-up kernel -- bound by memory latency -- loses to the company plus the
-# ~10 us a cross-stream wait costs the main stream on this runtime, event long complete or not (2.78 ms per step without, 2.80 with;
-# profiles/r04_stream_overlap.txt).
-OVERLAP_SIL = False
-
-
-def _side_stream(dev):
-    """One helper stream per device (the silhouette bits of the one-pass objective run on it beside the rasteriser's set-up)."""
-    st = _side_streams.get(dev.index)
-    if st is None:
-        st = _side_streams[dev.index] = torch.cuda.Stream(device=dev)
-    return st
 
 
 class _pixel_objective_onepass(torch.autograd.Function):
@@ -540,7 +517,7 @@ class _pixel_objective_onepass(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pos, tex, tri, adj, uv, uv_tri, ref, H, W, n_total, bg, boundary, ref_bg_sumsq, use_hints, want_grad, unit_upstream,
-                flags_out=None, mip_levels=None, zero_extra=None, overlap_sil=None, bin_lists=True, idp_out=None, record_slots=None,
+                flags_out=None, mip_levels=None, zero_extra=None, bin_lists=True, idp_out=None, record_slots=None,
                 skip_out=None):
         lib = _lib.load()
         B, V, _ = pos.shape
@@ -574,29 +551,10 @@ class _pixel_objective_onepass(torch.autograd.Function):
         chain = _build_mips(tex[None], mip_levels)[1:] if mip_levels is not None else []
         g_chain = [torch.empty_like(t) for t in chain] if want_tex else []
         if mip_levels is not None:
-            p.mip, p.n_levels = 1, len(chain)
-            for l, t in enumerate(chain):
-                p.tex_mip[l] = _ptr(t)
-                if g_chain:
-                    p.grad_tex_mip[l] = _ptr(g_chain[l])
-        # the silhouette bits need the positions only: on a second stream they run beside the rasteriser's set-up kernel (not inside a
-        # graph capture, where the fork would become part of the caller's graph topology).  Forked HERE, behind the zero-fills of the
-        # gradient buffers above: started earlier the kernel shares the memory system with them (the 69 MB fill took 68 us instead of 12)
-        if overlap_sil is None:
-            overlap_sil = OVERLAP_SIL
-        side = _side_stream(dev) if (overlap_sil and not torch.cuda.is_current_stream_capturing()) else None
-        if side is not None:
-            main = torch.cuda.current_stream(dev)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                _lib.call("fpcdr_silhouette_bits", _ptr(pos), _ptr(tri), _ptr(adj), B, V, T, H, W, _ptr(sil), ctypes.c_void_p(side.cuda_stream))
-                sil_event = torch.cuda.Event()
-                sil_event.record(side)
-            for t_ in (pos, tri, adj, sil):
-                t_.record_stream(side)
+            _wire_mips(p, chain, g_chain)
         capturing = torch.cuda.is_current_stream_capturing()
         hints = _hints_for(('onepass', dev.index, B, V, T, H, W), _MappedHints) if use_hints else None
-        nbins = B * ((H + _lib.OCC_BIN - 1) // _lib.OCC_BIN) * ((W + _lib.OCC_BIN - 1) // _lib.OCC_BIN)
+        nbins = _n_bins(B, H, W)
         if hints is not None:
             p.cap_bins, p.cap_occ, p.cap_def = hints.poll()      # (live bins, occupied bins, bins with a deferred pixel)
             # a batch of few bins -- one image of the reference's run shape has 1 900 -- is launched at its full size whatever the
@@ -654,14 +612,9 @@ class _pixel_objective_onepass(torch.autograd.Function):
         p.bg_sumsq, p.bg_coeff, p.n_total, p.value_out = _ptr(bg_sum), float(C), float(n_total), _ptr(out)
         if zero_extra is not None:      # (a caller's own small accumulators, zero-filled by the call's first kernel)
             p.zero_extra, p.zero_extra_bytes = _ptr(zero_extra), zero_extra.numel() * zero_extra.element_size()
-        if side is not None:      # (the call waits for the event right before its first kernel that reads the bits)
-            p.sil_ready, p.sil_event = 1, ctypes.c_void_p(sil_event.cuda_event)
         _lib.call("fpcdr_objective_fwd", ctypes.byref(p), _stream())
-        if g_chain:      # fold the levels' gradients into the texture's (the box filter's backward, coarse to fine)
-            g_all = [g_tex[None]] + g_chain
-            for l in range(len(chain), 0, -1):
-                _, h, w, _ = g_all[l - 1].shape
-                _lib.call("fpcdr_mip_downsample_bwd", _ptr(g_all[l]), _ptr(g_all[l - 1]), 1, h, w, C, _stream())
+        if g_chain:
+            _fold_mip_grads([g_tex[None]] + g_chain)
         ctx.save_for_backward(*(t for t in (g_pos, g_tex) if t is not None))
         ctx.have = (want_pos, want_tex)
         ctx.unit = bool(unit_upstream)
@@ -678,7 +631,7 @@ class _pixel_objective_onepass(torch.autograd.Function):
             g = g.to(torch.float32)
             g_pos = g_pos * g if g_pos is not None else None
             g_tex = g_tex * g if g_tex is not None else None
-        return (g_pos if ctx.needs_input_grad[0] else None, g_tex if ctx.needs_input_grad[1] else None) + (None,) * 22
+        return (g_pos if ctx.needs_input_grad[0] else None, g_tex if ctx.needs_input_grad[1] else None) + (None,) * 21
 
 
 def reference_background_sumsq(ref_u8, background=45.0 / 255.0):
@@ -1073,7 +1026,7 @@ def pixel_objective(glctx, pos, tri, uv, uv_tri, tex, ref_u8, resolution, n_tota
         return _pixel_objective_onepass.apply(pos.contiguous(), tex.contiguous(), tri, adj, uv.contiguous(), uv_tri.contiguous(),
                                               ref_u8.contiguous(), H, W, n_total, background, _lib.BOUNDARY[boundary_mode], ref_bg_sumsq,
                                               bool(launch_hints), torch.is_grad_enabled(), bool(unit_upstream), aa_flags_out, mip_levels, zero_extra,
-                                              None, True, id_plane_out, record_slots, skip_out)
+                                              True, id_plane_out, record_slots, skip_out)
     if skip_out is not None:
         raise ValueError("skip_out belongs to the one-pass form")
     if record_slots is not None:
@@ -1241,6 +1194,23 @@ def texture_construct_mip(tex, max_mip_level=None, cube_mode=False):
         return MipStack(_build_mips(tex.contiguous(), n)[1:], tex)
 
 
+def _wire_mips(p, chain, g_chain=()):
+    """Levels 1..n of a texture's mip chain -- and the buffers of their gradients, when there are any -- into the tex_mip / grad_tex_mip
+    tables of an objective's parameter struct."""
+    p.mip, p.n_levels = 1, len(chain)
+    for l, t in enumerate(chain):
+        p.tex_mip[l] = _ptr(t)
+        if g_chain:
+            p.grad_tex_mip[l] = _ptr(g_chain[l])
+
+
+def _fold_mip_grads(g_levels):
+    """Fold the gradients of a mip chain's levels [N,h,w,C] (level 0 first) into level 0's: the box filter's backward, coarse to fine."""
+    for l in range(len(g_levels) - 1, 0, -1):
+        N, h, w, C = g_levels[l - 1].shape
+        _lib.call("fpcdr_mip_downsample_bwd", _ptr(g_levels[l]), _ptr(g_levels[l - 1]), N, h, w, C, _stream())
+
+
 def _ptr_array(tensors):
     arr = (ctypes.c_void_p * (_lib.MAX_MIP + 1))()
     for i, t in enumerate(tensors):
@@ -1293,10 +1263,7 @@ class _texture_func(torch.autograd.Function):
         if ctx.custom:
             return (g_levels[0], g_uv, g_da, g_bias, None, None, None, None, None, None) + tuple(g_levels[1:])
         if need_tex:
-            # collapse the mip gradients down to level 0
-            for l in range(n_levels, 0, -1):
-                N, h, w, _ = chain[l - 1].shape
-                _lib.call("fpcdr_mip_downsample_bwd", _ptr(g_levels[l]), _ptr(g_levels[l - 1]), N, h, w, C, _stream())
+            _fold_mip_grads(g_levels)
         return (g_levels[0], g_uv, g_da, g_bias, None, None, None, None, None, None) + (None,) * (len(chain) - 1)
 
 

@@ -111,8 +111,10 @@ def _rasterize_fwd(m, ranges=None):
     return rast.cpu()
 
 
-def _objective_fwd(m, bin_lists):
-    """fpcdr_objective_fwd, value only, records addressed by pixel, no launch hints -> (id planes [B, bins * 1024] int32, sil [B,T] uint8)."""
+def _objective_fwd(m, bin_lists, sil_on=None):
+    """fpcdr_objective_fwd, value only, records addressed by pixel, no launch hints -> (id planes [B, bins * 1024] int32, sil [B,T] uint8).
+    sil_on: the caller computes the silhouette bits itself (fpcdr_silhouette_bits, sil_ready = 1) -- 'own': on the call's stream;
+    'side': on a second stream, with the event recorded behind it handed over as sil_event."""
     from fpc_diffrend_amd import _lib
     from fpc_diffrend_amd.ops import _ptr, _stream
     lib = _lib.load()
@@ -141,8 +143,18 @@ def _objective_fwd(m, bin_lists):
                        ref=_ptr(ref), bg=45.0 / 255.0, color_scale=255.0, grad_scale=1.0 / n_rec, sil=_ptr(sil), idp=_ptr(idp), occ=_ptr(occ),
                        cmask=_ptr(cmask), empty_color=_ptr(ecol), loss_sum=_ptr(acc), grad_pos=None, grad_tex=None, binlist=_ptr(binlist),
                        zero_outputs=1, rec=_ptr(rec), color=_ptr(color), grad_aa=_ptr(g_aa))
+    if sil_on is not None:
+        main = torch.cuda.current_stream()
+        st = torch.cuda.Stream() if sil_on == 'side' else main
+        st.wait_stream(main)      # (the inputs were made on the current stream)
+        _lib.call("fpcdr_silhouette_bits", _ptr(m['pos']), _ptr(m['tri']), _ptr(m['adj']), B, V, T, H, W, _ptr(sil), ctypes.c_void_p(st.cuda_stream))
+        p.sil_ready = 1
+        if sil_on == 'side':
+            event = torch.cuda.Event()
+            event.record(st)
+            p.sil_event = ctypes.c_void_p(event.cuda_event)
     _lib.call("fpcdr_objective_fwd", ctypes.byref(p), _stream())
-    torch.cuda.synchronize()
+    torch.cuda.synchronize()      # (both streams: every buffer above lives until here)
     return idp.view(torch.int32).reshape(B, -1).cpu(), sil.reshape(B, T).cpu()
 
 
@@ -222,3 +234,16 @@ def test_objective_fwd_ids_and_silhouette_bits_with_invalid_indices(bin_lists):
     bsel = torch.nonzero(covered, as_tuple=True)[0]
     assert torch.equal(bits[covered].to(torch.uint8), want[bsel, (ids[covered] - 1).long()])
     assert int(bits[~covered].abs().sum()) == 0
+
+
+@pytest.mark.parametrize("bin_lists", [True, False])
+def test_objective_fwd_takes_the_callers_silhouette_bits(bin_lists):
+    """fpcdr_objective_params.sil_ready / sil_event: a host that computes the silhouette bits itself -- (a) on the call's own
+    stream, (b) on a second stream, with the event recorded behind the kernel -- gets the id planes of the plain call, bit for bit (the
+    bits are the planes' bits 24 and above, so they reached the rasteriser unchanged)."""
+    m = _inputs()
+    planes, _ = _objective_fwd(m, bin_lists)
+    assert int(((planes >> 24) & 0xff != 0).sum()) > 100      # (silhouette bits show)
+    for sil_on in ('own', 'side'):
+        got, _ = _objective_fwd(m, bin_lists, sil_on=sil_on)
+        assert torch.equal(got, planes), f"sil_ready = 1, bits computed on {sil_on} stream: the id planes differ from the plain call's"
