@@ -194,6 +194,7 @@ SYMBOLS = {
     "fpcdr_bake_accumulate_u8": (_int, [_p, _p, _p, _p, ctypes.c_int64, _i, _i, _i, _i, _i, _i, _i, _p]),
     "fpcdr_bake_resolve": (_int, [_p, _p, _p, _i, _i, ctypes.c_double, ctypes.c_uint64, _p]),
     "fpcdr_bake_dilate": (_int, [_p, _p, _p, _p, _i, _i, _p]),
+    "fpcdr_downsample_u8": (_int, [_p, _p, ctypes.c_int64, _i, _i, _i, _p]),
 }
 
 # the two-call form of the pixel objective + the fused render pair (include/fpcdr_twocall.h): exported by libfpcdr_twocall.so only

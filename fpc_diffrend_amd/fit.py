@@ -27,7 +27,7 @@ import math
 import os
 import time
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -681,7 +681,9 @@ class FitConfig:
     lr_q: float = 10e-6
     enable_mip: bool = False
     max_mip_level: int = 6
-    resolution: Optional[Sequence[int]] = None     # (H, W); default: the scene's
+    resolution: Optional[Sequence[int]] = None     # (H, W); default: the scene's.  On a take from disk (scene.from_take) a size that is the
+                                                   # images' divided by one integer factor in 2..16 fits at that size: the captures are
+                                                   # reduced once, at construction (ops.downsample_images)
     weight_laplacian: float = 5000.0
     weight_meshedge: float = 0.0
     weight_normalconsistency: float = 0.0
@@ -722,6 +724,16 @@ class FitConfig:
     blur_kernel_size: int = 31      # odd, 3 .. 63 (the reference's GaussianBlur(kernel_size=(31, 31)), fit.py:506)
     blur_iters: int = 0             # 0 = every iteration is blurred; n = iterations i < n, then the run continues on the path the other
                                     # flags select (the one-pass objective by default)
+    pyramid: Sequence[Tuple[int, int]] = ()   # coarse-to-fine on a resolution pyramid of the captures: entries (factor, iterations) in order,
+                                    # e.g. ((8, 300), (4, 300), (2, 400)) = iterations 0-299 at 1/8 of the size, 300-599 at 1/4, 600-999 at
+                                    # 1/2, everything after at full size (a factor of 1 is allowed in an entry).  A level renders at
+                                    # (H / factor, W / factor) with the same matrices -- the projection chain is pure NDC -- against the
+                                    # captures box-reduced by that factor ("Downsample rule"), on the one-pass objective,
+                                    # touching 1 / factor^2 of the pixels.  () = off: a step is exactly the path it was
+    pyramid_mip: bool = True        # a step at a factor above 1 runs with enable_mip=True (max_mip_level as configured), whatever enable_mip
+                                    # says for full size; False: enable_mip everywhere.  On by default because the coarse levels are useless
+                                    # without it: the texture aliases under the 4-8 x larger pixel footprints, and on the CPU oracle's scan
+                                    #  the gradient at factor 8 then has the WRONG sign from 3 pixels of offset on
     log_interval: int = 0           # every n steps one JSON line {it, loss, lr, frames_per_s} (reference print, fit.py:621-623)
     reg_log_interval: int = 500     # every n steps the regulariser breakdown MEL / LAP / MNC (reference fit.py:597-601)
     log_path: Optional[str] = None  # JSON-lines file (appended); None with log_interval > 0 = stdout
@@ -764,6 +776,11 @@ class Fitter:
         self.n_frames = F
         self.frame_lo, self.frame_hi = _fdist.shard_frames(F, rank, world)      # (raises when F does not divide evenly over the ranks)
         self.resolution = tuple(cfg.resolution or sc.resolution)
+        self.full_resolution = self.resolution      # (the captures' size; `resolution` is the active pyramid level's, the same without one)
+        self._pyramid = self._check_pyramid(cfg, self.resolution)
+        # the mip flag of the active level (_set_level): cfg.enable_mip at full size and wherever pyramid_mip is off
+        self.enable_mip = bool(cfg.enable_mip)
+        mip_at_levels = bool(cfg.pyramid_mip and cfg.shading == 'texture' and any(s > 1 for s, _ in self._pyramid))
         self.cam_idxs = list(cfg.cam_idxs)
         # ---- static scene tensors (fit.py:424-432) ----
         self.v_base = torch.tensor(sc.v_base, dtype=torch.float32, device=dev)
@@ -804,7 +821,7 @@ class Fitter:
             self.maps['local'].requires_grad = True
             self.maps_intermediate['local'].requires_grad = True
             corrective_lr = cfg.lr_base * 0.1
-        self.glctx = dr.RasterizeGLContext(output_db=cfg.enable_mip, device=dev)
+        self.glctx = dr.RasterizeGLContext(output_db=bool(cfg.enable_mip or mip_at_levels), device=dev)
         # ---- optimiser: the reference's ten groups, same order (fit.py:493-505) ----
         groups = [{"params": self.m1, 'lr': corrective_lr}, {"params": self.m2, 'lr': corrective_lr},
                   {"params": self.m3, 'lr': corrective_lr}, {"params": self.maps['local'], 'lr': cfg.lr_base},
@@ -876,8 +893,9 @@ class Fitter:
         if targets is not None:
             self.targets = targets
         elif sc.images is not None:      # a take from disk: this rank's frames x the selected cameras
-            assert tuple(sc.images.shape[2:]) == self.resolution, "FitConfig.resolution differs from the take's images"
             self.targets = torch.from_numpy(np.ascontiguousarray(sc.images[self.frame_lo:self.frame_hi][:, self.cam_idxs])).to(dev)
+            if tuple(sc.images.shape[2:]) != self.resolution:      # a fixed reduced size: the captures box-reduced once
+                self.targets = dr.downsample_images(self.targets, self._take_factor(tuple(sc.images.shape[2:]), self.resolution))
         else:
             assert sc.weights_gt is not None, "a Scene needs reference images (scene.from_take) or a synthetic ground truth"
             self.targets = self.render_targets()
@@ -885,10 +903,73 @@ class Fitter:
         t = self.targets
         self.target_bg_sumsq = dr.reference_background_sumsq(t.reshape(-1, *self.resolution), BACKGROUND).reshape(t.shape[:2])
         self._bg_sum_key = None      # (the cached sum over the whole shard, loss_and_backward)
+        self.full_targets = self.targets      # (always the captures; `targets` is the active pyramid level's, the same tensor without one)
+        # ---- pyramid levels: per factor in use (targets, (H, W), target_bg_sumsq), each made from this rank's full-size targets ----
+        self._levels, self._level = None, 1
+        if self._pyramid:
+            self._levels = {1: (self.targets, self.resolution, self.target_bg_sumsq)}
+            for s in sorted({s for s, _ in self._pyramid if s > 1}):
+                lt = dr.downsample_images(self.full_targets, s)
+                lres = (self.resolution[0] // s, self.resolution[1] // s)
+                self._levels[s] = (lt, lres, dr.reference_background_sumsq(lt.reshape(-1, *lres), BACKGROUND).reshape(lt.shape[:2]))
         if cfg.init_texture == 'bake':
             self.bake_texture()
+        if self._levels is not None:
+            self._set_level(self.pyramid_factor())
 
     # ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_pyramid(cfg, resolution):
+        """FitConfig.pyramid as a tuple of (factor, iterations); ValueError for a malformed entry, a factor that does not divide the
+        resolution, or a combination with hip_graph."""
+        levels = []
+        for entry in tuple(cfg.pyramid or ()):
+            try:
+                s, n = entry
+                ok = int(s) == s and int(n) == n and not isinstance(s, bool) and not isinstance(n, bool)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok or not 1 <= int(s) <= 16 or int(n) < 0:
+                raise ValueError(f"FitConfig.pyramid holds entries (factor in 1..16, iterations >= 0) (got {entry!r})")
+            s, n = int(s), int(n)
+            if resolution[0] % s or resolution[1] % s:
+                raise ValueError(f"FitConfig.pyramid: the factor {s} does not divide the resolution {resolution[0]} x {resolution[1]}")
+            levels.append((s, n))
+        if levels and cfg.hip_graph:
+            raise ValueError("FitConfig.pyramid cannot be combined with hip_graph: the captured shapes would change from one level to "
+                             "the next")
+        return tuple(levels)
+
+    @staticmethod
+    def _take_factor(take_res, resolution):
+        """The one integer factor in 2..16 by which FitConfig.resolution divides a take's image size on both axes; ValueError otherwise."""
+        (Ht, Wt), (H, W) = take_res, resolution
+        s = Ht // H if H > 0 else 0
+        if not (2 <= s <= 16 and H * s == Ht and W * s == Wt):
+            raise ValueError(f"FitConfig.resolution {H} x {W} differs from the take's images ({Ht} x {Wt}) and is not their size divided by "
+                             "one integer factor in 2..16")
+        return s
+
+    def pyramid_factor(self, i=None):
+        """The pyramid factor of iteration i (default: the current one): 1 without a pyramid and after its last entry.  A function of the
+        iteration alone, like blur_taps, so a resumed run lands on the right level."""
+        i = self.iteration if i is None else i
+        for s, n in self._pyramid:
+            if i < n:
+                return s
+            i -= n
+        return 1
+
+    def _set_level(self, s):
+        """Make the level of factor s the active one: `resolution`, `targets`, `target_bg_sumsq` and `enable_mip` are that level's, and the
+        caches keyed to them are dropped.  full_resolution / full_targets keep naming the captures."""
+        if s == self._level:
+            return
+        self.targets, self.resolution, self.target_bg_sumsq = self._levels[s]
+        self.enable_mip = bool(self.cfg.enable_mip or (s > 1 and self.cfg.pyramid_mip))
+        self._bg_sum_key, self._targets_f32 = None, None
+        self._level = s
+
     @staticmethod
     def _n(frame_ids):
         return frame_ids.stop - frame_ids.start if isinstance(frame_ids, slice) else len(frame_ids)
@@ -996,7 +1077,7 @@ class Fitter:
 
         Returns (tex [Ht,Wt,C] float32, filled [Ht,Wt] bool: the texels a capture reached)."""
         dev = self.device
-        H, W = self.resolution
+        H, W = self.full_resolution
         Ht, Wt, C = self.tex_opt.shape
         if frame_ids is None:
             frames = torch.arange(self.frame_lo, self.frame_hi, device=dev)
@@ -1007,7 +1088,7 @@ class Fitter:
         frames = frames.long()
         views = None if views is None else views.long()
         glctx = dr.RasterizeGLContext(output_db=False, device=dev)
-        targets = self.targets.reshape(-1, H, W)
+        targets = self.full_targets.reshape(-1, H, W)
         acc = torch.zeros(Ht, Wt, 2, dtype=torch.int64, device=dev)
         for lo in range(0, int(frames.shape[0]), max(1, int(chunk))):
             ids = frames[lo:lo + max(1, int(chunk))].contiguous()
@@ -1034,7 +1115,7 @@ class Fitter:
         """Synthetic reference images: the hidden ground truth (weights, pose, texture) rendered through the
         same ops, quantised to 8 bit and clipped to [0,140] like the reference's loader (fit.py:531)."""
         sc, dev = self.sc, self.device
-        H, W = self.resolution
+        H, W = self.full_resolution
         Nc = len(self.cam_idxs)
         out = torch.empty(self.frame_hi - self.frame_lo, Nc, H, W, dtype=torch.uint8, device=dev)
         tex = torch.tensor(sc.texture, dtype=torch.float32, device=dev)
@@ -1048,18 +1129,18 @@ class Fitter:
             rigid = camera.rigid_grad(t_gt[ids], camera.unitquat_to_rotmat(q_gt[ids]))
             mvp = torch.matmul(self.proj[None], torch.matmul(rigid[:, None], self.t_mv[None])).reshape(-1, 4, 4)
             if self.cfg.shading == 'vertex':
-                img, rast_t = self.render_vertex(ctx, transform_clip_batched(mvp, verts))
+                img, rast_t = self.render_vertex(ctx, transform_clip_batched(mvp, verts), (H, W))
                 img = torch.where(rast_t[..., 3:] > 0, img, torch.tensor(BACKGROUND, device=dev))
             else:
-                img = render(ctx, mvp, verts, self.pos_idx, self.uv, self.uv_idx, tex, self.resolution, False, 0)
+                img = render(ctx, mvp, verts, self.pos_idx, self.uv, self.uv_idx, tex, (H, W), False, 0)
             img = torch.clamp(torch.round(img[..., 0] * 255.0), 0, 140).to(torch.uint8)
             out[lo - self.frame_lo: lo - self.frame_lo + len(ids)] = img.reshape(len(ids), Nc, H, W)
         return out
 
-    def render_vertex(self, glctx, pos_clip):
+    def render_vertex(self, glctx, pos_clip, resolution=None):
         """rasterize + interpolate only (no texture, no antialias): per-vertex grey through the uv index buffer,
-        background composited like fit.py:161.  Returns (colour [B,H,W,1], rast)."""
-        rast, _ = dr.rasterize(glctx, pos_clip, self.pos_idx, resolution=self.resolution)
+        background composited like fit.py:161.  resolution: default the active level's.  Returns (colour [B,H,W,1], rast)."""
+        rast, _ = dr.rasterize(glctx, pos_clip, self.pos_idx, resolution=resolution or self.resolution)
         col, _ = dr.interpolate(self.vcol[None], rast, self.uv_idx)
         return col, rast
 
@@ -1155,13 +1236,16 @@ class Fitter:
             self.check_indices(frame_ids, view_ids)
         cfg = self.cfg
         i = self.iteration
+        if self._levels is not None:      # (before anything below reads the resolution, the targets or the mip flag)
+            self._set_level(self.pyramid_factor(i))
+        mip = self.enable_mip
         self._mode_switch()
         self._skip_cur = None
         Fb, Nc = self._n(frame_ids), (len(self.cam_idxs) if view_ids is None else int(view_ids.shape[0]))
         C = self.tex_opt.shape[2]
         # (the mip branch of the reference's render(), fit.py:153-155, runs inside the same kernels)
         one_shot = (cfg.fused_objective and cfg.fused_render and cfg.fused_loss and C in (1, 3, 4) and cfg.shading == 'texture'
-                    and (not cfg.enable_mip or cfg.sparse_objective))
+                    and (not mip or cfg.sparse_objective))
         blur_taps = self.blur_taps(i) if cfg.blur_sigma > 0 else None
         if blur_taps is not None:
             one_shot = False           # the blurred loss needs the image in memory: the operator path
@@ -1189,7 +1273,7 @@ class Fitter:
             n_total = n_img_global * self.resolution[0] * self.resolution[1]
         elif not one_shot:
             colour, rast_out = render_from_clip(self.glctx, pos_clip, self.pos_idx, self.uv, self.uv_idx, self.tex_opt,
-                                                self.resolution, cfg.enable_mip, cfg.max_mip_level, cfg.fused_render)
+                                                self.resolution, mip, cfg.max_mip_level, cfg.fused_render)
         # regularisers (fit.py:578-595): evaluated on this rank's meshes, averaged over all ranks
         chain_terms = bool(cfg.weight_meshedge or cfg.weight_normalconsistency or (cfg.weight_laplacian and not cfg.fused_loss)
                            or (cfg.regularize_correctives and cfg.mode == 'combined' and i > cfg.max_iter / 2)
@@ -1232,7 +1316,7 @@ class Fitter:
             self._skip_cur = self._skip_target() if (cfg.one_pass and cfg.sparse_objective) else None
             pix = dr.pixel_objective(self.glctx, pos_clip, self.pos_idx, self.uv, self.uv_idx, self.tex_opt, ref, self.resolution,
                                      n_total, BACKGROUND, sparse=cfg.sparse_objective, ref_bg_sumsq=bg_sum,
-                                     enable_mip=cfg.enable_mip, max_mip_level=cfg.max_mip_level,
+                                     enable_mip=mip, max_mip_level=cfg.max_mip_level,
                                      queued_backward=cfg.queued_backward and not self.use_graph,
                                      one_pass=cfg.one_pass, unit_upstream=True, zero_extra=zero_buf,      # (the seeds below are 1)
                                      skip_out=self._skip_cur)
@@ -1347,6 +1431,8 @@ class Fitter:
     def step(self):
         """One Adam step (fit.py:524-618): forward, backward, gradient all-reduce, update, schedule, renormalise."""
         prepared = False
+        if self._levels is not None:
+            self._set_level(self.pyramid_factor())
         self._mode_switch()      # (before the optimiser's table of this step is written: a parameter that turns trainable now counts this step)
         if self.use_graph:
             frame_ids, view_ids, prepared = self._stage_inputs()
@@ -1500,6 +1586,8 @@ class Fitter:
         self.rng.bit_generator.state = state["rng"]
         self.result.copy_(state["result"].to(self.result.device))
         self._graphs, self._graph_key = None, None
+        if self._levels is not None:
+            self._set_level(self.pyramid_factor())
 
     def _load_optimizer(self, sd):
         """torch's Optimizer.load_state_dict replaces every param_group by the checkpoint's: a GroupedAdam checkpoint carries lr / betas /

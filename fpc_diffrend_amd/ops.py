@@ -30,7 +30,7 @@ from . import _lib
 
 __all__ = ['RasterizeGLContext', 'RasterizeCudaContext', 'RasterizeHipContext', 'rasterize', 'interpolate', 'texture',
            'texture_construct_mip', 'antialias', 'antialias_construct_topology_hash', 'render_textured', 'pixel_objective', 'undistort_images', 'compare_images',
-           'gaussian_taps', 'blurred_pixel_loss', 'bake_accumulate', 'bake_resolve']
+           'gaussian_taps', 'blurred_pixel_loss', 'bake_accumulate', 'bake_resolve', 'downsample_images']
 
 
 def _stream():
@@ -958,6 +958,33 @@ def bake_resolve(acc, color_scale=255.0, min_weight=0.0, dilate=8, hole_value=0.
                 cur, cur_f, nxt, nxt_f = nxt, nxt_f, cur, cur_f
     out = torch.where(cur_f, cur, torch.tensor(float(hole_value), dtype=torch.float32, device=dev))
     return out, filled
+
+
+def downsample_images(images, factor):
+    """Box reduction of 8-bit images by an integer factor, by the rule of DESIGN.md 3 "Downsample rule" (fpcdr_downsample_u8): every output
+    pixel is the exact mean of its factor x factor block of `images`, rounded half up, once; rows are not flipped.  A level of a resolution
+    pyramid (FitConfig.pyramid): the projection chain is pure NDC, so a render at (H / factor, W / factor) with the same matrices is aligned
+    with this reduction of the capture.  Make every level from the full-size images: a cascade rounds twice and gives other bytes.
+
+      images  uint8 GPU tensor [..., H, W] (made contiguous);  factor  an integer in 2..16 that divides H and W
+
+    Runs on the current stream and allocates its result only.  Returns a new uint8 tensor [..., H / factor, W / factor]."""
+    _check_tensor('images', images, torch.uint8)
+    if isinstance(factor, bool) or not isinstance(factor, (int, np.integer)):
+        raise ValueError(f"factor must be an integer (got {factor!r})")
+    factor = int(factor)
+    if not 2 <= factor <= 16:
+        raise ValueError(f"factor must lie in 2..16 (got {factor})")
+    if images.dim() < 2:
+        raise ValueError(f"images must be [..., H, W] (got shape {tuple(images.shape)})")
+    H, W = int(images.shape[-2]), int(images.shape[-1])
+    if H == 0 or W == 0 or H % factor or W % factor:
+        raise ValueError(f"factor {factor} does not divide the image size {H} x {W}")
+    images = images.contiguous()
+    out = torch.empty(tuple(images.shape[:-2]) + (H // factor, W // factor), dtype=torch.uint8, device=images.device)
+    with torch.cuda.device(images.device):
+        _lib.call("fpcdr_downsample_u8", _ptr(images), _ptr(out), images.numel() // (H * W), H, W, factor, _stream())
+    return out
 
 
 def pixel_objective(glctx, pos, tri, uv, uv_tri, tex, ref_u8, resolution, n_total=None, background=45.0 / 255.0,

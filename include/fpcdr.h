@@ -630,6 +630,16 @@ int fpcdr_bake_resolve(const uint64_t *acc, float *tex, uint8_t *filled, int Ht,
                        void *stream);
 int fpcdr_bake_dilate(const float *tex_in, const uint8_t *filled_in, float *tex_out, uint8_t *filled_out, int Ht, int Wt, void *stream);
 
+/* Box reduction of 8-bit images by an integer factor: the levels of a resolution pyramid of the captures.  A pure addition:
+ * FPCDR_ABI_VERSION stays 16.  DESIGN.md 3, "Downsample rule".
+ *   src [n_images, H, W] uint8, dst [n_images, H / s, W / s] uint8, fully overwritten
+ *   S(n, i, j) = sum of src[n, i * s + a, j * s + b] over 0 <= a, b < s                      (an integer of at most 65 280)
+ *   dst[n, i, j] = (2 * S + s * s) / (2 * s * s) in integer division: the exact mean, rounded half up, rounded once
+ * Rows are not flipped.  Make every level from the full-size image: a cascade of reductions rounds more than once and gives other bytes.
+ * Errors, before any launch: s outside 2..16, H or W not positive or not a multiple of s, n_images < 0, a NULL pointer, buffers that
+ * overlap.  n_images == 0 is success without a launch.  src and dst may sit at any address (wider accesses are used where it allows). */
+int fpcdr_downsample_u8(const uint8_t *src, uint8_t *dst, int64_t n_images, int H, int W, int s, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
