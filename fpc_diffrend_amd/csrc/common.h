@@ -6,7 +6,6 @@
 #include <stdlib.h>
 
 #include "../../include/fpcdr.h"
-#include "../../include/fpcdr_twocall.h"
 
 #define FPCDR_WAVE 64
 
@@ -31,11 +30,9 @@ void fpcdr_set_error(const char *fmt, ...);
 
 static inline int fpcdr_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
-// internal cross-file launchers (fused.hip), used by fpcdr_render_loss_fwd (rasterize.hip)
+// internal cross-file launcher (objective.hip), also used by the two-call form (fused.hip)
 int fpcdr_launch_sil(const float *pos, const int32_t *tri, const int32_t *adj, int B, int V, int T, int H, int W, uint8_t *sil,
                      void *zero_dst, size_t zero_bytes, hipStream_t st);
-int fpcdr_launch_aa_fix(const fpcdr_aa_loss_fwd_params *p, const uint32_t *cmask, const unsigned long long *edges,
-                        const int32_t *fix_list, const int32_t *fix_count, int nbins, hipStream_t st);
 
 // buffers the first kernel of fpcdr_objective_fwd zero-fills beside its own maps (fpcdr_objective_params.zero_outputs): 4-byte words
 struct FpcdrZeroList {

@@ -1,14 +1,19 @@
 // Fused pixel objective of the fit loop for gfx950 (MI355X): everything between the clip-space positions and
 // the scalar pixel loss of reference src/torch/fit.py:151-161 + :579, as three kernels instead of nine:
 //
-//   fpcdr_render_fwd (rasterize.hip)  rasterize + interpolate + texture      -> rast, colour        20 B/px
-//   fpcdr_aa_loss_fwd (this file)     antialias + background + pixel loss    -> d loss / d aa, flags 25 B/px
-//   fpcdr_render_aa_bwd (this file)   antialias bwd + texture bwd + interpolate bwd + rasterize bwd  20 B/px
+//   fpcdr_render_fwd      rasterize + interpolate + texture      -> rast, colour        20 B/px
+//   fpcdr_aa_loss_fwd     antialias + background + pixel loss    -> d loss / d aa, flags 25 B/px
+//   fpcdr_render_aa_bwd   antialias bwd + texture bwd + interpolate bwd + rasterize bwd  20 B/px
 //
 // versus 217 B/px for the separate operators (C = 1).  The antialiased colour, the texture-coordinate image and
 // every intermediate gradient image never reach HBM.  Values equal the separate operators' (same device
 // functions); the separate operators remain the nvdiffrast-compatible API and the parity reference.
+//
+// This is the two-call form of include/fpcdr_twocall.h, all of it: superseded by fpcdr_objective_fwd in the fit loop, kept as a parity
+// partner and for the dense mode, and compiled into libfpcdr_twocall.so only (csrc/Makefile).  Its forward kernels run the raster phase
+// they share with rasterize.hip (bin_raster.h) and read it out with shading, loss and antialias candidates (shade_bin below).
 #include "common.h"
+#include "../../include/fpcdr_twocall.h"
 
 #include <algorithm>
 #include <stdlib.h>
@@ -19,6 +24,8 @@ namespace {
 #include "raster_math.h"
 #include "aa_pairs.h"
 #include "sil_bits.h"
+
+#include "bin_raster.h"
 
 // ------------------------------------------------------------------------------------------------
 // Sparse mode: validity of pixels around a workgroup, from the occupancy map of fpcdr_render_fwd.  A pixel of an
@@ -249,7 +256,7 @@ struct MipArgs {
 };
 
 // BMODE >= 0: the texture boundary mode as a compile-time constant.  MIP: the texture lookup was 'linear-mipmap-linear' with the
-// footprint from the barycentrics' screen derivatives (bins_body<MIP>, rasterize.hip): texel gradients go to every level's buffer
+// footprint from the barycentrics' screen derivatives (shade_bin<MIP>): texel gradients go to every level's buffer
 // with global atomics (no LDS window), and the footprint's gradient flows through the derivative outputs of the rasteriser
 // (shade_pixel_bwd<true>), as in the chain interpolate(diff_attrs='all') -> texture(uv_da) of the separate operators.
 template <int CS, int BMODE = -1, bool MIP = false>
@@ -786,7 +793,7 @@ __global__ void __launch_bounds__(BWD_NT) FPCDR_BWDQ_WPE k_render_aa_bwd_queue(c
 }
 
 // ------------------------------------------------------------------------------------------------
-// Second half of fpcdr_render_loss_fwd.  k_bins<LOSS> (rasterize.hip) gave every pixel the loss term and gradient of
+// Second half of fpcdr_render_loss_fwd.  The LOSS read-out (shade_bin, below) gave every pixel the loss term and gradient of
 // its un-antialiased colour, marked the pixels with a silhouette pair INSIDE their bin and exported each bin's four
 // border lines.  One workgroup per 32x32 bin: 128 threads classify the pairs ACROSS the bin's border from its own and
 // its neighbours' lines (2 KB, contiguous), the candidates are gathered into an LDS list, and each gets the full
@@ -950,11 +957,455 @@ __global__ void __launch_bounds__(FIX_NT) k_aa_fix_queue(const int32_t *__restri
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// The fused render path (fpcdr_render_fwd, fpcdr_render_loss_fwd): the raster phase of bin_raster.h with a read-out in which the
+// thread that reads a pixel's winner also interpolates its texture coordinate and taps the texture, so texc never exists in HBM.
+struct ShadeArgs {
+    const float2 *uv;        // [Vt] texture coordinates
+    const int32_t *uv_tri;   // [T,3]
+    const float *tex;        // [Ht,Wt,C]
+    float *color;            // out [B,H,W,C]
+    int Ht, Wt, C, boundary;
+    uint8_t *occ;            // sparse mode (else null): out [B, gridDim.y, gridDim.x], 1 = some triangle's bounding box touches
+                             // the bin.  Bins with 0 are NOT written; the consumers treat their pixels as empty.
+                             // (k_occ_window turns this byte map into the per-bin window masks the consumers read)
+    float *empty_out;        // sparse mode: out [4], the colour an empty pixel gets (texture at uv = (0,0))
+    const float2 *tri_uv;    // optional [T,3]: uv[uv_tri] pre-gathered
+    // LOSS (fpcdr_render_loss_fwd): background + squared error of every pixel that antialiasing cannot touch
+    const uint8_t *sil;      // [B,T] silhouette bits (k_sil2)
+    const uint8_t *ref;      // [B,H,W]
+    float *g_aa;             // out [B,H,W,C]
+    uint32_t *cmask;         // out [B*bins][32]: row masks of the bin's CANDIDATE pixels, left to k_aa_fix
+    unsigned long long *edges;   // out [B*bins][4][32]: (z/w bits << 32 | silhouette bits << 24 | id + 1) of the four border lines
+    double *loss_sum;        // [FPCDR_LOSS_SLOTS]
+    float bg, color_scale, grad_scale;
+    // MIP instantiations (the reference's enable_mip branch, fit.py:153-155): tex = level 0, mip[l - 1] = level l of the chain
+    const float *mip[FPCDR_MAX_MIP];
+    int n_levels;
+};
+
+// One 32x32 bin (bxi, byi) of image b; OX x OY bins per image.  Every branch that leaves is uniform over the workgroup.
+// CS / BMODE: channel count and texture boundary mode as compile-time constants (0 / -1 = read them from ShadeArgs); the list
+// kernels of the objective are instantiated for the reference's case (one channel, 'wrap'), which strips the channel loops, the
+// index scaling and the mode branches from the ~200 instructions a shaded pixel costs
+template <bool LOSS, bool QUEUE, int CS = 0, int BMODE = -1, bool MIP = false>
+__device__ __forceinline__ void shade_bin(BinLds &lds, const int b, const int bxi, const int byi, const int OX, const int OY,
+                                          const float4 *__restrict__ pos, const int32_t *__restrict__ tri,
+                                          int V, int T, int H, int W, const TriRec *__restrict__ recs,
+                                          const TriBox *__restrict__ boxes, const TriBox *__restrict__ cboxes,
+                                          const ImgBox *__restrict__ ibox, float4 *__restrict__ rast, const ShadeArgs &sh) {
+    auto &s_z = lds.s_z; auto &s_tri = lds.s_tri; auto &s_list = lds.s_list;
+    const int bin_x0 = bxi * BIN, bin_y0 = byi * BIN;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t bin_lin = ((size_t)b * OY + byi) * OX + bxi;
+    const bool sparse = sh.occ != nullptr;
+    if (sparse && !QUEUE && b == 0 && bxi == 0 && byi == 0 && tid == 0) {   // (queue form: k_list_count writes it)
+        const Taps tp0 = make_taps(0.0f, 0.0f, sh.Ht, sh.Wt, sh.C, sh.boundary);
+        for (int c = 0; c < 4; ++c) sh.empty_out[c] = c < sh.C ? bilerp(sh.tex, tp0, c, sh.C) : 0.0f;
+    }
+    const BinHits bh = bin_raster<false>(lds, b, bxi, byi, OX, OY, T, H, W, recs, boxes, cboxes, ibox);
+    const bool bin_live = bh.live;
+    const int total_hits = bh.hits;
+    if (sparse) {      // (a bin the image's box does not reach, or no triangle's: no pixel is written, the consumers skip it too)
+        if (tid == 0) sh.occ[bin_lin] = total_hits > 0 ? 1 : 0;
+        if (total_hits == 0) return;
+    }
+    if (total_hits == 0) {
+        // ---- nothing touches this bin (most bins of a dense call): stream the empty result, two full 512-byte rows of
+        // rast per wave instruction instead of the shading loop's 8x8 quadrant pattern ----
+        float ecol[4] = {0.f, 0.f, 0.f, 0.f};
+        const Taps tp0 = make_taps(0.0f, 0.0f, sh.Ht, sh.Wt, sh.C, sh.boundary);
+        for (int c = 0; c < min(sh.C, 4); ++c) ecol[c] = bilerp(sh.tex, tp0, c, sh.C);
+        for (int i = tid; i < BIN * BIN; i += 256) {
+            const int px = bin_x0 + (i % BIN), py = bin_y0 + (i / BIN);
+            if (px >= W || py >= H) continue;
+            const size_t off = ((size_t)b * H + py) * W + px;
+            rast[off] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (sh.C <= 4) { for (int c = 0; c < sh.C; ++c) sh.color[off * sh.C + c] = ecol[c]; }
+            else {
+                const Taps tp0 = make_taps(0.0f, 0.0f, sh.Ht, sh.Wt, sh.C, sh.boundary);
+                for (int c = 0; c < sh.C; ++c) sh.color[off * sh.C + c] = bilerp(sh.tex, tp0, c, sh.C);
+            }
+        }
+        return;
+    }
+    const int C = CS > 0 ? CS : sh.C, boundary = BMODE >= 0 ? BMODE : sh.boundary;
+    // ---- read every pixel's winner ----
+    // From here on a thread owns the four pixels (tid & 31, (tid >> 5) + 8 k) of the bin: the 32 lanes of a half wave write
+    // one 512-byte row segment of rast per instruction (the raster's 8 x 8 quadrant pattern gave 128-byte pieces).
+    int win[4];
+    __shared__ float s_fy[BIN];      // NDC y of the bin's 32 rows: one IEEE division per row instead of one per pixel
+    if (tid < BIN) s_fy[tid] = (2.0f * (float)(bin_y0 + tid) + 1.0f) / (float)H - 1.0f;
+    __syncthreads();      // (the raster phase's folded winners, and s_fy)
+    const int zx = tid & 31, zy0 = tid >> 5;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned long long z = bin_live ? s_z[(zy0 + 8 * k) * BIN + zx] : Z_EMPTY;
+        win[k] = z == Z_EMPTY ? -1 : (int)(unsigned int)z;
+    }
+
+    // ---- shade + write (every pixel of the bin is written exactly once) ----
+    // One-channel colour and its loss gradient are 4 bytes per pixel: stores of 4 bytes per lane reach a quarter of the rate of
+    // 16-byte ones, so both are staged in LDS (the raster phase's lists are dead by now) and leave as float4 at the end.
+    static_assert(sizeof(s_list) >= BIN * BIN * sizeof(float) && sizeof(s_tri) >= BIN * BIN * sizeof(float), "staging aliases the raster lists");
+    float *s_col = reinterpret_cast<float *>(s_list);
+    float *s_gaa = reinterpret_cast<float *>(s_tri);
+    const bool stage = C == 1;
+    float col0[4] = {0.f, 0.f, 0.f, 0.f};   // LOSS: channel 0 of this thread's pixels (re-reading a just-written line stalls)
+    unsigned int any_sil = 0u;              // LOSS: silhouette bits of the triangles this thread's pixels show, OR-ed
+    const float sx = 2.0f / (float)W, sy = 2.0f / (float)H;
+    const float4 *p = pos + (size_t)b * V;
+    Taps empty_tp = {};
+    float empty_col[4] = {0.f, 0.f, 0.f, 0.f};
+    if (QUEUE && C <= 4) {
+        // list form: the colour of an empty pixel was computed once for the call (k_list_count, block 0) -- four scalar loads
+        // instead of a tap set and four texel loads in front of every bin's shading
+        for (int c = 0; c < C; ++c) empty_col[c] = sh.empty_out[c];
+    } else {
+        empty_tp = make_taps(0.0f, 0.0f, sh.Ht, sh.Wt, C, boundary);
+        for (int c = 0; c < min(C, 4); ++c) empty_col[c] = bilerp(sh.tex, empty_tp, c, C);
+    }
+    const int px = bin_x0 + zx;
+    // Every gather below goes through a 32-bit byte offset from a wave-uniform base (common.h ld32 / at32): per-image vertex, index
+    // and silhouette arrays, and the bin's own pixels at bin_off + zy * W + zx.
+    struct I3 { int a, b, c; };
+    struct UV3 { float2 q0, q1, q2; };
+    const size_t bin_off = ((size_t)b * H + bin_y0) * W + bin_x0;
+    float4 *const rast_bin = rast + bin_off;
+    const uint8_t *const sil_img = LOSS ? sh.sil + (size_t)b * T : nullptr;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int zy = zy0 + 8 * k, py = bin_y0 + zy;
+        if (px >= W || py >= H) continue;
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f), d = make_float4(0.f, 0.f, 0.f, 0.f);
+        const int t = win[k];
+        if (t >= 0) {
+            const I3 ti = ld32(reinterpret_cast<const I3 *>(tri), t);
+            const float fx = (2.0f * (float)px + 1.0f) / (float)W - 1.0f;
+            const float fy = s_fy[zy];
+            Shade sd = shade_pixel(ld32(p, ti.a), ld32(p, ti.b), ld32(p, ti.c), fx, fy, sx, sy);
+            o = make_float4(sd.u, sd.v, sd.zw, (float)(t + 1));
+            d = make_float4(sd.dudx, sd.dudy, sd.dvdx, sd.dvdy);
+        }
+        const unsigned int poff = (unsigned int)(zy * W + zx);      // pixel offset inside the bin's window of the image
+        const size_t off = bin_off + poff;
+        at32(rast_bin, poff) = o;
+        if (LOSS) {   // (z/w, id) of the bin's pixels for the neighbour tests below; this thread owns the entry
+            // id + 1 in 24 bits (ids are exact in rast's float anyway), the triangle's silhouette bits above them
+            const unsigned int sb = t >= 0 ? (unsigned int)ld32(sil_img, t) : 0u;
+            any_sil |= sb;
+            s_z[zy * BIN + zx] = ((unsigned long long)__float_as_uint(o.z) << 32) | (sb << 24) | (unsigned int)(t + 1);
+        }
+        // interpolate (reference fit.py:157) + texture 'linear' (fit.py:158), same arithmetic as the stand-alone
+        // kernels; an empty pixel samples uv = (0,0) exactly as they do (one tap set, hoisted out of the loops)
+        if (t >= 0) {
+            float2 q0, q1, q2;
+            if (sh.tri_uv) { const UV3 tq = ld32(reinterpret_cast<const UV3 *>(sh.tri_uv), t); q0 = tq.q0; q1 = tq.q1; q2 = tq.q2; }
+            else uv_indirect(sh.uv, sh.uv_tri, t, q0, q1, q2);      // (out of line: merged with the branch above, its loads would drag
+                                                                   //  64-bit address arithmetic into the common path)
+            const float w = 1.0f - o.x - o.y;
+            const float tu = o.x * q0.x + o.y * q1.x + w * q2.x;
+            const float tv = o.x * q0.y + o.y * q1.y + w * q2.y;
+            auto put = [&](int c, float v) {
+                if (stage) s_col[zy * BIN + zx] = v;
+                else sh.color[off * C + c] = v;
+                if (LOSS && c == 0) col0[k] = v;
+            };
+            if (MIP) {
+                // interpolate(..., rast_db, diff_attrs='all') + texture('linear-mipmap-linear') (fit.py:153-155), same arithmetic as
+                // the stand-alone kernels: the footprint of the texture coordinate from the barycentrics' screen derivatives
+                const float e0x = q0.x - q2.x, e0y = q0.y - q2.y, e1x = q1.x - q2.x, e1y = q1.y - q2.y;
+                const float4 da = make_float4(d.x * e0x + d.z * e1x, d.y * e0x + d.w * e1x, d.x * e0y + d.z * e1y, d.y * e0y + d.w * e1y);
+                TexLevels lv;
+                lv.tex[0] = sh.tex;
+                for (int l = 1; l <= FPCDR_MAX_MIP; ++l) lv.tex[l] = sh.mip[l - 1];
+                mip_sample_fwd(lv, 0, sh.n_levels, make_float2(tu, tv), true, da, 0.0f, sh.Ht, sh.Wt, C, true, boundary, put);
+            } else {
+            // ('zero' takes the general tap routine: its taps carry validity bits, which bilerp masks by)
+            const Taps tp = boundary == FPCDR_BOUNDARY_ZERO ? make_taps(tu, tv, sh.Ht, sh.Wt, C, boundary)
+                                                            : make_taps_fast(tu, tv, sh.Ht, sh.Wt, C, boundary);
+            for (int c = 0; c < C; ++c) put(c, bilerp<true>(sh.tex, tp, c, C));      // (the fused entry points require < 2^30 texel values)
+            }
+        } else if (stage) {
+            s_col[zy * BIN + zx] = empty_col[0];
+        } else {
+            for (int c = 0; c < C; ++c) sh.color[off * C + c] = c < 4 ? empty_col[c] : bilerp(sh.tex, empty_tp, c, C);
+        }
+    }
+    // the staged planes leave as 16-byte stores: thread -> four adjacent pixels of row tid >> 3
+    auto flush_plane = [&](const float *s_plane, float *__restrict__ dst) {
+        const int r = tid >> 3, c4 = (tid & 7) * 4;
+        const int fx0 = bin_x0 + c4, fy = bin_y0 + r;
+        if (fy >= H || fx0 >= W) return;
+        float *const dst_bin = dst + bin_off;      // (uniform)
+        const unsigned int poff = (unsigned int)(r * W + c4);
+        const float4 v = *reinterpret_cast<const float4 *>(s_plane + r * BIN + c4);
+        if ((W & 3) == 0 && (((size_t)dst) & 15) == 0) *reinterpret_cast<float4 *>(&at32(dst_bin, poff)) = v;
+        else {
+            const float e[4] = {v.x, v.y, v.z, v.w};
+            for (int j = 0; j < 4; ++j)
+                if (fx0 + j < W) at32(dst_bin, poff + j) = e[j];
+        }
+    };
+    if (!LOSS) {
+        if (stage) {     // (uniform)
+            __syncthreads();
+            flush_plane(s_col, sh.color);
+        }
+    }
+    if (LOSS) {
+        // ---- every pixel gets the loss term and gradient of its UN-antialiased colour; CANDIDATES are marked ----
+        // A pixel's antialiased colour differs from its colour only if one of its four pixel pairs has different ids AND
+        // the nearer triangle of the pair has a silhouette edge (the early-outs of for_active_edges, aa_pairs.h).  The
+        // pairs inside the bin are classified here from the ids in LDS; for the pairs across the bin's border the four
+        // border lines (z/w, id) go to a compact edge buffer.  k_aa_fix (fused.hip) classifies those, runs the full
+        // antialias on the candidates only and corrects their loss / gradient: no dense antialias pass over the image.
+        __shared__ unsigned int s_cmask[BIN];
+        __shared__ float s_lpart[4];
+        if (tid < BIN) s_cmask[tid] = 0u;
+        // (barrier: (z/w, id) entries, the staged colour and the cleared masks are visible.)  A pair inside the bin can only be a
+        // candidate if one of its two triangles owns a silhouette edge: most bins of a face show none at all -- the interior of the
+        // mesh -- and skip the neighbour tests of their 1024 pixels altogether (the pairs across the border are k_aa_fix's)
+        const bool bin_has_sil = __builtin_amdgcn_readfirstlane(__syncthreads_or(any_sil != 0u ? 1 : 0)) != 0;
+        const size_t bin_id = bin_lin;
+        unsigned long long *edge = sh.edges + bin_id * (4 * BIN);   // [left col | right col | bottom row | top row][32]
+        if (tid < 4 * BIN) {      // the four border lines: one entry per thread (pixels beyond the image export 0)
+            const int side = tid >> 5, i = tid & 31;
+            const int ex = side == 0 ? 0 : (side == 1 ? BIN - 1 : i), ey = side == 2 ? 0 : (side == 3 ? BIN - 1 : i);
+            edge[tid] = (bin_x0 + ex < W && bin_y0 + ey < H) ? s_z[ey * BIN + ex] : 0ull;
+        }
+        float lsum = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int zy = zy0 + 8 * k, py = bin_y0 + zy;
+            const bool inimg = px < W && py < H;
+            const int idx = zy * BIN + zx;
+            const unsigned long long me = inimg ? s_z[idx] : 0ull;
+            if (!inimg) continue;
+            const int id = (int)((unsigned int)me & 0xffffffu);
+            const float z = __uint_as_float((unsigned int)(me >> 32));
+            // pair_select keeps the FIRST pixel's triangle on a depth tie: right / upper pairs are (me, n), left / lower
+            // pairs (n, me), as for_active_edges is called; the chosen triangle's silhouette bits ride in the entries.
+            // First the cheap part for all four pairs: ids differ AND one of the two triangles owns a silhouette edge at all
+            // (interior triangles of a closed mesh own none, so most id discontinuities end here); only such pairs decide
+            // which of the two triangles is analysed.
+            bool cand = false;
+            if (bin_has_sil) {      // (uniform)
+                const bool hR = zx < BIN - 1 && px + 1 < W, hU = zy < BIN - 1 && py + 1 < H, hL = zx > 0, hD = zy > 0;
+                const unsigned long long nR = hR ? s_z[idx + 1] : me, nU = hU ? s_z[idx + BIN] : me;
+                const unsigned long long nL = hL ? s_z[idx - 1] : me, nD = hD ? s_z[idx - BIN] : me;
+                auto maybe = [&](unsigned long long n) {
+                    return ((unsigned int)n & 0xffffffu) != (unsigned int)id && ((((unsigned int)n | (unsigned int)me) >> 24) & 0xffu) != 0;
+                };
+                if (((int)maybe(nR) | (int)maybe(nU) | (int)maybe(nL) | (int)maybe(nD))) {
+                    auto pair = [&](unsigned long long n, bool me_first) {
+                        const int nid = (int)((unsigned int)n & 0xffffffu);
+                        if (nid == id) return false;
+                        const float nz = __uint_as_float((unsigned int)(n >> 32));
+                        const PairSel ps = me_first ? pair_select(id, z, nid, nz, T) : pair_select(nid, nz, id, z, T);
+                        const bool takes_n = me_first ? ps.use1 : !ps.use1;
+                        return ps.tau >= 0 && (((unsigned int)(takes_n ? n : me) >> 24) & 0xffu) != 0;
+                    };
+                    cand = (hR && pair(nR, true)) || (hU && pair(nU, true)) || (hL && pair(nL, false)) || (hD && pair(nD, false));
+                }
+            }
+            if (cand) atomicOr(&s_cmask[zy], 1u << zx);
+            const unsigned int poff = (unsigned int)(zy * W + zx);
+            const size_t off = bin_off + poff;
+            if (id > 0) {
+                const float rf = (float)ld32(sh.ref + bin_off, poff);
+                const float d0 = rf - sh.bg * sh.color_scale;
+                for (int c = 0; c < C; ++c) {
+                    const float cv = c == 0 ? col0[k] : sh.color[off * C + c];   // this thread wrote it above
+                    const float dd = rf - cv * sh.color_scale;
+                    lsum += dd * dd - d0 * d0;
+                    const float gq = (-2.0f * sh.color_scale * sh.grad_scale) * dd;
+                    if (stage) s_gaa[idx] = gq;
+                    else sh.g_aa[off * C + c] = gq;
+                }
+            } else if (stage) {
+                s_gaa[idx] = 0.0f;
+            } else {
+                for (int c = 0; c < C; ++c) sh.g_aa[off * C + c] = 0.0f;
+            }
+        }
+        lsum = wave_sum_dpp(lsum);
+        if (lane == 0) s_lpart[wave] = lsum;
+        __syncthreads();
+        if (stage) {
+            flush_plane(s_col, sh.color);
+            flush_plane(s_gaa, sh.g_aa);
+        }
+        if (tid < BIN) sh.cmask[bin_id * BIN + tid] = s_cmask[tid];
+        if (tid == 0) {
+            const double tot = (double)s_lpart[0] + (double)s_lpart[1] + (double)s_lpart[2] + (double)s_lpart[3];
+            const unsigned int slot = ((unsigned int)bxi + 31u * (unsigned int)byi + 977u * (unsigned int)b) % FPCDR_LOSS_SLOTS;
+            if (tot != 0.0) atomicAdd(sh.loss_sum + slot, tot);
+        }
+    }
+}
+
+// dense form (fpcdr_render_fwd): one workgroup per bin, grid (OX, OY, B)
+__global__ void __launch_bounds__(256) FPCDR_BINS_WPE k_bins_shade(const float4 *__restrict__ pos, const int32_t *__restrict__ tri,
+                                              int V, int T, int H, int W, const TriRec *__restrict__ recs,
+                                              const TriBox *__restrict__ boxes, const TriBox *__restrict__ cboxes,
+                                              const ImgBox *__restrict__ ibox, float4 *__restrict__ rast, ShadeArgs sh) {
+    __shared__ BinLds lds;
+    shade_bin<false, false>(lds, blockIdx.z, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, pos, tri, V, T, H, W, recs, boxes, cboxes, ibox, rast, sh);
+}
+
+// list form (fpcdr_render_loss_fwd): one workgroup per entry of the list of live bins, as k_bins_list of rasterize.hip
+template <int CS = 0, int BMODE = -1, bool MIP = false>
+__global__ void __launch_bounds__(256) FPCDR_BINS_WPE k_bins_loss_list(const int32_t *__restrict__ list, const int32_t *__restrict__ count,
+                                              int cap, int OX, int OY, fpcdr_bin_decode dc,
+                                              const float4 *__restrict__ pos, const int32_t *__restrict__ tri,
+                                              int V, int T, int H, int W, const TriRec *__restrict__ recs,
+                                              const TriBox *__restrict__ boxes, const TriBox *__restrict__ cboxes,
+                                              const ImgBox *__restrict__ ibox, float4 *__restrict__ rast, ShadeArgs sh) {
+    __shared__ BinLds lds;
+    const int item = fpcdr_list_item(*count, cap);      // (XCD x takes the x-th eighth of the entries: common.h)
+    if (item < 0) return;
+    const int lin = __builtin_amdgcn_readfirstlane(list[item]);
+    int b, byi, bxi;
+    fpcdr_decode_bin(lin, dc, b, byi, bxi);
+    shade_bin<true, true, CS, BMODE, MIP>(lds, b, bxi, byi, OX, OY, pos, tri, V, T, H, W, recs, boxes, cboxes, ibox, rast, sh);
+}
+
+// strided form: sweeps up what the hinted launch above did not reach, as k_bins_queue of rasterize.hip (inlined into the loop the body
+// spills 150+ SGPRs and runs ~25 % slower than stand-alone)
+template <bool MIP = false>
+__global__ void __launch_bounds__(256) k_bins_loss_queue(const int32_t *__restrict__ list, const int32_t *__restrict__ count,
+                                              int first, int OX, int OY, fpcdr_bin_decode dc,
+                                              const float4 *__restrict__ pos, const int32_t *__restrict__ tri,
+                                              int V, int T, int H, int W, const TriRec *__restrict__ recs,
+                                              const TriBox *__restrict__ boxes, const TriBox *__restrict__ cboxes,
+                                              const ImgBox *__restrict__ ibox, float4 *__restrict__ rast, ShadeArgs sh) {
+    __shared__ BinLds lds;
+    const int n = *count;
+    for (int item = first + blockIdx.x; item < n; item += gridDim.x) {
+        const int lin = __builtin_amdgcn_readfirstlane(list[item]);
+        int b, byi, bxi;
+        fpcdr_decode_bin(lin, dc, b, byi, bxi);
+        shade_bin<true, true, 0, -1, MIP>(lds, b, bxi, byi, OX, OY, pos, tri, V, T, H, W, recs, boxes, cboxes, ibox, rast, sh);
+        __syncthreads();     // the next bin's first LDS writes must not overtake this bin's last LDS reads
+    }
+}
+
+// per-bin window masks of the occupancy map (include/fpcdr.h, fpcdr_render_fwd_params.occ)
+__global__ void __launch_bounds__(256) k_occ_window(const uint8_t *__restrict__ raw, int B, int OY, int OX, uint16_t *__restrict__ win) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * OY * OX) return;
+    win[i] = (uint16_t)window_mask(raw, i, OY, OX);
+}
+
+// work-queue mode: image boxes + zeroed live map, raw occupancy map and queue header (grid-stride)
+__global__ void __launch_bounds__(256) k_init_queue(ImgBox *ibox, int B, uint32_t *__restrict__ live_words, long long n_live_words,
+                                                    uint32_t *__restrict__ occ_words, long long n_occ_words, int32_t *__restrict__ hdr,
+                                                    int32_t *__restrict__ hdr_bwd, int32_t *__restrict__ bin_cnt = nullptr, long long n_bins = 0) {
+    const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    if (i0 < B) ibox[i0] = {0x7fffffff, 0x7fffffff, -1, -1, 0, 0, 0, 0};
+    if (i0 < 16) { hdr[i0] = 0; hdr_bwd[i0] = 0; }
+    for (long long i = i0; i < n_live_words; i += stride) live_words[i] = 0u;
+    for (long long i = i0; i < n_occ_words; i += stride) occ_words[i] = 0u;
+    if (bin_cnt)
+        for (long long i = i0; i < n_bins; i += stride) bin_cnt[i] = 0;      // per-bin triangle counts (k_setup<true>)
+}
+
+// ---------------------------------------------------------------------------------------------
+// Fused backward of texture('linear') -> interpolate -> rasterize (reference fit.py:158,157,151) for the render
+// path: reads dL/d colour (4C B/px) and rast (16 B/px), writes nothing dense.  A covered pixel with a non-zero
+// gradient re-derives its texture coordinate, scatters into grad_tex (4C atomics), chains d colour / d uv through
+// the barycentrics to the three clip-space vertices and scatters into grad_pos (pre-reduced per wave by vertex).
+__global__ void __launch_bounds__(256) k_render_bwd(const float4 *__restrict__ pos, const int32_t *__restrict__ tri,
+                                                    const float2 *__restrict__ uv, const int32_t *__restrict__ uv_tri,
+                                                    const float *__restrict__ tex, const float4 *__restrict__ rast,
+                                                    const float *__restrict__ dy, int V, int T, int H, int W, int Ht, int Wt,
+                                                    int C, int boundary, float *__restrict__ grad_pos,
+                                                    float *__restrict__ grad_tex, const float2 *__restrict__ tri_uv) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int px = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+    const int py = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    const int b = blockIdx.z;
+    int key0 = -1, key1 = -1, key2 = -1;
+    float g0[3] = {0, 0, 0}, g1[3] = {0, 0, 0}, g2[3] = {0, 0, 0};
+    if (px < W && py < H) {
+        const size_t off = ((size_t)b * H + py) * W + px;
+        const float *g = dy + off * C;
+        bool any = false;
+        for (int c = 0; c < C; ++c) any |= (g[c] != 0.0f);
+        if (any) {
+            const float4 r = rast[off];
+            int t = (int)r.w - 1;
+            if (t >= T) t = -1;
+            // texture backward; an empty pixel sampled uv = (0,0) in the forward pass and scatters there
+            float2 q0 = make_float2(0.f, 0.f), q1 = q0, q2 = q0;
+            float tu = 0.0f, tv = 0.0f;
+            if (t >= 0) {
+                if (tri_uv) { q0 = tri_uv[3 * t]; q1 = tri_uv[3 * t + 1]; q2 = tri_uv[3 * t + 2]; }
+                else { q0 = uv[uv_tri[3 * t]]; q1 = uv[uv_tri[3 * t + 1]]; q2 = uv[uv_tri[3 * t + 2]]; }
+                const float w = 1.0f - r.x - r.y;
+                tu = r.x * q0.x + r.y * q1.x + w * q2.x;
+                tv = r.x * q0.y + r.y * q1.y + w * q2.y;
+            }
+            const Taps tp = make_taps(tu, tv, Ht, Wt, C, boundary);
+            const float w00 = (1.0f - tp.fx) * (1.0f - tp.fy), w10 = tp.fx * (1.0f - tp.fy);
+            const float w01 = (1.0f - tp.fx) * tp.fy, w11 = tp.fx * tp.fy;
+            float gfx = 0.f, gfy = 0.f;
+            for (int c = 0; c < C; ++c) {
+                const float gc = g[c];
+                float t00, t10, t01, t11;
+                load_taps(tex, tp, c, C, t00, t10, t01, t11);
+                mask_taps(tp, t00, t10, t01, t11);
+                gfx += gc * ((t10 - t00) * (1.0f - tp.fy) + (t11 - t01) * tp.fy);
+                gfy += gc * ((t01 + (t11 - t01) * tp.fx) - (t00 + (t10 - t00) * tp.fx));
+                if (grad_tex && gc != 0.0f) {      // (boundary mode 'zero': the padding receives no gradient)
+                    if (tp.valid & 1u) atomicAdd(grad_tex + tp.i00 + c, gc * w00);
+                    if (tp.valid & 2u) atomicAdd(grad_tex + tp.i10 + c, gc * w10);
+                    if (tp.valid & 4u) atomicAdd(grad_tex + tp.i01 + c, gc * w01);
+                    if (tp.valid & 8u) atomicAdd(grad_tex + tp.i11 + c, gc * w11);
+                }
+            }
+            if (t >= 0 && grad_pos) {
+                const float mu = (boundary == FPCDR_BOUNDARY_CLAMP && !(tu >= 0.0f && tu <= 1.0f)) ? 0.0f : 1.0f;
+                const float mv = (boundary == FPCDR_BOUNDARY_CLAMP && !(tv >= 0.0f && tv <= 1.0f)) ? 0.0f : 1.0f;
+                const float gtu = gfx * (float)Wt * mu, gtv = gfy * (float)Ht * mv;
+                // interpolate backward: d uv / d (u, v)
+                const float gu = gtu * (q0.x - q2.x) + gtv * (q0.y - q2.y);
+                const float gv = gtu * (q1.x - q2.x) + gtv * (q1.y - q2.y);
+                if (gu != 0.0f || gv != 0.0f) {
+                    const int i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
+                    const float4 *p = pos + (size_t)b * V;
+                    const float fx = (2.0f * (float)px + 1.0f) / (float)W - 1.0f;
+                    const float fy = (2.0f * (float)py + 1.0f) / (float)H - 1.0f;
+                    shade_pixel_bwd<false>(p[i0], p[i1], p[i2], fx, fy, 2.0f / (float)W, 2.0f / (float)H,
+                                           make_float4(gu, gv, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), g0, g1, g2);
+                    key0 = i0; key1 = i1; key2 = i2;
+                }
+            }
+        }
+    }
+    if (!grad_pos || __ballot(key0 >= 0) == 0ull) return;
+    float *gp = grad_pos + (size_t)b * V * 4;
+    {
+        float *const d[3] = {gp + 4 * (size_t)max(key0, 0), gp + 4 * (size_t)max(key0, 0) + 1, gp + 4 * (size_t)max(key0, 0) + 3};
+        wave_group_atomic_add<3>(key0, d, g0);
+    }
+    {
+        float *const d[3] = {gp + 4 * (size_t)max(key1, 0), gp + 4 * (size_t)max(key1, 0) + 1, gp + 4 * (size_t)max(key1, 0) + 3};
+        wave_group_atomic_add<3>(key1, d, g1);
+    }
+    {
+        float *const d[3] = {gp + 4 * (size_t)max(key2, 0), gp + 4 * (size_t)max(key2, 0) + 1, gp + 4 * (size_t)max(key2, 0) + 3};
+        wave_group_atomic_add<3>(key2, d, g2);
+    }
+}
+
 }  // namespace
 
-// ---- a piece of fpcdr_render_loss_fwd (rasterize.hip) that lives in this file; not part of the C ABI ----
-int fpcdr_launch_aa_fix(const fpcdr_aa_loss_fwd_params *p, const uint32_t *cmask, const unsigned long long *edges,
-                        const int32_t *fix_list, const int32_t *fix_count, int nbins, hipStream_t st) {
+// ---- the last step of fpcdr_render_loss_fwd (below): the antialias fix of the candidate pixels ----
+static int fpcdr_launch_aa_fix(const fpcdr_aa_loss_fwd_params *p, const uint32_t *cmask, const unsigned long long *edges,
+                               const int32_t *fix_list, const int32_t *fix_count, int nbins, hipStream_t st) {
     const int cap = (p->cap_fix > 0 && p->cap_fix < nbins) ? p->cap_fix : nbins;
     const fpcdr_bin_decode dc = fpcdr_make_bin_decode(FPCDR_OCC_DIM(p->W), FPCDR_OCC_DIM(p->H));
 #define ARGS                                                                                                                   \
@@ -1093,4 +1544,137 @@ extern "C" int fpcdr_render_aa_bwd(const fpcdr_render_aa_bwd_params *p, void *st
 #undef LAUNCH
     FPCDR_CHECK_LAUNCH();
     return FPCDR_OK;
+}
+
+// ---- the forward entry points: set-up, bin lists and raster phase of bin_raster.h, read out by shade_bin ----
+extern "C" int fpcdr_render_fwd(const fpcdr_render_fwd_params *p, void *stream) {
+    FPCDR_REQUIRE(p != nullptr, "null params");
+    FPCDR_REQUIRE(p->pos && p->tri && p->scratch && p->rast && p->uv && p->uv_tri && p->tex && p->color, "null pointer");
+    FPCDR_REQUIRE(p->B > 0 && p->V > 0 && p->T > 0 && p->H > 0 && p->W > 0 && p->Ht > 0 && p->Wt > 0 && p->C > 0,
+                  "sizes must be positive");
+    FPCDR_REQUIRE(p->H <= 32767 && p->W <= 32767 && p->B <= 65535, "resolution / batch too large");
+    FPCDR_REQUIRE(p->T < (1 << 24), "more than 2^24 triangles (rast stores triangle index + 1 as a float)");
+    FPCDR_REQUIRE(p->boundary_mode == FPCDR_BOUNDARY_WRAP || p->boundary_mode == FPCDR_BOUNDARY_CLAMP || p->boundary_mode == FPCDR_BOUNDARY_ZERO,
+                  "bad boundary mode");
+    FPCDR_REQUIRE((long long)p->Ht * p->Wt * p->C < (1ll << 30), "texture too large (the fused paths take < 2^30 texel values)");
+    FPCDR_REQUIRE(!p->mip, "the mip-mapped lookup is part of fpcdr_render_loss_fwd only");
+    hipStream_t st = (hipStream_t)stream;
+    const RasterScratch rs = raster_scratch(p->scratch, p->B, p->T);
+    hipLaunchKernelGGL(k_init_ibox, dim3(fpcdr_cdiv(p->B, 256)), dim3(256), 0, st, rs.ibox, p->B);
+    launch_setup(st, p->pos, p->tri, p->B, p->V, p->T, p->H, p->W, rs, nullptr, nullptr);
+    dim3 grid(fpcdr_cdiv(p->W, BIN), fpcdr_cdiv(p->H, BIN), p->B);
+    ShadeArgs sh = {(const float2 *)p->uv, p->uv_tri, p->tex, p->color, p->Ht, p->Wt, p->C, p->boundary_mode,
+                    nullptr, p->empty_color, (const float2 *)p->tri_uv};
+    const size_t nbins = (size_t)p->B * grid.y * grid.x;
+    if (p->occ) {
+        FPCDR_REQUIRE(p->empty_color != nullptr, "sparse mode needs empty_color");
+        sh.occ = (uint8_t *)p->occ + fpcdr_queue_layout_of(p->B, p->H, p->W).occ_raw;   // raw byte map behind the window masks
+    }
+    hipLaunchKernelGGL(k_bins_shade, grid, dim3(256), 0, st, (const float4 *)p->pos, p->tri, p->V, p->T, p->H, p->W,
+                       rs.recs, rs.boxes, rs.cboxes, rs.ibox, (float4 *)p->rast, sh);
+    if (p->occ)
+        hipLaunchKernelGGL(k_occ_window, dim3(fpcdr_cdiv((long long)nbins, 256)), dim3(256), 0, st, sh.occ, p->B, (int)grid.y,
+                           (int)grid.x, p->occ);
+    FPCDR_CHECK_LAUNCH();
+    return FPCDR_OK;
+}
+
+extern "C" int fpcdr_render_bwd(const fpcdr_render_bwd_params *p, void *stream) {
+    FPCDR_REQUIRE(p != nullptr, "null params");
+    FPCDR_REQUIRE(p->pos && p->tri && p->uv && p->uv_tri && p->tex && p->rast && p->dy, "null pointer");
+    FPCDR_REQUIRE(p->grad_pos || p->grad_tex, "nothing to compute");
+    FPCDR_REQUIRE(p->B > 0 && p->V > 0 && p->T > 0 && p->H > 0 && p->W > 0 && p->Ht > 0 && p->Wt > 0 && p->C > 0,
+                  "sizes must be positive");
+    FPCDR_REQUIRE(p->B <= 65535, "more than 65535 images per call");
+    dim3 grid(fpcdr_cdiv(p->W, 16), fpcdr_cdiv(p->H, 16), p->B);
+    hipLaunchKernelGGL(k_render_bwd, grid, dim3(256), 0, (hipStream_t)stream, (const float4 *)p->pos, p->tri,
+                       (const float2 *)p->uv, p->uv_tri, p->tex, (const float4 *)p->rast, p->dy, p->V, p->T, p->H, p->W, p->Ht,
+                       p->Wt, p->C, p->boundary_mode, p->grad_pos, p->grad_tex, (const float2 *)p->tri_uv);
+    FPCDR_CHECK_LAUNCH();
+    return FPCDR_OK;
+}
+
+extern "C" int fpcdr_render_loss_fwd(const fpcdr_render_fwd_params *p, const fpcdr_aa_loss_fwd_params *l, uint32_t *cmask,
+                                     void *stream) {
+    FPCDR_REQUIRE(p != nullptr && l != nullptr && cmask != nullptr, "null params");
+    FPCDR_REQUIRE(p->pos && p->tri && p->scratch && p->uv && p->uv_tri && p->tex && p->rast && p->color, "null pointer");
+    FPCDR_REQUIRE(p->occ && p->empty_color, "fpcdr_render_loss_fwd works in sparse mode only (occ, empty_color)");
+    FPCDR_REQUIRE(((size_t)p->occ & 3) == 0 && ((size_t)cmask & 7) == 0, "occ must be 4-byte and cmask 8-byte aligned");
+    FPCDR_REQUIRE(l->adj && l->ref && l->sil && l->flags && l->grad_aa && l->loss_sum, "null pointer");
+    FPCDR_REQUIRE(l->color == p->color && l->rast == p->rast && l->pos == p->pos && l->tri == p->tri && l->occ == p->occ &&
+                      l->empty_color == p->empty_color && l->B == p->B && l->H == p->H && l->W == p->W && l->C == p->C &&
+                      l->V == p->V && l->T == p->T,
+                  "the two parameter blocks describe different batches");
+    FPCDR_REQUIRE(p->B > 0 && p->V > 0 && p->T > 0 && p->H > 0 && p->W > 0 && p->Vt > 0 && p->Ht > 0 && p->Wt > 0 && p->C > 0,
+                  "sizes must be positive");
+    FPCDR_REQUIRE(p->C == 1 || p->C == 3 || p->C == 4, "fused objective supports C = 1, 3, 4");
+    FPCDR_REQUIRE(p->H <= 32767 && p->W <= 32767 && p->B <= 65535, "resolution / batch too large");
+    FPCDR_REQUIRE(p->T < (1 << 24), "more than 2^24 triangles");
+    FPCDR_REQUIRE(p->boundary_mode == FPCDR_BOUNDARY_WRAP || p->boundary_mode == FPCDR_BOUNDARY_CLAMP || p->boundary_mode == FPCDR_BOUNDARY_ZERO,
+                  "bad boundary mode");
+    FPCDR_REQUIRE((long long)p->Ht * p->Wt * p->C < (1ll << 30), "texture too large (the fused paths take < 2^30 texel values)");
+    if (p->mip) {
+        FPCDR_REQUIRE(p->n_levels >= 0 && p->n_levels <= FPCDR_MAX_MIP, "bad n_levels");
+        for (int lvl = 1; lvl <= p->n_levels; ++lvl) {
+            FPCDR_REQUIRE(p->tex_mip[lvl - 1] != nullptr, "missing mip level");
+            FPCDR_REQUIRE(!((p->Ht >> (lvl - 1)) & 1) && !((p->Wt >> (lvl - 1)) & 1), "mip levels need even sizes");
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // (the silhouette kernel also zeroes the call's flag planes: the caller need not)
+    int rc = fpcdr_launch_sil(p->pos, p->tri, l->adj, p->B, p->V, p->T, p->H, p->W, l->sil, l->flags,
+                              (size_t)2 * p->B * p->H * FPCDR_AA_ROW_WORDS(p->W) * sizeof(uint64_t), st);
+    if (rc) return rc;
+    const RasterScratch rs = raster_scratch(p->scratch, p->B, p->T);
+    const int OX = fpcdr_cdiv(p->W, BIN), OY = fpcdr_cdiv(p->H, BIN);
+    const size_t nbins = (size_t)p->B * OY * OX;
+    FPCDR_REQUIRE(nbins < 0x7ffffff0ULL, "too many bins for one call");      // (list launches are rounded up to a multiple of 8 workgroups)
+    const fpcdr_queue_layout q = fpcdr_queue_layout_of(p->B, p->H, p->W);
+    char *cm = (char *)cmask, *oc = (char *)p->occ;
+    int32_t *hdr = (int32_t *)(cm + q.cm_hdr), *bin_list = (int32_t *)(cm + q.cm_bin_list), *fix_list = (int32_t *)(cm + q.cm_fix_list);
+    uint8_t *live = (uint8_t *)(cm + q.cm_live);
+    int32_t *hdr_bwd = (int32_t *)(oc + q.occ_hdr), *bwd_list = (int32_t *)(oc + q.occ_bwd_list);
+    uint8_t *occ_raw = (uint8_t *)(oc + q.occ_raw);
+    // header in occ (survives the call; include/fpcdr.h FPCDR_OCC_COUNTS): [0] backward bins, [2] live bins, [3] antialias-fix bins
+    hipLaunchKernelGGL(k_init_queue, dim3(256), dim3(256), 0, st, rs.ibox, p->B, (uint32_t *)live, (long long)(align_up(nbins, 4) / 4),
+                       (uint32_t *)oc, (long long)(q.occ_hdr / 4), hdr, hdr_bwd);
+    launch_setup(st, p->pos, p->tri, p->B, p->V, p->T, p->H, p->W, rs, live, nullptr);
+    int32_t *n_bins = hdr_bwd + 2, *n_fix = hdr_bwd + 3;     // all three counts live in the occ header, where the caller finds them
+    int32_t *blk = (int32_t *)(cm + q.cm_blk);          // [2][nblk] per-block counts, then offsets
+    launch_list_round<0>(st, false, live, nbins, OY, OX, blk, bin_list, nullptr, n_bins, nullptr, nullptr, p->tex, p->Ht, p->Wt, p->C,
+                         p->boundary_mode, p->empty_color);
+    ShadeArgs sh = {(const float2 *)p->uv, p->uv_tri, p->tex, p->color, p->Ht, p->Wt, p->C, p->boundary_mode,
+                    occ_raw, p->empty_color, (const float2 *)p->tri_uv,
+                    l->sil, l->ref, l->grad_aa, cmask, (unsigned long long *)(cm + q.cm_edges), l->loss_sum, l->bg, l->color_scale,
+                    l->grad_scale};
+    if (p->mip) {
+        for (int lvl = 0; lvl < FPCDR_MAX_MIP; ++lvl) sh.mip[lvl] = lvl < p->n_levels ? p->tex_mip[lvl] : nullptr;
+        sh.n_levels = p->n_levels;
+    }
+    // hinted single-shot launch + strided sweep of the rest (l->cap_bins <= 0: no hint, one workgroup per possible entry)
+    const fpcdr_bin_decode dc = fpcdr_make_bin_decode(OX, OY);
+    const int cap_bins = (l->cap_bins > 0 && (size_t)l->cap_bins < nbins) ? l->cap_bins : (int)nbins;
+    if (p->mip && p->C != 1)
+        hipLaunchKernelGGL((k_bins_loss_list<0, -1, true>), dim3(fpcdr_list_grid(cap_bins)), dim3(256), 0, st, bin_list, n_bins, cap_bins, OX, OY, dc,
+                       (const float4 *)p->pos, p->tri, p->V, p->T, p->H, p->W, rs.recs, rs.boxes, rs.cboxes, rs.ibox, (float4 *)p->rast, sh);
+    else if (p->mip)
+        hipLaunchKernelGGL((k_bins_loss_list<1, -1, true>), dim3(fpcdr_list_grid(cap_bins)), dim3(256), 0, st, bin_list, n_bins, cap_bins, OX, OY, dc,
+                       (const float4 *)p->pos, p->tri, p->V, p->T, p->H, p->W, rs.recs, rs.boxes, rs.cboxes, rs.ibox, (float4 *)p->rast, sh);
+    else if (p->C == 1 && p->boundary_mode == FPCDR_BOUNDARY_WRAP)     // the reference's case, with both as compile-time constants
+        hipLaunchKernelGGL((k_bins_loss_list<1, FPCDR_BOUNDARY_WRAP>), dim3(fpcdr_list_grid(cap_bins)), dim3(256), 0, st, bin_list, n_bins, cap_bins, OX, OY, dc,
+                       (const float4 *)p->pos, p->tri, p->V, p->T, p->H, p->W, rs.recs, rs.boxes, rs.cboxes, rs.ibox, (float4 *)p->rast, sh);
+    else
+        hipLaunchKernelGGL(k_bins_loss_list<>, dim3(fpcdr_list_grid(cap_bins)), dim3(256), 0, st, bin_list, n_bins, cap_bins, OX, OY, dc,
+                       (const float4 *)p->pos, p->tri, p->V, p->T, p->H, p->W, rs.recs, rs.boxes, rs.cboxes, rs.ibox, (float4 *)p->rast, sh);
+    if ((size_t)cap_bins < nbins) {
+        if (p->mip)
+            hipLaunchKernelGGL(k_bins_loss_queue<true>, dim3(FPCDR_SWEEP_WGS), dim3(256), 0, st, bin_list, n_bins, cap_bins, OX, OY, dc,
+                               (const float4 *)p->pos, p->tri, p->V, p->T, p->H, p->W, rs.recs, rs.boxes, rs.cboxes, rs.ibox, (float4 *)p->rast, sh);
+        else
+            hipLaunchKernelGGL(k_bins_loss_queue<false>, dim3(FPCDR_SWEEP_WGS), dim3(256), 0, st, bin_list, n_bins, cap_bins, OX, OY, dc,
+                               (const float4 *)p->pos, p->tri, p->V, p->T, p->H, p->W, rs.recs, rs.boxes, rs.cboxes, rs.ibox, (float4 *)p->rast, sh);
+    }
+    launch_list_round<1>(st, false, occ_raw, nbins, OY, OX, blk, fix_list, bwd_list, n_fix, hdr_bwd, p->occ);
+    FPCDR_CHECK_LAUNCH();
+    return fpcdr_launch_aa_fix(l, cmask, (const unsigned long long *)(cm + q.cm_edges), fix_list, n_fix, (int)nbins, st);
 }

@@ -6,7 +6,7 @@
 // instructions (profiles/r04_backward_ablation.txt).  The objective is a scalar, so its gradient is known the moment a pixel's loss
 // term is: here the thread that shades a pixel also chains its gradient back while barycentrics, taps, texels and vertices are live.
 //
-//   k_bins_list<IDS> (rasterize.hip)   coverage + depth only; leaves (triangle + 1) | silhouette bits << 24 per pixel, 4 KB per bin
+//   k_bins_list (rasterize.hip)        coverage + depth only; leaves (triangle + 1) | silhouette bits << 24 per pixel, 4 KB per bin
 //   k_shade                            one workgroup per occupied bin: shade, texture, background + squared error, texture /
 //                                      interpolate / rasterize backward of the un-antialiased gradient into per-bin LDS accumulators
 //                                      (vertex table + texel window, doubles), one flush.  Pixels with a pixel pair of different ids

@@ -1,4 +1,4 @@
-// Bilinear texture sampling shared by texture.hip and the fused render kernels (rasterize.hip).
+// Bilinear texture sampling shared by texture.hip and the fused render kernels (fused.hip, objective.hip).
 #pragma once
 #include "common.h"
 

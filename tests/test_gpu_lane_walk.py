@@ -1,8 +1,9 @@
-"""The lane walk of the bin rasteriser (rasterize.hip, bins_body: one lane per small triangle, winners folded into the bin's LDS depth
+"""The lane walk of the bin rasteriser (bin_raster.h, bin_raster: one lane per small triangle, winners folded into the bin's LDS depth
 buffer as 64-bit keys).  Its inner trip keeps a running float for the depth plane's x offset, a running LDS address that is also the
 loop test, and a two-instruction depth key; this file pins what those may not change.  Every comparison is exact: ids against the CPU
-oracle's rasteriser, through fpcdr_rasterize_fwd (k_bins) and through the id planes of fpcdr_objective_fwd (the list kernels; with
-and without per-bin triangle lists).
+oracle's rasteriser, through fpcdr_rasterize_fwd (k_bins), through the id planes of fpcdr_objective_fwd (the list kernels; with
+and without per-bin triangle lists) and through fpcdr_render_fwd of the two-call library (the same raster phase under that library's own
+read-out), whose rast must also equal fpcdr_rasterize_fwd's bit for bit.
 
 Scenes are hand-built in pixel coordinates (w = 1 or 2, so that z / w is the z written down) with a random soup mixed in:
   depth keys   planes at z = w and z = -w (kept), one ulp beyond each (dropped), +0.0 against -0.0 under both index orders, several
@@ -57,12 +58,23 @@ def _shown(ids, t):
     return int((ids == t + 1).sum())
 
 
-# ------------------------------------------------------------------------------------------------ the two GPU paths
+# ------------------------------------------------------------------------------------------------ the three GPU paths
 
 def _gpu_rast(pos, tri, res):
     import fpc_diffrend_amd.ops as dr
     ctx = dr.RasterizeGLContext(device='cuda')
     rast, _ = dr.rasterize(ctx, pos.cuda(), tri.cuda(), res)
+    return rast.cpu()
+
+
+def _gpu_rast_twocall(pos, tri, res):
+    """rast of ops.render_textured (fpcdr_render_fwd, dense form): a 4 x 4 one-channel texture, uv_tri = tri."""
+    import fpc_diffrend_amd.ops as dr
+    ctx = dr.RasterizeGLContext(device='cuda')
+    g = torch.Generator().manual_seed(3)
+    uv = torch.rand(pos.shape[1], 2, generator=g).cuda()
+    tex = torch.rand(4, 4, 1, generator=g).cuda()
+    _, rast = dr.render_textured(ctx, pos.cuda(), tri.cuda(), uv, tri.cuda(), tex, res)
     return rast.cpu()
 
 
@@ -72,6 +84,10 @@ def _check_exact(pos, tri, res, ids_ref):
     assert torch.equal(rast[..., 3].to(torch.int32), ids_ref), "fpcdr_rasterize_fwd: ids differ from the oracle"
     for bin_lists in (True, False):
         assert torch.equal(objective_ids(pos, tri, res, bin_lists), ids_ref), f"fpcdr_objective_fwd (bin lists: {bin_lists}): ids differ from the oracle"
+    rast_tc = _gpu_rast_twocall(pos, tri, res)
+    assert torch.equal(rast_tc[..., 3].to(torch.int32), ids_ref), "fpcdr_render_fwd: ids differ from the oracle"
+    assert torch.equal(rast_tc[..., :3].contiguous().view(torch.int32), rast[..., :3].contiguous().view(torch.int32)), \
+        "fpcdr_render_fwd: rast[..., :3] differs from fpcdr_rasterize_fwd's"
     return rast
 
 
