@@ -124,6 +124,13 @@ class BlurLoss(ctypes.Structure):
                 ("taps", ctypes.c_float * 64), ("tmp", _p), ("blurred", _p), ("loss_sum", _p), ("grad_color", _p)]
 
 
+class NormLoss(ctypes.Structure):
+    _fields_ = [("color", _p), ("rast", _p), ("ref", _p), ("B", _i), ("H", _i), ("W", _i), ("C", _i),
+                ("bg", ctypes.c_float), ("color_scale", ctypes.c_float), ("grad_scale", ctypes.c_float), ("eps", ctypes.c_float),
+                ("radius", _i), ("taps", ctypes.c_float * 64), ("tmp", _p), ("stats", _p), ("d", _p), ("pq", _p), ("p", _p),
+                ("loss_sum", _p), ("grad_color", _p)]
+
+
 ADAM_MAX_TENSORS = 16     # FPCDR_ADAM_MAX_TENSORS
 
 
@@ -186,6 +193,8 @@ SYMBOLS = {
     "fpcdr_pixel_loss": (_int, [ctypes.POINTER(PixelLoss), _p]),
     "fpcdr_blur_loss_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "fpcdr_blur_loss": (_int, [ctypes.POINTER(BlurLoss), _p]),
+    "fpcdr_norm_loss_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "fpcdr_norm_loss": (_int, [ctypes.POINTER(NormLoss), _p]),
     "fpcdr_adam_step": (_int, [ctypes.POINTER(AdamParams), _p]),
     "fpcdr_undistort_u8": (_int, [_p, _p, _p, ctypes.c_int64, _i, _i, _i, _i, _i, _p]),
     "fpcdr_compare_u8": (_int, [_p, _int, ctypes.c_float, _p, _p, _p, ctypes.c_int64, _i, _i, _i, _i, _i, _i, _p]),

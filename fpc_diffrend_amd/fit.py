@@ -282,6 +282,14 @@ def pixel_loss_blurred(colour, rast_out, ref_u8, taps, n_total=None):
     return acc, grad
 
 
+def pixel_loss_normalised(colour, rast_out, ref_u8, taps, eps, n_total=None):
+    """pixel_loss_fused with render and capture each normalised by its own Gaussian window before they are compared (DESIGN.md 3,
+    "Normalised loss rule"; fpcdr_norm_loss): returns (sum d^2 [1] f64 tensor, d mean / d colour [B,H,W,C]) with mean over n_total elements."""
+    n_total = n_total or colour.numel()
+    acc, grad, _ = dr.norm_loss_call(colour, rast_out, ref_u8, taps, 1.0 / n_total, eps, True, BACKGROUND)
+    return acc, grad
+
+
 class _mvp_func(torch.autograd.Function):
     """Model-view-projection matrices of a minibatch in one kernel each way (fpcdr_mvp_fwd / _bwd)."""
 
@@ -724,6 +732,17 @@ class FitConfig:
     blur_kernel_size: int = 31      # odd, 3 .. 63 (the reference's GaussianBlur(kernel_size=(31, 31)), fit.py:506)
     blur_iters: int = 0             # 0 = every iteration is blurred; n = iterations i < n, then the run continues on the path the other
                                     # flags select (the one-pass objective by default)
+    norm_sigma: float = 0.0         # > 0: the pixel term is the LOCALLY NORMALISED loss (fit.pixel_loss_normalised; DESIGN.md 3, "Normalised
+                                    # loss rule") on the operator path: render and capture are each reduced by the mean and divided by the
+                                    # deviation of their own Gaussian window of this sigma, so a camera's exposure, gain and black level drop
+                                    # out.  The logged loss is then DIMENSIONLESS (a mean of squared differences of normalised values, not of
+                                    # grey levels).  Within a window the loss sees neither the absolute level nor the contrast of the texture:
+                                    # use it with a baked or supplied start texture (init_texture='bake'), not from noise.  0 = off: nothing
+                                    # changes.  Not together with blur_sigma > 0 (ValueError)
+    norm_kernel_size: int = 31      # odd, 3 .. 63
+    norm_eps: float = 2.0           # in grey levels, > 0: added (squared) to the window's variance, so flat regions stay finite and quiet
+    norm_iters: int = 0             # 0 = every iteration is normalised; n = iterations i < n, then the run continues on the path the other
+                                    # flags select
     pyramid: Sequence[Tuple[int, int]] = ()   # coarse-to-fine on a resolution pyramid of the captures: entries (factor, iterations) in order,
                                     # e.g. ((8, 300), (4, 300), (2, 400)) = iterations 0-299 at 1/8 of the size, 300-599 at 1/4, 600-999 at
                                     # 1/2, everything after at full size (a factor of 1 is allowed in an entry).  A level renders at
@@ -737,6 +756,10 @@ class FitConfig:
     log_interval: int = 0           # every n steps one JSON line {it, loss, lr, frames_per_s} (reference print, fit.py:621-623)
     reg_log_interval: int = 500     # every n steps the regulariser breakdown MEL / LAP / MNC (reference fit.py:597-601)
     log_path: Optional[str] = None  # JSON-lines file (appended); None with log_interval > 0 = stdout
+
+    def __post_init__(self):
+        if self.blur_sigma > 0 and self.norm_sigma > 0:
+            raise ValueError("FitConfig.blur_sigma > 0 and norm_sigma > 0 exclude each other: an iteration has one pixel term")
 
 
 def setup_dataset(blendshapes, n_frames, device):
@@ -837,6 +860,15 @@ class Fitter:
             dr.gaussian_taps(cfg.blur_kernel_size, cfg.blur_sigma)                       # (raises for a bad kernel size or sigma)
             if cfg.blur_sigma_end is not None:
                 dr.gaussian_taps(cfg.blur_kernel_size, cfg.blur_sigma_end)
+        if cfg.norm_sigma > 0:
+            if not cfg.fused_loss:
+                raise ValueError("FitConfig.norm_sigma > 0 needs fused_loss=True: the normalised loss replaces pixel_loss_fused")
+            if cfg.hip_graph:
+                raise ValueError("FitConfig.norm_sigma > 0 cannot be combined with hip_graph: the switch back to the path the other "
+                                 "flags select changes the step from one iteration to the next")
+            dr.gaussian_taps(cfg.norm_kernel_size, cfg.norm_sigma)                       # (raises for a bad kernel size or sigma)
+            if not (float(cfg.norm_eps) > 0.0 and float(cfg.norm_eps) < float('inf')):
+                raise ValueError(f"FitConfig.norm_eps must be finite and positive (got {cfg.norm_eps})")
         if cfg.hip_graph == 'auto':
             self.use_graph = self.auto_graph((cfg.frames_per_step or (self.frame_hi - self.frame_lo)) * (cfg.views_per_step or len(self.cam_idxs)),
                                              self.resolution)
@@ -1229,6 +1261,15 @@ class Fitter:
             sigma = sigma * (float(cfg.blur_sigma_end) / sigma) ** (min(i, n - 1) / max(n - 1, 1))
         return dr.gaussian_taps(cfg.blur_kernel_size, sigma)
 
+    def norm_taps(self, i=None):
+        """The taps of the normalised pixel loss at iteration i (default: the current one), or None when that iteration is not
+        normalised.  A function of the iteration alone, so a resumed run continues on the right side of the switch."""
+        cfg = self.cfg
+        i = self.iteration if i is None else i
+        if not cfg.norm_sigma > 0 or (cfg.norm_iters and i >= cfg.norm_iters):
+            return None
+        return dr.gaussian_taps(cfg.norm_kernel_size, float(cfg.norm_sigma))
+
     def loss_and_backward(self, frame_ids, view_ids=None, validate=True):
         """Forward + backward of fit.py:556-611 for a batch of frames x cameras (view_ids: see mvp).  Returns the loss (tensor).
         validate: check a caller's index tensors on the host first (check_indices); step() passes False for its own draws."""
@@ -1249,6 +1290,9 @@ class Fitter:
         blur_taps = self.blur_taps(i) if cfg.blur_sigma > 0 else None
         if blur_taps is not None:
             one_shot = False           # the blurred loss needs the image in memory: the operator path
+        norm_taps = self.norm_taps(i) if cfg.norm_sigma > 0 else None
+        if norm_taps is not None:
+            one_shot = False           # so does the normalised loss
         # one flat buffer for the small accumulators of this step's backward kernels, zero-filled by the objective's first kernel; the
         # pool around it goes to the functions whose backward takes views of it
         zero_buf, pool = None, None
@@ -1329,6 +1373,8 @@ class Fitter:
         elif cfg.fused_loss:
             if blur_taps is not None:
                 sum_sq, g_colour = pixel_loss_blurred(colour, rast_out, ref, blur_taps, n_total)
+            elif norm_taps is not None:
+                sum_sq, g_colour = pixel_loss_normalised(colour, rast_out, ref, norm_taps, cfg.norm_eps, n_total)
             else:
                 sum_sq, g_colour = pixel_loss_fused(colour, rast_out, ref, n_total)
             self._backward(colour, g_colour, reg, lap)

@@ -30,7 +30,7 @@ from . import _lib
 
 __all__ = ['RasterizeGLContext', 'RasterizeCudaContext', 'RasterizeHipContext', 'rasterize', 'interpolate', 'texture',
            'texture_construct_mip', 'antialias', 'antialias_construct_topology_hash', 'render_textured', 'pixel_objective', 'undistort_images', 'compare_images',
-           'gaussian_taps', 'blurred_pixel_loss', 'bake_accumulate', 'bake_resolve', 'downsample_images']
+           'gaussian_taps', 'blurred_pixel_loss', 'normalised_pixel_loss', 'bake_accumulate', 'bake_resolve', 'downsample_images']
 
 
 def _stream():
@@ -711,6 +711,84 @@ def blurred_pixel_loss(colour, rast, ref_u8, sigma=None, kernel_size=31, n_total
             raise ValueError("blurred_pixel_loss needs sigma (or taps)")
         taps = gaussian_taps(kernel_size, sigma)
     return _blurred_pixel_loss_func.apply(colour, rast, ref_u8, taps, float(n_total or colour.numel()), background)
+
+
+def _norm_check(taps, eps, H, W):
+    """The taps as a CPU float32 tensor [k] and eps as a float, or ValueError: the argument checks of the normalised loss that need no GPU
+    (they run before the tensors are looked at)."""
+    taps = torch.as_tensor(taps, dtype=torch.float32).detach().cpu().reshape(-1)
+    k = taps.numel()
+    if k % 2 == 0 or not 3 <= k <= 63:
+        raise ValueError(f"the number of taps must be odd and in 3 .. 63 (got {k})")
+    if bool((taps < 0).any()) or not bool(torch.isfinite(taps).all()):
+        raise ValueError("the taps of the normalised loss must be finite and non-negative (m >= mu^2 rests on it)")
+    if (k - 1) // 2 >= min(H, W):
+        raise ValueError(f"reflected borders need (kernel_size - 1) / 2 < min(H, W) (got kernel size {k} for {H} x {W})")
+    eps = float(eps)
+    if not (eps > 0.0 and eps < float('inf')):
+        raise ValueError(f"eps must be finite and positive, in grey levels (got {eps})")
+    return taps, eps
+
+
+def norm_loss_call(colour, rast, ref_u8, taps, grad_scale, eps=2.0, want_grad=True, background=45.0 / 255.0):
+    """One fpcdr_norm_loss call ("Normalised loss rule"): -> (sum d^2 [1] f64, grad_scale * d sum / d colour [B,H,W,C] or
+    None, planes), planes a dict of the float32 planes the kernels wrote: 'stats' [B,H,W,C,4] = (mu_a, m_a, mu_t, m_t), 'd' [B,H,W,C]
+    and, with a gradient, 'pq' [B,H,W,C,2] = (P, q) and 'p' [B,H,W,C]."""
+    if not (torch.is_tensor(colour) and colour.dim() == 4):
+        raise ValueError("colour must be a [B,H,W,C] tensor")
+    B, H, W, C = colour.shape
+    taps, eps = _norm_check(taps, eps, H, W)
+    _check_tensor('colour', colour, torch.float32, 4)
+    _check_tensor('rast', rast, torch.float32, 4)
+    _check_tensor('ref_u8', ref_u8, torch.uint8, 3)
+    if tuple(rast.shape) != (B, H, W, 4) or tuple(ref_u8.shape) != (B, H, W):
+        raise ValueError(f"rast must be [B,H,W,4] and ref_u8 [B,H,W] for colour {tuple(colour.shape)}")
+    k = taps.numel()
+    colour, rast, ref_u8 = colour.detach().contiguous(), rast.detach().contiguous(), ref_u8.contiguous()
+    with torch.cuda.device(colour.device):
+        f32 = dict(dtype=torch.float32, device=colour.device)
+        acc = torch.zeros(1, dtype=torch.float64, device=colour.device)
+        tmp, stats = torch.empty(B, H, W, C, 4, **f32), torch.empty(B, H, W, C, 4, **f32)
+        planes = {'stats': stats, 'd': torch.empty_like(colour)}
+        grad = None
+        if want_grad:
+            grad = torch.empty_like(colour)
+            planes['pq'], planes['p'] = torch.empty(B, H, W, C, 2, **f32), torch.empty_like(colour)
+        p = _lib.NormLoss(color=_ptr(colour), rast=_ptr(rast), ref=_ptr(ref_u8), B=B, H=H, W=W, C=C, bg=float(background),
+                          color_scale=255.0, grad_scale=float(grad_scale), eps=eps, radius=(k - 1) // 2, tmp=_ptr(tmp),
+                          stats=_ptr(stats), d=_ptr(planes['d']), pq=_ptr(planes.get('pq')), p=_ptr(planes.get('p')),
+                          loss_sum=_ptr(acc), grad_color=_ptr(grad))
+        for t in range(k):
+            p.taps[t] = float(taps[t])
+        _lib.call("fpcdr_norm_loss", ctypes.byref(p), _stream())
+    return acc, grad, planes
+
+
+class _normalised_pixel_loss_func(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, colour, rast, ref_u8, taps, n_total, eps, background):
+        acc, grad, _ = norm_loss_call(colour, rast, ref_u8, taps, 1.0 / n_total, eps, True, background)
+        ctx.save_for_backward(grad)
+        return (acc[0] / n_total).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        return grad * upstream, None, None, None, None, None, None
+
+
+def normalised_pixel_loss(colour, rast, ref_u8, sigma=None, kernel_size=31, eps=2.0, n_total=None, background=45.0 / 255.0, taps=None):
+    """mean over n_total elements (default: all of colour) of (n_a - n_t)^2, the render a = 255 * (rast.w > 0 ? colour : background) and
+    the capture t = ref each normalised by the mean and the deviation of its own Gaussian window, n = (x - G x) / sqrt(G x^2 - (G x)^2 +
+    eps^2) ("Normalised loss rule"; fpcdr_norm_loss): a camera's gain and offset drop out.  A dimensionless float32 scalar
+    whose backward is the closed-form gradient the same call computed, times the upstream scalar.  eps is in grey levels; taps= (odd,
+    3 .. 63 non-negative entries) overrides sigma and kernel_size.  Within a window the loss sees neither the level nor the contrast of the
+    texture: start from a baked or supplied texture, not from noise."""
+    if taps is None:
+        if sigma is None:
+            raise ValueError("normalised_pixel_loss needs sigma (or taps)")
+        taps = gaussian_taps(kernel_size, sigma)
+    return _normalised_pixel_loss_func.apply(colour, rast, ref_u8, taps, float(n_total or colour.numel()), float(eps), background)
 
 
 def undistort_images(images, intr, dist, clip_max=255, flip_rows=False):

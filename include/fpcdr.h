@@ -640,6 +640,45 @@ int fpcdr_bake_dilate(const float *tex_in, const uint8_t *filled_in, float *tex_
  * overlap.  n_images == 0 is success without a launch.  src and dst may sit at any address (wider accesses are used where it allows). */
 int fpcdr_downsample_u8(const uint8_t *src, uint8_t *dst, int64_t n_images, int H, int W, int s, void *stream);
 
+/* Locally normalised pixel loss: a pixel term that does not see a camera's exposure, gain or black level (the reference carries
+ * whiten / normalize_highlights in utils.py and builds torch.nn.LocalResponseNorm(2) at src/torch/fit.py:510, but wires none of it
+ * into its loss).  A pure addition: FPCDR_ABI_VERSION stays 16.  DESIGN.md 3, "Normalised loss rule"; taps, reflected borders and
+ * the adjoint G^T are those of fpcdr_blur_loss.  Per image, pixel and channel, in float32, every operation rounded once:
+ *   a  = color_scale * (rast.w > 0 ? color : bg)            t = (float)ref                    (t is the same for every channel)
+ *   for x in (a, t):  mu = G x,  m = G (x * x),  v = max(m - mu * mu, 0),  s = sqrt(v + eps * eps),  n = (x - mu) / s
+ *   d  = n_a - n_t                                          loss_sum += sum d^2               one float64, accumulated with an atomic
+ *   p  = (2 d) / s_a,  q = (p * n_a) / s_a,  P = p - q * mu_a
+ *   grad_color = rast.w > 0 ? (color_scale * grad_scale) * ((p - G^T P) - a * (G^T q)) : 0
+ * An uncovered pixel gets no gradient, but its a = color_scale * bg enters the windows of its neighbours.  The caller owns every
+ * buffer, in units of U = fpcdr_norm_loss_scratch_bytes(B, H, W, C) (one float per entry): tmp 4 U (scratch), stats 4 U, on return
+ * (mu_a, m_a, mu_t, m_t) per entry, d 1 U, and for a gradient pq 2 U, on return (P, q) per entry, and p 1 U.  tmp and stats are 16-byte
+ * aligned, pq 8-byte.  grad_color may be NULL: then only the value is computed (three of the five passes) and pq, p are not touched.
+ * Every plane and grad_color are written by plain stores in a fixed order: bit-identical from run to run.
+ * Errors, before any launch: a NULL pointer, sizes <= 0, C > 4, B or H > 65535, W * C >= 2^28, radius outside 1 .. 31, radius >
+ * min(H, W) - 1, an eps that is not finite and > 0, a misaligned plane. */
+typedef struct fpcdr_norm_loss_params fpcdr_norm_loss_params;
+struct fpcdr_norm_loss_params {
+    const float *color;    /* [B,H,W,C] */
+    const float *rast;     /* [B,H,W,4]; covered = rast.w > 0 */
+    const uint8_t *ref;    /* [B,H,W] 8-bit capture, broadcast over C */
+    int32_t B, H, W, C;
+    float bg;              /* background colour, reference 45/255 */
+    float color_scale;     /* reference 255 */
+    float grad_scale;      /* 1 / (number of elements of the global mean) */
+    float eps;             /* in grey levels, finite and > 0; the project's default is 2 */
+    int32_t radius;        /* (kernel size - 1) / 2 */
+    float taps[64];        /* taps[0 .. 2 * radius]; the rest is ignored */
+    float *tmp;            /* scratch [B,H,W,C,4] */
+    float *stats;          /* out [B,H,W,C,4]: (mu_a, m_a, mu_t, m_t) */
+    float *d;              /* out [B,H,W,C]: n_a - n_t */
+    float *pq;             /* out [B,H,W,C,2]: (P, q); may be NULL when grad_color is */
+    float *p;              /* out [B,H,W,C]; may be NULL when grad_color is */
+    double *loss_sum;      /* accumulated, one f64 */
+    float *grad_color;     /* out [B,H,W,C], or NULL */
+};
+size_t fpcdr_norm_loss_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t C);
+int fpcdr_norm_loss(const fpcdr_norm_loss_params *p, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
