@@ -5,48 +5,27 @@
 // t = ref are normalised by the mean and the deviation of their own Gaussian window before they are compared,
 //     mu = G x,  m = G (x x),  v = max(m - mu mu, 0),  s = sqrt(v + eps eps),  n = (x - mu) / s,      d = n_a - n_t,  loss_sum += sum d^2,
 // so that a gain and an offset of a camera (x -> alpha x + beta) drop out.  With p = 2 d / s_a, q = p n_a / s_a, P = p - q mu_a the gradient
-// is grad_a = p - G^T P - a (G^T q), masked and scaled like k_pixel_loss's.  Taps, reflected borders and the fold adjoint are those of
-// blur.hip (whose kernels stay as they are; the tiling below is a copy of theirs).
+// is grad_a = p - G^T P - a (G^T q), masked and scaled like k_pixel_loss's.  Taps, reflected borders, the tiling and the column pass
+// (with its fold adjoint) are sep_window.h's, shared with blur.hip; k_norm_rows_adj states the fold formula once more, for two planes.
 //
 // Five streaming passes: rows (from the inputs) -> the four row sums of an entry as one float4; columns over that plane (4 W C flat
 // columns) -> (mu_a, m_a, mu_t, m_t); pointwise -> d (+ the f64 sum) and, with a gradient wanted, the planes (P, q) and p; column
 // adjoint over (P, q) (2 W C flat columns); row adjoint with the final combine and the coverage mask.  Every plane is written by plain
-// stores, one lane per entry, each 1-D sum by fused multiply-add in the order t = 0 .. 2 r: bit-identical from run to run.  The taps
-// arrive in the kernel arguments and are indexed by the (uniform) loop counter: scalar loads, no private segment.
-#include "common.h"
+// stores, one lane per entry, each 1-D sum by fused multiply-add in the order t = 0 .. 2 r: bit-identical from run to run.
+#include "sep_window.h"
 
 #include <cmath>
 
 namespace {
 
-constexpr int NORM_RMAX = 31;      // 2 r + 1 <= 63
-constexpr int NORM_CMAX = 4;
-// Tile extents (tests/test_gpu_norm.py states the same numbers).  LDS: forward rows 4 * 318 * (4 + 1) floats = 25440 B, adjoint rows
-// 2 * 4 * 318 * 4 floats = 40704 B, columns (64 + 62) * 64 floats = 32256 B: at least four workgroups fit the 160 KiB of a CU.
-constexpr int ROW_TX = 256, ROW_TY = 4;
-constexpr int COL_TX = 64, COL_TY = 64;
-constexpr int ROW_SPAN = ROW_TX + 2 * NORM_RMAX;
+// LDS: forward rows 4 * 318 * (4 + 1) floats = 25440 B, adjoint rows 2 * 4 * 318 * 4 floats = 40704 B, columns 32256 B (sep_window.h).
 constexpr size_t POINT_BLOCKS = 4096;      // workgroups of the pointwise pass: 16 a CU
-
-struct NormTaps {
-    float g[64];
-};
-
-// flat index q = px * C + c of a row segment -> (px, c), C in 1 .. NORM_CMAX: constant divisors behind a uniform switch
-__device__ __forceinline__ void norm_split(int q, int C, int &px, int &c) {
-    switch (C) {
-        case 1: px = q; c = 0; break;
-        case 2: px = q >> 1; c = q & 1; break;
-        case 3: px = q / 3; c = q - 3 * px; break;
-        default: px = q >> 2; c = q & 3; break;
-    }
-}
 
 // Forward rows: a per entry and t per pixel staged with reflected indices; dst[entry] = (G_x a, G_x a^2, G_x t, G_x t^2).
 __global__ void __launch_bounds__(256) k_norm_rows(const float *__restrict__ color, const float4 *__restrict__ rast,
                                                    const uint8_t *__restrict__ ref, float4 *__restrict__ dst, int H, int W, int C, int r,
-                                                   float bg, float color_scale, NormTaps taps) {
-    __shared__ float sa[ROW_TY][ROW_SPAN * NORM_CMAX];
+                                                   float bg, float color_scale, WinTaps taps) {
+    __shared__ float sa[ROW_TY][ROW_SPAN * WIN_CMAX];
     __shared__ float st[ROW_TY][ROW_SPAN];
     const int x0 = blockIdx.x * ROW_TX, y0 = blockIdx.y * ROW_TY;
     const size_t img = (size_t)blockIdx.z * H * W;
@@ -55,10 +34,9 @@ __global__ void __launch_bounds__(256) k_norm_rows(const float *__restrict__ col
         const int y = y0 + row;
         for (int q = threadIdx.x; q < nq; q += 256) {
             int px, c;
-            norm_split(q, C, px, c);
+            win_split(q, C, px, c);
             int x = x0 - r + px;
-            if (x < 0) x = -x;
-            if (x > W - 1) x = 2 * (W - 1) - x;      // (below 0 only past the last sample any output of the image takes)
+            win_reflect(x, W);
             float va = 0.0f, vt = 0.0f;
             if (y < H && x >= 0 && x < W) {
                 const size_t pix = img + (size_t)y * W + x;
@@ -76,7 +54,7 @@ __global__ void __launch_bounds__(256) k_norm_rows(const float *__restrict__ col
         if (y >= H) break;
         for (int q = threadIdx.x; q < tq; q += 256) {
             int px, c;
-            norm_split(q, C, px, c);
+            win_split(q, C, px, c);
             const int x = x0 + px;
             if (x >= W) continue;
             const float *pa = &sa[row][q];               // pixel x - r of this channel
@@ -94,51 +72,11 @@ __global__ void __launch_bounds__(256) k_norm_rows(const float *__restrict__ col
     }
 }
 
-// Column passes over planes of H rows of L floats (blur.hip's k_blur_cols without the sum).  ADJ = false: reflected staging, dst = G_y src.
-// ADJ = true: zero-extended staging, dst = G_y^T src by the fold formula.
+// Column passes over planes of H rows of L floats (sep_window.h, without the sum).  ADJ = false: dst = G_y src.  ADJ = true: dst = G_y^T src.
 template <bool ADJ>
 __global__ void __launch_bounds__(256) k_norm_cols(const float *__restrict__ src, float *__restrict__ dst, int H, int L, int r,
-                                                   NormTaps taps) {
-    __shared__ float s[COL_TY + 2 * NORM_RMAX][COL_TX];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int q = blockIdx.x * COL_TX + lane, y0 = blockIdx.y * COL_TY;
-    const size_t base = (size_t)blockIdx.z * H * L;
-    const int ny = COL_TY + 2 * r, k = 2 * r + 1;
-    for (int row = w; row < ny; row += 4) {              // rows y0 - r .. y0 + COL_TY + r - 1
-        int y = y0 - r + row;
-        if (!ADJ) {
-            if (y < 0) y = -y;
-            if (y > H - 1) y = 2 * (H - 1) - y;
-        }
-        float v = 0.0f;
-        if (y >= 0 && y < H && q < L) v = src[base + (size_t)y * L + q];
-        s[row][lane] = v;
-    }
-    __syncthreads();
-    for (int i = 0; i < COL_TY / 4; ++i) {
-        const int row = w * (COL_TY / 4) + i, y = y0 + row;      // (uniform over the wave)
-        if (y >= H) break;
-        if (q >= L) continue;
-        float acc = 0.0f;
-        if (!ADJ) {
-            for (int t = 0; t < k; ++t) acc = __builtin_fmaf(taps.g[t], s[row + t][lane], acc);
-        } else {
-            for (int t = 0; t < k; ++t) acc = __builtin_fmaf(taps.g[t], s[row + 2 * r - t][lane], acc);
-            const int lo = y0 - r;                       // row of s[0]
-            if (y >= 1 && y <= r)
-                for (int t = 0; t < k; ++t) {
-                    const int pos = r - y - t, li = pos - lo;
-                    if (pos >= 0 && pos < H && li >= 0 && li < ny) acc = __builtin_fmaf(taps.g[t], s[li][lane], acc);
-                }
-            const int j = H - 1 - y;
-            if (j >= 1 && j <= r)
-                for (int t = 0; t < k; ++t) {
-                    const int pos = H - 1 + j + r - t, li = pos - lo;
-                    if (pos >= 0 && pos < H && li >= 0 && li < ny) acc = __builtin_fmaf(taps.g[t], s[li][lane], acc);
-                }
-        }
-        dst[base + (size_t)y * L + q] = acc;
-    }
+                                                   WinTaps taps) {
+    win_cols<ADJ, false>(src, dst, nullptr, H, L, r, taps);
 }
 
 // Pointwise: one lane per entry e = pix * C + c.  d (and, with pq, the planes (P, q) and p) by plain stores; sum d^2 wave -> block ->
@@ -188,9 +126,9 @@ __global__ void __launch_bounds__(256) k_norm_point(const float *__restrict__ co
 __global__ void __launch_bounds__(256) k_norm_rows_adj(const float *__restrict__ color, const float4 *__restrict__ rast,
                                                        const float2 *__restrict__ src, const float *__restrict__ p_in,
                                                        float *__restrict__ dst, int H, int W, int C, int r, float color_scale, float gain,
-                                                       NormTaps taps) {
-    __shared__ float sP[ROW_TY][ROW_SPAN * NORM_CMAX];
-    __shared__ float sQ[ROW_TY][ROW_SPAN * NORM_CMAX];
+                                                       WinTaps taps) {
+    __shared__ float sP[ROW_TY][ROW_SPAN * WIN_CMAX];
+    __shared__ float sQ[ROW_TY][ROW_SPAN * WIN_CMAX];
     const int x0 = blockIdx.x * ROW_TX, y0 = blockIdx.y * ROW_TY;
     const size_t img = (size_t)blockIdx.z * H * W;
     const int nq = (ROW_TX + 2 * r) * C;
@@ -198,7 +136,7 @@ __global__ void __launch_bounds__(256) k_norm_rows_adj(const float *__restrict__
         const int y = y0 + row;
         for (int q = threadIdx.x; q < nq; q += 256) {
             int px, c;
-            norm_split(q, C, px, c);
+            win_split(q, C, px, c);
             const int x = x0 - r + px;
             float2 v = make_float2(0.0f, 0.0f);
             if (y < H && x >= 0 && x < W) v = src[(img + (size_t)y * W + x) * C + c];
@@ -213,10 +151,10 @@ __global__ void __launch_bounds__(256) k_norm_rows_adj(const float *__restrict__
         if (y >= H) break;
         for (int q = threadIdx.x; q < tq; q += 256) {
             int px, c;
-            norm_split(q, C, px, c);
+            win_split(q, C, px, c);
             const int x = x0 + px;
             if (x >= W) continue;
-            float aP = 0.0f, aQ = 0.0f;
+            float aP = 0.0f, aQ = 0.0f;              // sep_window.h's fold formula, two planes tap by tap
             for (int t = 0; t < k; ++t) {
                 const int li = q + (2 * r - t) * C;
                 aP = __builtin_fmaf(taps.g[t], sP[row][li], aP);
@@ -263,22 +201,20 @@ extern "C" int fpcdr_norm_loss(const fpcdr_norm_loss_params *p, void *stream) {
     FPCDR_REQUIRE(p->color && p->rast && p->ref && p->tmp && p->stats && p->d && p->loss_sum, "null pointer");
     FPCDR_REQUIRE(!p->grad_color || (p->pq && p->p), "a gradient needs the planes pq and p");
     FPCDR_REQUIRE(p->B > 0 && p->H > 0 && p->W > 0 && p->C > 0, "sizes must be positive");
-    FPCDR_REQUIRE(p->C <= NORM_CMAX, "at most 4 channels");
+    FPCDR_REQUIRE(p->C <= WIN_CMAX, "at most 4 channels");
     FPCDR_REQUIRE(p->B <= 65535 && p->H <= 65535 && (long long)p->W * p->C < (1ll << 28), "sizes out of range");
-    FPCDR_REQUIRE(p->radius >= 1 && p->radius <= NORM_RMAX, "kernel size 2 * radius + 1 must be odd and in 3 .. 63");
+    FPCDR_REQUIRE(p->radius >= 1 && p->radius <= WIN_RMAX, "kernel size 2 * radius + 1 must be odd and in 3 .. 63");
     FPCDR_REQUIRE(p->radius <= (p->H < p->W ? p->H : p->W) - 1, "reflected borders need radius <= min(H, W) - 1");
     FPCDR_REQUIRE(std::isfinite(p->eps) && p->eps > 0.0f && std::isfinite(p->eps * p->eps), "eps must be finite and positive");
     FPCDR_REQUIRE(((uintptr_t)p->tmp & 15) == 0 && ((uintptr_t)p->stats & 15) == 0 && ((uintptr_t)p->pq & 7) == 0,
                   "tmp and stats must be 16-byte aligned, pq 8-byte aligned");
     const hipStream_t st = (hipStream_t)stream;
     const int B = p->B, H = p->H, W = p->W, C = p->C, L = W * C, r = p->radius;
-    NormTaps taps;
-    for (int t = 0; t < 64; ++t) taps.g[t] = t <= 2 * r ? p->taps[t] : 0.0f;
+    const WinTaps taps = win_taps(p->taps, r);
     const float eps2 = p->eps * p->eps;
     const size_t n_pix = (size_t)B * H * W, n_blocks = (n_pix * C + 255) / 256;
-    const dim3 grid_rows((W + ROW_TX - 1) / ROW_TX, (H + ROW_TY - 1) / ROW_TY, B);
-    const dim3 grid_cols4((4 * L + COL_TX - 1) / COL_TX, (H + COL_TY - 1) / COL_TY, B);
-    const dim3 grid_cols2((2 * L + COL_TX - 1) / COL_TX, (H + COL_TY - 1) / COL_TY, B);
+    const dim3 grid_rows = win_grid(W, ROW_TX, H, ROW_TY, B);
+    const dim3 grid_cols4 = win_grid(4 * L, COL_TX, H, COL_TY, B), grid_cols2 = win_grid(2 * L, COL_TX, H, COL_TY, B);
     // (a grid-stride loop over at most POINT_BLOCKS workgroups: one f64 atomic per workgroup on one address -- a workgroup per 256
     // entries was 259 k atomics at 32 x 1080p and 3.2 ms of a 0.8 ms pass)
     const dim3 grid_point((unsigned)(n_blocks < POINT_BLOCKS ? n_blocks : POINT_BLOCKS));

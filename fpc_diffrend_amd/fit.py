@@ -290,6 +290,16 @@ def pixel_loss_normalised(colour, rast_out, ref_u8, taps, eps, n_total=None):
     return acc, grad
 
 
+def _check_window_term(cfg, kind, name, graph_why, sigmas):
+    """What FitConfig.blur_sigma > 0 and norm_sigma > 0 (kind 'blur' / 'norm') both ask of the other options, or ValueError."""
+    if not cfg.fused_loss:
+        raise ValueError(f"FitConfig.{kind}_sigma > 0 needs fused_loss=True: the {name} loss replaces pixel_loss_fused")
+    if cfg.hip_graph:
+        raise ValueError(f"FitConfig.{kind}_sigma > 0 cannot be combined with hip_graph: {graph_why}")
+    for sigma in sigmas:
+        dr.gaussian_taps(getattr(cfg, kind + '_kernel_size'), sigma)                     # (raises for a bad kernel size or sigma)
+
+
 class _mvp_func(torch.autograd.Function):
     """Model-view-projection matrices of a minibatch in one kernel each way (fpcdr_mvp_fwd / _bwd)."""
 
@@ -852,21 +862,11 @@ class Fitter:
                   {"params": self.q_opt, 'lr': cfg.lr_q}, {"params": self.per_frame_t, 'lr': cfg.lr_t},
                   {"params": self.per_frame_q, 'lr': cfg.lr_q}, {"params": self.tex_opt, 'lr': cfg.lr_base * cfg.lr_tex_coef}]
         if cfg.blur_sigma > 0:
-            if not cfg.fused_loss:
-                raise ValueError("FitConfig.blur_sigma > 0 needs fused_loss=True: the blurred loss replaces pixel_loss_fused")
-            if cfg.hip_graph:
-                raise ValueError("FitConfig.blur_sigma > 0 cannot be combined with hip_graph: sigma and the switch back to the one-pass "
-                                 "objective change from one iteration to the next")
-            dr.gaussian_taps(cfg.blur_kernel_size, cfg.blur_sigma)                       # (raises for a bad kernel size or sigma)
-            if cfg.blur_sigma_end is not None:
-                dr.gaussian_taps(cfg.blur_kernel_size, cfg.blur_sigma_end)
+            _check_window_term(cfg, 'blur', "blurred", "sigma and the switch back to the one-pass objective change from one iteration to the next",
+                               (cfg.blur_sigma,) + (() if cfg.blur_sigma_end is None else (cfg.blur_sigma_end,)))
         if cfg.norm_sigma > 0:
-            if not cfg.fused_loss:
-                raise ValueError("FitConfig.norm_sigma > 0 needs fused_loss=True: the normalised loss replaces pixel_loss_fused")
-            if cfg.hip_graph:
-                raise ValueError("FitConfig.norm_sigma > 0 cannot be combined with hip_graph: the switch back to the path the other "
-                                 "flags select changes the step from one iteration to the next")
-            dr.gaussian_taps(cfg.norm_kernel_size, cfg.norm_sigma)                       # (raises for a bad kernel size or sigma)
+            _check_window_term(cfg, 'norm', "normalised", "the switch back to the path the other flags select changes the step from one "
+                               "iteration to the next", (cfg.norm_sigma,))
             if not (float(cfg.norm_eps) > 0.0 and float(cfg.norm_eps) < float('inf')):
                 raise ValueError(f"FitConfig.norm_eps must be finite and positive (got {cfg.norm_eps})")
         if cfg.hip_graph == 'auto':
@@ -1248,27 +1248,26 @@ class Fitter:
             for m in (self.m1, self.m2, self.m3):
                 m.requires_grad = True
 
+    def _window_taps(self, kind, i, sigma_at=None):
+        """The taps of the windowed pixel term `kind` ('blur' / 'norm') at iteration i (default: the current one), or None when that
+        iteration does not use it.  sigma_at(i, n), n the iterations the term lasts, overrides the constant sigma."""
+        cfg = self.cfg
+        i = self.iteration if i is None else i
+        sigma, iters = getattr(cfg, kind + '_sigma'), getattr(cfg, kind + '_iters')
+        if not sigma > 0 or (iters and i >= iters):
+            return None
+        return dr.gaussian_taps(getattr(cfg, kind + '_kernel_size'), sigma_at(i, iters or cfg.max_iter) if sigma_at else float(sigma))
+
     def blur_taps(self, i=None):
         """The taps of the blurred pixel loss at iteration i (default: the current one), or None when that iteration is not blurred.
         A function of the iteration alone, so a resumed run continues on the right side of the switch."""
-        cfg = self.cfg
-        i = self.iteration if i is None else i
-        if not cfg.blur_sigma > 0 or (cfg.blur_iters and i >= cfg.blur_iters):
-            return None
-        sigma = float(cfg.blur_sigma)
-        if cfg.blur_sigma_end is not None:
-            n = cfg.blur_iters or cfg.max_iter
-            sigma = sigma * (float(cfg.blur_sigma_end) / sigma) ** (min(i, n - 1) / max(n - 1, 1))
-        return dr.gaussian_taps(cfg.blur_kernel_size, sigma)
+        s0, s1 = float(self.cfg.blur_sigma), self.cfg.blur_sigma_end
+        return self._window_taps('blur', i, None if s1 is None else lambda i, n: s0 * (float(s1) / s0) ** (min(i, n - 1) / max(n - 1, 1)))
 
     def norm_taps(self, i=None):
         """The taps of the normalised pixel loss at iteration i (default: the current one), or None when that iteration is not
         normalised.  A function of the iteration alone, so a resumed run continues on the right side of the switch."""
-        cfg = self.cfg
-        i = self.iteration if i is None else i
-        if not cfg.norm_sigma > 0 or (cfg.norm_iters and i >= cfg.norm_iters):
-            return None
-        return dr.gaussian_taps(cfg.norm_kernel_size, float(cfg.norm_sigma))
+        return self._window_taps('norm', i)
 
     def loss_and_backward(self, frame_ids, view_ids=None, validate=True):
         """Forward + backward of fit.py:556-611 for a batch of frames x cameras (view_ids: see mvp).  Returns the loss (tensor).
@@ -1287,12 +1286,12 @@ class Fitter:
         # (the mip branch of the reference's render(), fit.py:153-155, runs inside the same kernels)
         one_shot = (cfg.fused_objective and cfg.fused_render and cfg.fused_loss and C in (1, 3, 4) and cfg.shading == 'texture'
                     and (not mip or cfg.sparse_objective))
-        blur_taps = self.blur_taps(i) if cfg.blur_sigma > 0 else None
-        if blur_taps is not None:
-            one_shot = False           # the blurred loss needs the image in memory: the operator path
-        norm_taps = self.norm_taps(i) if cfg.norm_sigma > 0 else None
-        if norm_taps is not None:
-            one_shot = False           # so does the normalised loss
+        # the windowed pixel term of this iteration, (kind, taps), or None (FitConfig lets at most one sigma be > 0)
+        window = ('blur', self.blur_taps(i)) if cfg.blur_sigma > 0 else ('norm', self.norm_taps(i)) if cfg.norm_sigma > 0 else None
+        if window is not None and window[1] is None:
+            window = None
+        if window is not None:
+            one_shot = False           # a windowed loss needs the image in memory: the operator path
         # one flat buffer for the small accumulators of this step's backward kernels, zero-filled by the objective's first kernel; the
         # pool around it goes to the functions whose backward takes views of it
         zero_buf, pool = None, None
@@ -1371,12 +1370,12 @@ class Fitter:
             if lap is not None:
                 loss = loss + lap.detach()
         elif cfg.fused_loss:
-            if blur_taps is not None:
-                sum_sq, g_colour = pixel_loss_blurred(colour, rast_out, ref, blur_taps, n_total)
-            elif norm_taps is not None:
-                sum_sq, g_colour = pixel_loss_normalised(colour, rast_out, ref, norm_taps, cfg.norm_eps, n_total)
-            else:
+            if window is None:
                 sum_sq, g_colour = pixel_loss_fused(colour, rast_out, ref, n_total)
+            elif window[0] == 'blur':
+                sum_sq, g_colour = pixel_loss_blurred(colour, rast_out, ref, window[1], n_total)
+            else:
+                sum_sq, g_colour = pixel_loss_normalised(colour, rast_out, ref, window[1], cfg.norm_eps, n_total)
             self._backward(colour, g_colour, reg, lap)
             loss = sum_sq[0].to(torch.float32) / n_total + reg.detach() + (lap.detach() if lap is not None else 0.0)
         else:

@@ -660,46 +660,64 @@ def gaussian_taps(kernel_size, sigma):
     return torch.from_numpy((g / g.sum()).astype(np.float32))
 
 
-def blur_loss_call(colour, rast, ref_u8, taps, grad_scale, background=45.0 / 255.0, want_grad=True):
-    """One fpcdr_blur_loss call: -> (sum E^2 [1] f64, grad_scale * d sum / d colour [B,H,W,C] or None, E [B,H,W,C])."""
-    _check_tensor('colour', colour, torch.float32, 4)
-    _check_tensor('rast', rast, torch.float32, 4)
-    _check_tensor('ref_u8', ref_u8, torch.uint8, 3)
+def _window_args(colour, rast, ref_u8, taps, nonneg_taps=False):
+    """What both windowed-loss calls do before they allocate: -> (colour, rast, ref_u8 detached and contiguous, the taps as a CPU
+    float32 tensor [k]), or ValueError.  The checks that need no GPU (the taps) run before the tensors are looked at."""
+    if not (torch.is_tensor(colour) and colour.dim() == 4):
+        raise ValueError("colour must be a [B,H,W,C] tensor")
     B, H, W, C = colour.shape
-    if tuple(rast.shape) != (B, H, W, 4) or tuple(ref_u8.shape) != (B, H, W):
-        raise ValueError(f"rast must be [B,H,W,4] and ref_u8 [B,H,W] for colour {tuple(colour.shape)}")
     taps = torch.as_tensor(taps, dtype=torch.float32).detach().cpu().reshape(-1)
     k = taps.numel()
     if k % 2 == 0 or not 3 <= k <= 63:
         raise ValueError(f"the number of taps must be odd and in 3 .. 63 (got {k})")
-    r = (k - 1) // 2
-    if r >= min(H, W):
+    if nonneg_taps and (bool((taps < 0).any()) or not bool(torch.isfinite(taps).all())):
+        raise ValueError("the taps of the normalised loss must be finite and non-negative (m >= mu^2 rests on it)")
+    if (k - 1) // 2 >= min(H, W):
         raise ValueError(f"reflected borders need (kernel_size - 1) / 2 < min(H, W) (got kernel size {k} for {H} x {W})")
-    colour, rast, ref_u8 = colour.detach().contiguous(), rast.detach().contiguous(), ref_u8.contiguous()
+    _check_tensor('colour', colour, torch.float32, 4)
+    _check_tensor('rast', rast, torch.float32, 4)
+    _check_tensor('ref_u8', ref_u8, torch.uint8, 3)
+    if tuple(rast.shape) != (B, H, W, 4) or tuple(ref_u8.shape) != (B, H, W):
+        raise ValueError(f"rast must be [B,H,W,4] and ref_u8 [B,H,W] for colour {tuple(colour.shape)}")
+    return colour.detach().contiguous(), rast.detach().contiguous(), ref_u8.contiguous(), taps
+
+
+def _set_taps(p, taps):
+    """taps [k] -> the taps field of a parameter struct (fpcdr_blur_loss_params / fpcdr_norm_loss_params)"""
+    for t in range(taps.numel()):
+        p.taps[t] = float(taps[t])
+
+
+def blur_loss_call(colour, rast, ref_u8, taps, grad_scale, background=45.0 / 255.0, want_grad=True):
+    """One fpcdr_blur_loss call: -> (sum E^2 [1] f64, grad_scale * d sum / d colour [B,H,W,C] or None, E [B,H,W,C])."""
+    colour, rast, ref_u8, taps = _window_args(colour, rast, ref_u8, taps)
+    B, H, W, C = colour.shape
     with torch.cuda.device(colour.device):
         acc = torch.zeros(1, dtype=torch.float64, device=colour.device)
         tmp, blurred = torch.empty_like(colour), torch.empty_like(colour)
         grad = torch.empty_like(colour) if want_grad else None
         p = _lib.BlurLoss(color=_ptr(colour), rast=_ptr(rast), ref=_ptr(ref_u8), B=B, H=H, W=W, C=C, bg=float(background),
-                          color_scale=255.0, grad_scale=float(grad_scale), radius=r, tmp=_ptr(tmp), blurred=_ptr(blurred),
-                          loss_sum=_ptr(acc), grad_color=_ptr(grad))
-        for t in range(k):
-            p.taps[t] = float(taps[t])
+                          color_scale=255.0, grad_scale=float(grad_scale), radius=(taps.numel() - 1) // 2, tmp=_ptr(tmp),
+                          blurred=_ptr(blurred), loss_sum=_ptr(acc), grad_color=_ptr(grad))
+        _set_taps(p, taps)
         _lib.call("fpcdr_blur_loss", ctypes.byref(p), _stream())
     return acc, grad, blurred
 
 
-class _blurred_pixel_loss_func(torch.autograd.Function):
+class _windowed_pixel_loss_func(torch.autograd.Function):
+    """call = blur_loss_call or norm_loss_call, rest = its arguments behind grad_scale: the mean over n_total, and the gradient the same
+    call computed, times the upstream scalar, as the backward."""
     @staticmethod
-    def forward(ctx, colour, rast, ref_u8, taps, n_total, background):
-        acc, grad, _ = blur_loss_call(colour, rast, ref_u8, taps, 1.0 / n_total, background, want_grad=True)
+    def forward(ctx, call, n_total, colour, rast, ref_u8, taps, *rest):
+        acc, grad, _ = call(colour, rast, ref_u8, taps, 1.0 / n_total, *rest)
         ctx.save_for_backward(grad)
+        ctx.n_rest = len(rest)
         return (acc[0] / n_total).to(torch.float32)
 
     @staticmethod
     def backward(ctx, upstream):
         grad, = ctx.saved_tensors
-        return grad * upstream, None, None, None, None, None
+        return (None, None, grad * upstream, None, None, None) + (None,) * ctx.n_rest
 
 
 def blurred_pixel_loss(colour, rast, ref_u8, sigma=None, kernel_size=31, n_total=None, background=45.0 / 255.0, taps=None):
@@ -710,41 +728,18 @@ def blurred_pixel_loss(colour, rast, ref_u8, sigma=None, kernel_size=31, n_total
         if sigma is None:
             raise ValueError("blurred_pixel_loss needs sigma (or taps)")
         taps = gaussian_taps(kernel_size, sigma)
-    return _blurred_pixel_loss_func.apply(colour, rast, ref_u8, taps, float(n_total or colour.numel()), background)
-
-
-def _norm_check(taps, eps, H, W):
-    """The taps as a CPU float32 tensor [k] and eps as a float, or ValueError: the argument checks of the normalised loss that need no GPU
-    (they run before the tensors are looked at)."""
-    taps = torch.as_tensor(taps, dtype=torch.float32).detach().cpu().reshape(-1)
-    k = taps.numel()
-    if k % 2 == 0 or not 3 <= k <= 63:
-        raise ValueError(f"the number of taps must be odd and in 3 .. 63 (got {k})")
-    if bool((taps < 0).any()) or not bool(torch.isfinite(taps).all()):
-        raise ValueError("the taps of the normalised loss must be finite and non-negative (m >= mu^2 rests on it)")
-    if (k - 1) // 2 >= min(H, W):
-        raise ValueError(f"reflected borders need (kernel_size - 1) / 2 < min(H, W) (got kernel size {k} for {H} x {W})")
-    eps = float(eps)
-    if not (eps > 0.0 and eps < float('inf')):
-        raise ValueError(f"eps must be finite and positive, in grey levels (got {eps})")
-    return taps, eps
+    return _windowed_pixel_loss_func.apply(blur_loss_call, float(n_total or colour.numel()), colour, rast, ref_u8, taps, background)
 
 
 def norm_loss_call(colour, rast, ref_u8, taps, grad_scale, eps=2.0, want_grad=True, background=45.0 / 255.0):
     """One fpcdr_norm_loss call ("Normalised loss rule"): -> (sum d^2 [1] f64, grad_scale * d sum / d colour [B,H,W,C] or
     None, planes), planes a dict of the float32 planes the kernels wrote: 'stats' [B,H,W,C,4] = (mu_a, m_a, mu_t, m_t), 'd' [B,H,W,C]
     and, with a gradient, 'pq' [B,H,W,C,2] = (P, q) and 'p' [B,H,W,C]."""
-    if not (torch.is_tensor(colour) and colour.dim() == 4):
-        raise ValueError("colour must be a [B,H,W,C] tensor")
+    eps = float(eps)
+    if not (eps > 0.0 and eps < float('inf')):
+        raise ValueError(f"eps must be finite and positive, in grey levels (got {eps})")
+    colour, rast, ref_u8, taps = _window_args(colour, rast, ref_u8, taps, nonneg_taps=True)
     B, H, W, C = colour.shape
-    taps, eps = _norm_check(taps, eps, H, W)
-    _check_tensor('colour', colour, torch.float32, 4)
-    _check_tensor('rast', rast, torch.float32, 4)
-    _check_tensor('ref_u8', ref_u8, torch.uint8, 3)
-    if tuple(rast.shape) != (B, H, W, 4) or tuple(ref_u8.shape) != (B, H, W):
-        raise ValueError(f"rast must be [B,H,W,4] and ref_u8 [B,H,W] for colour {tuple(colour.shape)}")
-    k = taps.numel()
-    colour, rast, ref_u8 = colour.detach().contiguous(), rast.detach().contiguous(), ref_u8.contiguous()
     with torch.cuda.device(colour.device):
         f32 = dict(dtype=torch.float32, device=colour.device)
         acc = torch.zeros(1, dtype=torch.float64, device=colour.device)
@@ -755,26 +750,12 @@ def norm_loss_call(colour, rast, ref_u8, taps, grad_scale, eps=2.0, want_grad=Tr
             grad = torch.empty_like(colour)
             planes['pq'], planes['p'] = torch.empty(B, H, W, C, 2, **f32), torch.empty_like(colour)
         p = _lib.NormLoss(color=_ptr(colour), rast=_ptr(rast), ref=_ptr(ref_u8), B=B, H=H, W=W, C=C, bg=float(background),
-                          color_scale=255.0, grad_scale=float(grad_scale), eps=eps, radius=(k - 1) // 2, tmp=_ptr(tmp),
+                          color_scale=255.0, grad_scale=float(grad_scale), eps=eps, radius=(taps.numel() - 1) // 2, tmp=_ptr(tmp),
                           stats=_ptr(stats), d=_ptr(planes['d']), pq=_ptr(planes.get('pq')), p=_ptr(planes.get('p')),
                           loss_sum=_ptr(acc), grad_color=_ptr(grad))
-        for t in range(k):
-            p.taps[t] = float(taps[t])
+        _set_taps(p, taps)
         _lib.call("fpcdr_norm_loss", ctypes.byref(p), _stream())
     return acc, grad, planes
-
-
-class _normalised_pixel_loss_func(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, colour, rast, ref_u8, taps, n_total, eps, background):
-        acc, grad, _ = norm_loss_call(colour, rast, ref_u8, taps, 1.0 / n_total, eps, True, background)
-        ctx.save_for_backward(grad)
-        return (acc[0] / n_total).to(torch.float32)
-
-    @staticmethod
-    def backward(ctx, upstream):
-        grad, = ctx.saved_tensors
-        return grad * upstream, None, None, None, None, None, None
 
 
 def normalised_pixel_loss(colour, rast, ref_u8, sigma=None, kernel_size=31, eps=2.0, n_total=None, background=45.0 / 255.0, taps=None):
@@ -788,7 +769,8 @@ def normalised_pixel_loss(colour, rast, ref_u8, sigma=None, kernel_size=31, eps=
         if sigma is None:
             raise ValueError("normalised_pixel_loss needs sigma (or taps)")
         taps = gaussian_taps(kernel_size, sigma)
-    return _normalised_pixel_loss_func.apply(colour, rast, ref_u8, taps, float(n_total or colour.numel()), float(eps), background)
+    return _windowed_pixel_loss_func.apply(norm_loss_call, float(n_total or colour.numel()), colour, rast, ref_u8, taps, float(eps), True,
+                                           background)
 
 
 def undistort_images(images, intr, dist, clip_max=255, flip_rows=False):

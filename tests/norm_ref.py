@@ -144,7 +144,7 @@ def loss_plain(colour, coverage, ref_u8, g, eps=EPS, n_total=None, background=BA
     return (d * d).sum() / float(n_total or colour.numel())
 
 
-# the cases of tests/test_gpu_norm.py beyond blur_ref.SHAPES: (B, H, W, C, kernel size, sigma).  Tile extents of csrc/norm.hip: the row
+# the cases of tests/test_gpu_norm.py beyond blur_ref.SHAPES: (B, H, W, C, kernel size, sigma).  Tile extents of csrc/sep_window.h: the row
 # passes take ROW_TX pixels x ROW_TY rows per workgroup, the column passes COL_TX flat columns x COL_TY rows, flat columns being 4 W C
 # (forward) or 2 W C (adjoint) wide
 ROW_TX, ROW_TY = 256, 4

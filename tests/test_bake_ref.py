@@ -353,27 +353,16 @@ def test_bake_has_no_cpu_path():
 
 def test_bake_kernels_have_no_private_segment():
     """a kernel with a private segment is dispatched several times slower.  The three kernels of bake.hip keep
-    everything in registers and use no LDS; read from the built object the way test_compare_kernels_have_no_private_segment reads its
-    kernels'."""
-    import shutil, subprocess, tempfile
-    llvm = "/opt/rocm/lib/llvm/bin"
-    path = os.path.join(ROOT, "fpc_diffrend_amd", "csrc", "_build", "bake.o")
-    if not (os.path.exists(path) and os.path.exists(os.path.join(llvm, "llvm-readelf"))):
+    everything in registers and use no LDS; read from the built object (tests/codeobj.py)."""
+    import codeobj
+    recs = codeobj.kernels("bake.o")
+    if recs is None:
         pytest.skip("no built objects / llvm tools")
-    tmp = tempfile.mkdtemp()
-    try:
-        subprocess.check_call([f"{llvm}/llvm-objcopy", f"--dump-section=.hip_fatbin={tmp}/fb.bin", path], stderr=subprocess.DEVNULL)
-        subprocess.check_call([f"{llvm}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                               f"--input={tmp}/fb.bin", f"--output={tmp}/dev.co", "--unbundle"], stderr=subprocess.DEVNULL)
-        notes = subprocess.check_output([f"{llvm}/llvm-readelf", "--notes", f"{tmp}/dev.co"], text=True)
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     seen = set()
-    for blk in re.split(r"\n\s*- \.agpr_count", notes)[1:]:
-        name = re.search(r"\.name:\s*(\S+)", blk).group(1)
+    for name, private, lds in recs:
         for k in ("k_bake_accumulate", "k_bake_resolve", "k_bake_dilate"):
             if k in name:
                 seen.add(k)
-                assert int(re.search(r"\.private_segment_fixed_size:\s*(\d+)", blk).group(1)) == 0, name
-                assert int(re.search(r"\.group_segment_fixed_size:\s*(\d+)", blk).group(1)) == 0, name
+                assert private == 0, name
+                assert lds == 0, name
     assert len(seen) == 3

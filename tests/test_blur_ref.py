@@ -120,27 +120,26 @@ def test_library_exports_the_blur_entry_with_abi_16_and_the_binding_mirrors_the_
 
 def test_blur_kernels_have_no_private_segment():
     """The taps are indexed by a runtime radius: from registers that would be a private segment.  They are read
-    uniformly from the kernel arguments instead; read from the built object the way test_fit_loop_kernels_have_no_private_segment
-    reads the fit loop's."""
-    import shutil
-    import tempfile
-    llvm = "/opt/rocm/lib/llvm/bin"
-    obj = os.path.join(ROOT, "fpc_diffrend_amd", "csrc", "_build", "blur.o")
-    if not (os.path.exists(obj) and os.path.exists(os.path.join(llvm, "llvm-readelf"))):
+    uniformly from the kernel arguments instead; read from the built object (tests/codeobj.py)."""
+    import codeobj
+    recs = codeobj.kernels("blur.o")
+    if recs is None:
         pytest.skip("no built objects / llvm tools")
-    tmp = tempfile.mkdtemp()
-    try:
-        subprocess.check_call([f"{llvm}/llvm-objcopy", f"--dump-section=.hip_fatbin={tmp}/fb.bin", obj], stderr=subprocess.DEVNULL)
-        subprocess.check_call([f"{llvm}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                               f"--input={tmp}/fb.bin", f"--output={tmp}/dev.co", "--unbundle"], stderr=subprocess.DEVNULL)
-        notes = subprocess.check_output([f"{llvm}/llvm-readelf", "--notes", f"{tmp}/dev.co"], text=True)
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     seen = 0
-    for blk in re.split(r"\n\s*- \.agpr_count", notes)[1:]:
-        name = re.search(r"\.name:\s*(\S+)", blk).group(1)
+    for name, private, lds in recs:
         if re.search(r"k_blur_rows|k_blur_cols", name):
             seen += 1
-            assert int(re.search(r"\.private_segment_fixed_size:\s*(\d+)", blk).group(1)) == 0, name
-            assert int(re.search(r"\.group_segment_fixed_size:\s*(\d+)", blk).group(1)) <= 80 * 1024, name      # two workgroups per CU
+            assert private == 0, name
+            assert lds <= 80 * 1024, name      # two workgroups per CU
     assert seen == 4
+
+
+def test_gpu_blur_states_the_tile_extents_of_the_source():
+    """tests/test_gpu_blur.py builds its EXTENT_SHAPES around a copy of the tile extents (it reads no C): that copy and
+    csrc/sep_window.h state the same four numbers."""
+    gpu_test = open(os.path.join(HERE, "test_gpu_blur.py")).read()
+    m = re.search(r"^ROW_TX, ROW_TY = (\d+), (\d+)\nCOL_TX, COL_TY = (\d+), (\d+)$", gpu_test, re.M)
+    assert m, "test_gpu_blur.py no longer states its tile extents in the form this test reads"
+    row_tx, row_ty, col_tx, col_ty = m.groups()
+    src = open(os.path.join(ROOT, "fpc_diffrend_amd", "csrc", "sep_window.h")).read()
+    assert re.search(rf"ROW_TX = {row_tx}, ROW_TY = {row_ty};", src) and re.search(rf"COL_TX = {col_tx}, COL_TY = {col_ty};", src)

@@ -106,28 +106,17 @@ def test_downsample_has_no_cpu_path():
 
 def test_downsample_kernels_have_no_private_segment():
     """a kernel with a private segment is dispatched several times slower.  Every instance of k_downsample_u8 (one per
-    factor) keeps everything in registers and uses no LDS; read from the built object the way
-    test_bake_kernels_have_no_private_segment reads its kernels'."""
-    import shutil, subprocess, tempfile
-    llvm = "/opt/rocm/lib/llvm/bin"
-    path = os.path.join(ROOT, "fpc_diffrend_amd", "csrc", "_build", "downsample.o")
-    if not (os.path.exists(path) and os.path.exists(os.path.join(llvm, "llvm-readelf"))):
+    factor) keeps everything in registers and uses no LDS; read from the built object (tests/codeobj.py)."""
+    import codeobj
+    recs = codeobj.kernels("downsample.o")
+    if recs is None:
         pytest.skip("no built objects / llvm tools")
-    tmp = tempfile.mkdtemp()
-    try:
-        subprocess.check_call([f"{llvm}/llvm-objcopy", f"--dump-section=.hip_fatbin={tmp}/fb.bin", path], stderr=subprocess.DEVNULL)
-        subprocess.check_call([f"{llvm}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                               f"--input={tmp}/fb.bin", f"--output={tmp}/dev.co", "--unbundle"], stderr=subprocess.DEVNULL)
-        notes = subprocess.check_output([f"{llvm}/llvm-readelf", "--notes", f"{tmp}/dev.co"], text=True)
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     seen = set()
-    for blk in re.split(r"\n\s*- \.agpr_count", notes)[1:]:
-        name = re.search(r"\.name:\s*(\S+)", blk).group(1)
+    for name, private, lds in recs:
         if "k_downsample_u8" in name:
             seen.add(name)
-            assert int(re.search(r"\.private_segment_fixed_size:\s*(\d+)", blk).group(1)) == 0, name
-            assert int(re.search(r"\.group_segment_fixed_size:\s*(\d+)", blk).group(1)) == 0, name
+            assert private == 0, name
+            assert lds == 0, name
     assert len(seen) == len(FACTORS), seen
 
 

@@ -33,7 +33,7 @@ import fitstep_ref as R
 
 pytestmark = pytest.mark.gpu
 
-# the tile extents of csrc/blur.hip (ROW_TX x ROW_TY pixels x rows in the row passes, COL_TX x COL_TY flat columns x rows in the
+# the tile extents of csrc/sep_window.h (ROW_TX x ROW_TY pixels x rows in the row passes, COL_TX x COL_TY flat columns x rows in the
 # column passes): one case each with W, and with H, one below, at and one above an extent
 ROW_TX, ROW_TY = 256, 4
 COL_TX, COL_TY = 64, 64

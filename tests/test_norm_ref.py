@@ -110,7 +110,7 @@ def test_norm_shapes_cover_the_tile_extents():
     assert {N.ROW_TY - 1, N.ROW_TY, N.ROW_TY + 1} <= hs
     assert {N.COL_TX // 4 - 1, N.COL_TX // 4, N.COL_TX // 4 + 1} <= ws and {N.COL_TX // 2 - 1, N.COL_TX // 2, N.COL_TX // 2 + 1} <= ws
     assert any(s[3] == 2 for s in N.ALL_SHAPES)
-    src = open(os.path.join(ROOT, "fpc_diffrend_amd", "csrc", "norm.hip")).read()
+    src = open(os.path.join(ROOT, "fpc_diffrend_amd", "csrc", "sep_window.h")).read()
     assert re.search(rf"ROW_TX = {N.ROW_TX}, ROW_TY = {N.ROW_TY};", src) and re.search(rf"COL_TX = {N.COL_TX}, COL_TY = {N.COL_TY};", src)
     colour, cover, ref = N.flat_inputs()
     W = N.FLAT_SHAPE[2]
@@ -212,29 +212,17 @@ def test_bad_arguments_give_an_error_code_before_any_launch():
 
 def test_norm_kernels_have_no_private_segment():
     """the taps are indexed by a runtime radius -- from registers that would be a private segment.  They are read
-    uniformly from the kernel arguments; read from the built object the way test_downsample_kernels_have_no_private_segment reads its
-    kernels'.  LDS: at least four workgroups a CU (160 KiB)."""
-    import shutil
-    import tempfile
-    llvm = "/opt/rocm/lib/llvm/bin"
-    obj = os.path.join(ROOT, "fpc_diffrend_amd", "csrc", "_build", "norm.o")
-    if not (os.path.exists(obj) and os.path.exists(os.path.join(llvm, "llvm-readelf"))):
+    uniformly from the kernel arguments; read from the built object (tests/codeobj.py).  LDS: at least four workgroups a CU (160 KiB)."""
+    import codeobj
+    recs = codeobj.kernels("norm.o")
+    if recs is None:
         pytest.skip("no built objects / llvm tools")
-    tmp = tempfile.mkdtemp()
-    try:
-        subprocess.check_call([f"{llvm}/llvm-objcopy", f"--dump-section=.hip_fatbin={tmp}/fb.bin", obj], stderr=subprocess.DEVNULL)
-        subprocess.check_call([f"{llvm}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                               f"--input={tmp}/fb.bin", f"--output={tmp}/dev.co", "--unbundle"], stderr=subprocess.DEVNULL)
-        notes = subprocess.check_output([f"{llvm}/llvm-readelf", "--notes", f"{tmp}/dev.co"], text=True)
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     seen = set()
-    for blk in re.split(r"\n\s*- \.agpr_count", notes)[1:]:
-        name = re.search(r"\.name:\s*(\S+)", blk).group(1)
+    for name, private, lds in recs:
         if "k_norm_" in name:
             seen.add(name)
-            assert int(re.search(r"\.private_segment_fixed_size:\s*(\d+)", blk).group(1)) == 0, name
-            assert int(re.search(r"\.group_segment_fixed_size:\s*(\d+)", blk).group(1)) <= 160 * 1024 // 4, name
+            assert private == 0, name
+            assert lds <= 160 * 1024 // 4, name
     assert len(seen) == 5, seen              # rows, cols<false>, cols<true>, point, rows_adj
 
 

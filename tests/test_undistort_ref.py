@@ -151,27 +151,15 @@ def test_undistortion_has_no_cpu_path(tmp_path):
 
 def test_undistort_kernel_has_no_private_segment():
     """a kernel with a private segment is dispatched several times slower.  k_undistort_u8 keeps its 16 results in
-    four packed registers; read from the built object the way test_fit_loop_kernels_have_no_private_segment reads the fit loop's."""
-    import re, shutil, subprocess, tempfile
-    llvm = "/opt/rocm/lib/llvm/bin"
-    path = os.path.join(ROOT, "fpc_diffrend_amd", "csrc", "_build", "undistort.o")
-    if not (os.path.isdir(os.path.dirname(path)) and os.path.exists(os.path.join(llvm, "llvm-readelf"))):
+    four packed registers; read from the built object (tests/codeobj.py)."""
+    import codeobj
+    recs = codeobj.kernels("undistort.o")
+    if recs is None:
         pytest.skip("no built objects / llvm tools")
-    if not os.path.exists(path):
-        pytest.skip("objects not built")
-    tmp = tempfile.mkdtemp()
-    try:
-        subprocess.check_call([f"{llvm}/llvm-objcopy", f"--dump-section=.hip_fatbin={tmp}/fb.bin", path], stderr=subprocess.DEVNULL)
-        subprocess.check_call([f"{llvm}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                               f"--input={tmp}/fb.bin", f"--output={tmp}/dev.co", "--unbundle"], stderr=subprocess.DEVNULL)
-        notes = subprocess.check_output([f"{llvm}/llvm-readelf", "--notes", f"{tmp}/dev.co"], text=True)
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     seen = 0
-    for blk in re.split(r"\n\s*- \.agpr_count", notes)[1:]:
-        name = re.search(r"\.name:\s*(\S+)", blk).group(1)
+    for name, private, lds in recs:
         if "k_undistort_u8" in name:
             seen += 1
-            assert int(re.search(r"\.private_segment_fixed_size:\s*(\d+)", blk).group(1)) == 0, name
-            assert int(re.search(r"\.group_segment_fixed_size:\s*(\d+)", blk).group(1)) == 0, name
+            assert private == 0, name
+            assert lds == 0, name
     assert seen == 1
