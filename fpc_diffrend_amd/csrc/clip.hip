@@ -150,34 +150,37 @@ __global__ void __launch_bounds__(256) k_clip_bwd_both(const float *__restrict__
 //   mode 0 (forward):   out[f][v] = inv_deg[v] * sum_n x[f][n] - x[f][v]            (L x,   L = D^-1 A - I)
 //   mode 1 (backward):  out[f][v] = sum_n inv_deg[n] * x[f][n] - x[f][v]            (L^T x, L^T = A D^-1 - I)
 // nbr [V,D] holds neighbour indices, entries >= V are padding.  Both directions are gathers: no atomics.
-// One vertex's ring sum: sum over the ring of w_n * fetch(n), w_n = inv_deg[n] (mode 1) or 1 (mode 0).
-// slot-major table: consecutive threads read consecutive entries; a vertex's ring is stored front to back, so the
+// ring_walk: one vertex's ring, acc[i] = sum over the ring's slots d (neighbour n) of term(owner, d, n, in, c)[i].  `owner` is the vertex
+// whose ring slot d belongs to (the calling lane's own in the unrolled part, the heavy vertex's in the wave part below), so a term may
+// read per-slot tables [D,V] and the owner's own data; `in` = the slot holds a neighbour -- a pad slot is handed a valid index and must
+// give zeros.
+// Slot-major table: consecutive threads read consecutive entries; a vertex's ring is stored front to back, so the
 // first pad ends it (a UV sphere has two poles of degree ~100 among vertices of degree 6).  Eight slots are
 // fetched together and their neighbours gathered together: the kernel is a chain of dependent loads otherwise
 // (one slot per trip is ~100 dependent round trips for the two pole threads, 40 us of a launch whose other threads are done after 3).
 // Rings longer than the first eight slots (a pole, the centre of a fan) are finished by the WHOLE WAVE, one such vertex at a time: lane l
-// takes slots 8 + l, 72 + l, ..., three DPP sums hand the result to the owner.  (Left to its own thread a ring of 150 is 19 dependent
+// takes slots 8 + l, 72 + l, ..., N DPP sums hand the result to the owner.  (Left to its own thread a ring of 150 is 19 dependent
 // rounds of index load + gather, ~40 us during which the launch's other 480 k threads have long finished.)  Every lane of the wave must
 // call this, `ok` = the lane has a vertex.
-template <typename Fetch>
-__device__ __forceinline__ void ring_sum(const int32_t *__restrict__ nbr, const float *__restrict__ inv_deg, int V, int D, int mode, int v, bool ok,
-                                         Fetch fetch, float &sx, float &sy, float &sz) {
+template <int N, typename Term>
+__device__ __forceinline__ void ring_walk(const int32_t *__restrict__ nbr, int V, int D, int v, bool ok, Term term, float (&acc)[N]) {
     constexpr int U = 8;
-    sx = 0.f; sy = 0.f; sz = 0.f;
+#pragma unroll
+    for (int i = 0; i < N; ++i) acc[i] = 0.f;
     int nb[U];
 #pragma unroll
     for (int d = 0; d < U; ++d) nb[d] = (ok && d < D) ? nbr[(size_t)d * V + v] : V;
     {
-        float wgt[U], gx[U], gy[U], gz[U];
+        float c[U][N];
 #pragma unroll
         for (int d = 0; d < U; ++d) {
             const bool in = nb[d] < V;
-            const int n = in ? nb[d] : (ok ? v : 0);
-            wgt[d] = in ? (mode ? inv_deg[n] : 1.0f) : 0.0f;
-            fetch(n, gx[d], gy[d], gz[d]);
+            term(ok ? v : 0, d, in ? nb[d] : (ok ? v : 0), in, c[d]);
         }
 #pragma unroll
-        for (int d = 0; d < U; ++d) { sx += wgt[d] * gx[d]; sy += wgt[d] * gy[d]; sz += wgt[d] * gz[d]; }
+        for (int d = 0; d < U; ++d)
+#pragma unroll
+            for (int i = 0; i < N; ++i) acc[i] += c[d][i];
     }
     const int lane = threadIdx.x & 63;
     unsigned long long heavy = __ballot(D > U && nb[U - 1] < V);
@@ -185,33 +188,53 @@ __device__ __forceinline__ void ring_sum(const int32_t *__restrict__ nbr, const 
         const int leader = __builtin_ctzll(heavy);
         heavy &= heavy - 1;
         const int hv = __shfl(v, leader, 64);
-        float px = 0.f, py = 0.f, pz = 0.f;
+        float p[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) p[i] = 0.f;
         for (int d = U + lane; d < D; d += 64) {
             const int n = nbr[(size_t)d * V + hv];
             if (n < V) {
-                const float w = mode ? inv_deg[n] : 1.0f;
-                float gx, gy, gz;
-                fetch(n, gx, gy, gz);
-                px += w * gx; py += w * gy; pz += w * gz;
+                float c[N];
+                term(hv, d, n, true, c);
+#pragma unroll
+                for (int i = 0; i < N; ++i) p[i] += c[i];
             }
         }
-        px = wave_sum_dpp(px); py = wave_sum_dpp(py); pz = wave_sum_dpp(pz);
-        if (lane == leader) { sx += px; sy += py; sz += pz; }
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const float t = wave_sum_dpp(p[i]);
+            if (lane == leader) acc[i] += t;
+        }
     }
 }
 
+// The Laplacian's use of the walk: sum over the ring of w_n * fetch(n), w_n = inv_deg[n] (mode 1) or 1 (mode 0).
+template <typename Fetch>
+__device__ __forceinline__ void ring_sum(const int32_t *__restrict__ nbr, const float *__restrict__ inv_deg, int V, int D, int mode, int v, bool ok,
+                                         Fetch fetch, float &sx, float &sy, float &sz) {
+    float acc[3];
+    ring_walk<3>(nbr, V, D, v, ok, [&](int, int, int n, bool in, float (&c)[3]) {
+        const float w = in ? (mode ? inv_deg[n] : 1.0f) : 0.0f;
+        float gx, gy, gz;
+        fetch(n, gx, gy, gz);
+        c[0] = w * gx; c[1] = w * gy; c[2] = w * gz;
+    }, acc);
+    sx = acc[0]; sy = acc[1]; sz = acc[2];
+}
+
+// (MODE is a template argument: as a kernel argument the unrolled ring walk branched on it slot by slot)
+template <int MODE>
 __global__ void __launch_bounds__(256) k_lap_gather(const float *__restrict__ x, const int32_t *__restrict__ nbr,
-                                                    const float *__restrict__ inv_deg, int V, int D, int mode,
-                                                    float *__restrict__ out) {
+                                                    const float *__restrict__ inv_deg, int V, int D, float *__restrict__ out) {
     const int f = blockIdx.y;
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     const bool ok = v < V;
     const float *xf = x + (size_t)f * V * 3;
     float sx, sy, sz;
-    ring_sum(nbr, inv_deg, V, D, mode, v, ok, [&](int n, float &a, float &b, float &c) { a = xf[3 * n]; b = xf[3 * n + 1]; c = xf[3 * n + 2]; },
+    ring_sum(nbr, inv_deg, V, D, MODE, v, ok, [&](int n, float &a, float &b, float &c) { a = xf[3 * n]; b = xf[3 * n + 1]; c = xf[3 * n + 2]; },
              sx, sy, sz);
     if (!ok) return;
-    const float s = mode ? 1.0f : inv_deg[v];
+    const float s = MODE ? 1.0f : inv_deg[v];
     float *o = out + ((size_t)f * V + v) * 3;
     o[0] = s * sx - xf[3 * v]; o[1] = s * sy - xf[3 * v + 1]; o[2] = s * sz - xf[3 * v + 2];
 }
@@ -224,8 +247,11 @@ __global__ void __launch_bounds__(256) k_lap_gather(const float *__restrict__ x,
 // stores per_f for the backward and zeroes the accumulators for the next call.  (r3 let the last workgroup to finish do that behind
 // a ticket counter with relaxed atomics: correct on gfx950, where agent-scope read-modify-writes execute at the memory side, but
 // not by the memory model; a release fence per workgroup writes the XCD's whole L2 back and slowed a concurrent store stream 4x.)
+// REST: the term measures against a rest shape, d = L x - rest_lap (rest_lap [V,3] = L x_rest, made once by this very kernel without
+// REST, so that d is exactly 0 at x = x_rest); `lap` then holds d, which the backward kernel takes as it takes L x.
+template <bool REST>
 __global__ void __launch_bounds__(256) k_lap_penalty_fwd(const float *__restrict__ x, const int32_t *__restrict__ nbr,
-                                                         const float *__restrict__ inv_deg, int F, int V, int D,
+                                                         const float *__restrict__ inv_deg, const float *__restrict__ rest_lap, int F, int V, int D,
                                                          float *__restrict__ lap, double *__restrict__ acc) {
     __shared__ double s_part[4];
     const int f = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -237,7 +263,8 @@ __global__ void __launch_bounds__(256) k_lap_penalty_fwd(const float *__restrict
              sx, sy, sz);
     if (v < V) {
         const float s = inv_deg[v];
-        const float lx = s * sx - xf[3 * v], ly = s * sy - xf[3 * v + 1], lz = s * sz - xf[3 * v + 2];
+        float lx = s * sx - xf[3 * v], ly = s * sy - xf[3 * v + 1], lz = s * sz - xf[3 * v + 2];
+        if (REST) { lx -= rest_lap[3 * v]; ly -= rest_lap[3 * v + 1]; lz -= rest_lap[3 * v + 2]; }
         float *o = lap + ((size_t)f * V + v) * 3;
         o[0] = lx; o[1] = ly; o[2] = lz;
         nrm = sqrtf(lx * lx + ly * ly + lz * lz);
@@ -291,6 +318,61 @@ __global__ void __launch_bounds__(256) k_lap_penalty_bwd(const float *__restrict
     y(v, yx, yy, yz);
     float *o = grad_x + ((size_t)f * V + v) * 3;
     o[0] = sx - yx; o[1] = sy - yy; o[2] = sz - yz;
+}
+
+// The stretch term ("Stretch rule"): every edge's length against its length in a rest shape (rest_len [D,V], aligned with nbr;
+// null: against the constant `target`, the reference's mesh_edge_loss, fit.py:580),
+//   per_f = 1 / (2 E) sum_v sum_d s^2,  s = |x_n - x_v| - l,   value = weight / F * sum_f per_f   (every edge is seen from both ends).
+// Value partials AND the gradient from one walk of the ring: d value / d x_v = coef * sum_d (s / len) (x_v - x_n), coef = 2 weight / (F E),
+// needs v's own ring only -- a gather, no float atomics; a slot of length 0 gives 0, as torch's norm does.  The value goes the way of
+// k_lap_penalty_fwd: one double add per workgroup, the finish kernel behind the kernel boundary.
+__global__ void __launch_bounds__(256) k_stretch_penalty(const float *__restrict__ x, const int32_t *__restrict__ nbr,
+                                                         const float *__restrict__ rest_len, float target, int V, int D, float coef,
+                                                         float *__restrict__ grad_x, double *__restrict__ acc) {
+    __shared__ double s_part[4];
+    const int f = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool ok = v < V;
+    const float *xf = x + (size_t)f * V * 3;
+    float a[4];      // sum_d (s / len) (x_v - x_n), and sum_d s^2
+    ring_walk<4>(nbr, V, D, v, ok, [&](int o, int d, int n, bool in, float (&c)[4]) {
+        const float ex = xf[3 * n] - xf[3 * o], ey = xf[3 * n + 1] - xf[3 * o + 1], ez = xf[3 * n + 2] - xf[3 * o + 2];
+        const float len = sqrtf(ex * ex + ey * ey + ez * ez);
+        const float l = rest_len ? (in ? rest_len[(size_t)d * V + o] : 0.0f) : target;
+        const float s = len - l;
+        const float q = (in && len > 0.0f) ? s / len : 0.0f;
+        c[0] = -(q * ex); c[1] = -(q * ey); c[2] = -(q * ez);
+        c[3] = in ? s * s : 0.0f;
+    }, a);
+    if (ok && grad_x) {
+        float *o = grad_x + ((size_t)f * V + v) * 3;
+        o[0] = coef * a[0]; o[1] = coef * a[1]; o[2] = coef * a[2];
+    }
+    const float ws = wave_sum_dpp(a[3]);      // (a lane without a vertex has no slot: 0)
+    if (lane == 0) s_part[wave] = (double)ws;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        __hip_atomic_fetch_add(&acc[f], s_part[0] + s_part[1] + s_part[2] + s_part[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// per_f, the value, and the accumulators zeroed for the next call (the contract of k_lap_penalty_finish); E = 0: everything 0
+__global__ void __launch_bounds__(256) k_stretch_finish(double *__restrict__ acc, int F, int E, float weight, float *__restrict__ per,
+                                                        float *__restrict__ out) {
+    __shared__ double s_tot[256];
+    double tot = 0.0;
+    for (int i = threadIdx.x; i < F; i += blockDim.x) {
+        const double p = E > 0 ? acc[i] / (2.0 * (double)E) : 0.0;
+        per[i] = (float)p;
+        tot += p;
+        acc[i] = 0.0;
+    }
+    s_tot[threadIdx.x] = tot;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if ((int)threadIdx.x < o) s_tot[threadIdx.x] += s_tot[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = (float)((double)weight * s_tot[0] / (double)F);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -503,10 +585,24 @@ extern "C" int fpcdr_laplacian_gather(const float *x, const int32_t *nbr, const 
                                       int32_t D, int32_t transpose, void *stream) {
     FPCDR_REQUIRE(x && nbr && inv_deg && out, "null pointer");
     FPCDR_REQUIRE(F > 0 && V > 0 && D > 0 && F <= 65535, "bad sizes");
-    hipLaunchKernelGGL(k_lap_gather, dim3(fpcdr_cdiv(V, 256), F), dim3(256), 0, (hipStream_t)stream, x, nbr, inv_deg, V, D,
-                       transpose ? 1 : 0, out);
+    if (transpose)
+        hipLaunchKernelGGL(k_lap_gather<1>, dim3(fpcdr_cdiv(V, 256), F), dim3(256), 0, (hipStream_t)stream, x, nbr, inv_deg, V, D, out);
+    else
+        hipLaunchKernelGGL(k_lap_gather<0>, dim3(fpcdr_cdiv(V, 256), F), dim3(256), 0, (hipStream_t)stream, x, nbr, inv_deg, V, D, out);
     FPCDR_CHECK_LAUNCH();
     return FPCDR_OK;
+}
+
+// (both forward entries; rest_lap null: the plain term)
+static void lap_penalty_fwd(const float *x, const int32_t *nbr, const float *inv_deg, const float *rest_lap, float *lap, void *acc, float *per,
+                            float *out, float weight, int32_t F, int32_t V, int32_t D, void *stream) {
+    // acc: F doubles (+ one spare 8-byte slot: the size of earlier ABI versions), zero on entry and zero again when the call has run
+    const dim3 grid(fpcdr_cdiv(V, 256), F);
+    if (rest_lap)
+        hipLaunchKernelGGL(k_lap_penalty_fwd<true>, grid, dim3(256), 0, (hipStream_t)stream, x, nbr, inv_deg, rest_lap, F, V, D, lap, (double *)acc);
+    else
+        hipLaunchKernelGGL(k_lap_penalty_fwd<false>, grid, dim3(256), 0, (hipStream_t)stream, x, nbr, inv_deg, rest_lap, F, V, D, lap, (double *)acc);
+    hipLaunchKernelGGL(k_lap_penalty_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, (double *)acc, F, V, weight, per, out);
 }
 
 extern "C" int fpcdr_laplacian_penalty_fwd(const float *x, const int32_t *nbr, const float *inv_deg, float *lap, void *acc, float *per,
@@ -514,10 +610,31 @@ extern "C" int fpcdr_laplacian_penalty_fwd(const float *x, const int32_t *nbr, c
     FPCDR_REQUIRE(x && nbr && inv_deg && lap && acc && per && out, "null pointer");
     FPCDR_REQUIRE(F > 0 && V > 0 && D > 0 && F <= 65535, "bad sizes");
     FPCDR_REQUIRE(((size_t)acc & 7) == 0, "acc must be 8-byte aligned");
-    // acc: F doubles (+ one spare 8-byte slot: the size of earlier ABI versions), zero on entry and zero again when the call has run
-    hipLaunchKernelGGL(k_lap_penalty_fwd, dim3(fpcdr_cdiv(V, 256), F), dim3(256), 0, (hipStream_t)stream, x, nbr, inv_deg, F, V, D,
-                       lap, (double *)acc);
-    hipLaunchKernelGGL(k_lap_penalty_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, (double *)acc, F, V, weight, per, out);
+    lap_penalty_fwd(x, nbr, inv_deg, nullptr, lap, acc, per, out, weight, F, V, D, stream);
+    FPCDR_CHECK_LAUNCH();
+    return FPCDR_OK;
+}
+
+extern "C" int fpcdr_laplacian_penalty_rest_fwd(const float *x, const int32_t *nbr, const float *inv_deg, const float *rest_lap, float *lap,
+                                                void *acc, float *per, float *out, float weight, int32_t F, int32_t V, int32_t D,
+                                                void *stream) {
+    FPCDR_REQUIRE(x && nbr && inv_deg && lap && acc && per && out, "null pointer");
+    FPCDR_REQUIRE(F > 0 && V > 0 && D > 0 && F <= 65535, "bad sizes");
+    FPCDR_REQUIRE(((size_t)acc & 7) == 0, "acc must be 8-byte aligned");
+    lap_penalty_fwd(x, nbr, inv_deg, rest_lap, lap, acc, per, out, weight, F, V, D, stream);
+    FPCDR_CHECK_LAUNCH();
+    return FPCDR_OK;
+}
+
+extern "C" int fpcdr_stretch_penalty(const float *x, const int32_t *nbr, const float *rest_len, float target, float *grad_x, void *acc,
+                                     float *per, float *out, float weight, int32_t F, int32_t V, int32_t D, int32_t E, void *stream) {
+    FPCDR_REQUIRE(x && nbr && acc && per && out, "null pointer");
+    FPCDR_REQUIRE(F > 0 && V > 0 && D > 0 && F <= 65535 && E >= 0, "bad sizes");
+    FPCDR_REQUIRE(((size_t)acc & 7) == 0, "acc must be 8-byte aligned");
+    const float coef = E > 0 ? 2.0f * weight / ((float)F * (float)E) : 0.0f;
+    hipLaunchKernelGGL(k_stretch_penalty, dim3(fpcdr_cdiv(V, 256), F), dim3(256), 0, (hipStream_t)stream, x, nbr, rest_len, target, V, D, coef,
+                       grad_x, (double *)acc);
+    hipLaunchKernelGGL(k_stretch_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, (double *)acc, F, E, weight, per, out);
     FPCDR_CHECK_LAUNCH();
     return FPCDR_OK;
 }

@@ -424,11 +424,13 @@ class _uniform_laplacian(torch.autograd.Function):
         return _uniform_laplacian._apply(g, nbr, nbr32, inv_deg, True), None, None, None
 
 
-def mesh_laplacian_smoothing(verts, topo, per_mesh=False):
+def mesh_laplacian_smoothing(verts, topo, per_mesh=False, rest=None):
     """Uniform Laplacian smoothing (pytorch3d mesh_laplacian_smoothing(method='uniform'), reference fit.py:581):
     mean_v || mean_{n in N(v)} x_n - x_v || of every mesh of verts [F,V,3]; per_mesh=True returns the [F] values, else
-    their mean."""
+    their mean.  rest (a RestShape): the differentials are measured against the rest shape's, || L x - L x_rest ||."""
     lap = _uniform_laplacian.apply(verts, topo.nbr, topo.nbr32, topo.inv_deg)
+    if rest is not None:
+        lap = lap - rest.lap[None]
     per = lap.norm(dim=2).mean(dim=1)
     return per if per_mesh else per.mean()
 
@@ -439,7 +441,7 @@ class _laplacian_penalty(torch.autograd.Function):
     times the upstream scalar, or as it is with unit (the caller guarantees d loss / d value = 1)."""
 
     @staticmethod
-    def forward(ctx, verts, nbr32, inv_deg, weight, eager=False, unit=False, acc=None):
+    def forward(ctx, verts, nbr32, inv_deg, weight, eager=False, unit=False, acc=None, rest_lap=None):
         if not verts.is_cuda:
             raise RuntimeError("the mesh regularisers run on the GPU only (fpcdr_laplacian_penalty_fwd); there is no CPU fallback")
         x = verts.contiguous()
@@ -453,8 +455,13 @@ class _laplacian_penalty(torch.autograd.Function):
         assert acc.dtype == torch.float64 and acc.numel() >= F + 1 and acc.is_contiguous()
         per = torch.empty(F, dtype=torch.float32, device=x.device)
         out = torch.empty((), dtype=torch.float32, device=x.device)
-        _lib.call("fpcdr_laplacian_penalty_fwd", _ptr(x), _ptr(nbr32), _ptr(inv_deg), _ptr(lap), _ptr(acc), _ptr(per), _ptr(out),
-                  float(weight), F, V, nbr32.shape[0], _stream())
+        if rest_lap is None:
+            _lib.call("fpcdr_laplacian_penalty_fwd", _ptr(x), _ptr(nbr32), _ptr(inv_deg), _ptr(lap), _ptr(acc), _ptr(per), _ptr(out),
+                      float(weight), F, V, nbr32.shape[0], _stream())
+        else:      # lap = L x - L x_rest; the backward kernel takes it as it takes L x
+            assert rest_lap.shape == (V, 3) and rest_lap.dtype == torch.float32 and rest_lap.is_contiguous() and rest_lap.device == x.device
+            _lib.call("fpcdr_laplacian_penalty_rest_fwd", _ptr(x), _ptr(nbr32), _ptr(inv_deg), _ptr(rest_lap), _ptr(lap), _ptr(acc),
+                      _ptr(per), _ptr(out), float(weight), F, V, nbr32.shape[0], _stream())
         gx = None
         if eager:
             gx = torch.empty_like(lap)
@@ -471,13 +478,13 @@ class _laplacian_penalty(torch.autograd.Function):
     def backward(ctx, g):
         if ctx.eager:
             gx, = ctx.saved_tensors
-            return (gx if ctx.unit else gx * g.to(torch.float32)), None, None, None, None, None, None
+            return (gx if ctx.unit else gx * g.to(torch.float32)), None, None, None, None, None, None, None
         lap, nbr32, inv_deg, per = ctx.saved_tensors
         F, V, _ = lap.shape
         gx = torch.empty_like(lap)
         _lib.call("fpcdr_laplacian_penalty_bwd", _ptr(lap), _ptr(nbr32), _ptr(inv_deg), _ptr(per), _ptr(g.to(torch.float32).contiguous()),
                   _ptr(gx), ctx.weight, F, V, nbr32.shape[0], _stream())
-        return gx, None, None, None, None, None, None
+        return gx, None, None, None, None, None, None, None
 
 
 _unit_scalars = {}
@@ -491,12 +498,98 @@ def _unit_scalar(dev):
     return t
 
 
-def laplacian_penalty(verts, topo, weight, eager_grad=False, unit_upstream=False, acc=None):
+def laplacian_penalty(verts, topo, weight, eager_grad=False, unit_upstream=False, acc=None, rest=None):
     """weight * mean over the meshes of verts [F,V,3] of mesh_laplacian_smoothing(mesh)^2 -- the reference's term (fit.py:581 squares
     the value of the ONE mesh of its step) -- as two launches per step instead of a gather and fifteen torch kernels.
     eager_grad: the gradient is computed with the value (backward() only multiplies by the upstream scalar, or not at all with
-    unit_upstream).  acc: see _laplacian_penalty.forward."""
-    return _laplacian_penalty.apply(verts, topo.nbr32, topo.inv_deg, weight, eager_grad, unit_upstream, acc)
+    unit_upstream).  acc: see _laplacian_penalty.forward.  rest (a RestShape): the term measures against the rest shape, L x - L x_rest
+    in place of L x ("Rest Laplacian rule"): exactly 0, value and gradient, at the rest shape itself."""
+    return _laplacian_penalty.apply(verts, topo.nbr32, topo.inv_deg, weight, eager_grad, unit_upstream, acc,
+                                    None if rest is None else rest.lap)
+
+
+def rest_edge_lengths(nbr32, v_rest):
+    """rest_len [D,V] float32 for the slot-major one-ring table nbr32 [D,V] (MeshTopology.nbr32): || x_rest[nbr[d][v]] - x_rest[v] ||,
+    formed in float64 on the host from the float32 rest positions [V,3] and rounded once -- both ends of an edge hold the same number;
+    pads 0.  Also the number of edges (sum of the degrees / 2)."""
+    nbr = nbr32.detach().cpu().numpy().astype(np.int64)
+    x = v_rest.detach().to('cpu', torch.float32).reshape(-1, 3).numpy().astype(np.float64)
+    V = x.shape[0]
+    assert nbr.shape[1] == V
+    real = nbr < V
+    d = x[np.where(real, nbr, 0)] - x[None]
+    length = np.where(real, np.sqrt((d * d).sum(axis=2)), 0.0)
+    n_real = int(real.sum())
+    assert n_real % 2 == 0
+    return torch.from_numpy(length.astype(np.float32)), n_real // 2
+
+
+class RestShape:
+    """What the rest-shape regularisers need of a rest mesh, built once: .lap [V,3] = L x_rest, .len [D,V] the rest length of every slot of
+    topo.nbr32, .n_edges.  .lap comes from the device code that forms the term's own L x (fpcdr_laplacian_penalty_rest_fwd without a
+    rest), so that L x - .lap is exactly 0 at the rest shape; on a CPU topology it is None (the Laplacian runs on the GPU only)."""
+
+    def __init__(self, topo, v_rest):
+        dev = topo.nbr32.device
+        x = v_rest.detach().to(torch.float32).reshape(1, -1, 3).contiguous()
+        V, D = x.shape[1], topo.nbr32.shape[0]
+        assert V == topo.n_vertices
+        length, self.n_edges = rest_edge_lengths(topo.nbr32, x)
+        self.len = length.to(dev)
+        self.lap = None
+        if dev.type == 'cuda':
+            x = x.to(dev)
+            lap = torch.empty_like(x)
+            acc = torch.zeros(2, dtype=torch.float64, device=dev)
+            per, out = torch.empty(1, dtype=torch.float32, device=dev), torch.empty((), dtype=torch.float32, device=dev)
+            _lib.call("fpcdr_laplacian_penalty_rest_fwd", _ptr(x), _ptr(topo.nbr32), _ptr(topo.inv_deg), None, _ptr(lap), _ptr(acc),
+                      _ptr(per), _ptr(out), 0.0, 1, V, D, _stream())
+            self.lap = lap[0]
+
+
+class _stretch_penalty(torch.autograd.Function):
+    """weight * mean_f mean_edges (|e| - l)^2 with its gradient from ONE call (fpcdr_stretch_penalty): the kernel that walks a vertex's
+    ring for the value has everything the gradient at that vertex needs, so the gradient for a unit upstream is always made in
+    forward(); backward() multiplies it by the upstream scalar, or hands it over as it is with unit."""
+
+    @staticmethod
+    def forward(ctx, verts, nbr32, rest_len, n_edges, target, weight, unit=False, acc=None):
+        if not verts.is_cuda:
+            raise RuntimeError("the mesh regularisers run on the GPU only (fpcdr_stretch_penalty); there is no CPU fallback")
+        x = verts.contiguous()
+        F, V, _ = x.shape
+        if rest_len is not None:
+            assert rest_len.shape == nbr32.shape and rest_len.dtype == torch.float32 and rest_len.is_contiguous() and rest_len.device == x.device
+        if acc is None:      # F + 1 doubles, zero on entry; the call leaves them zero (see _laplacian_penalty.forward)
+            acc = torch.zeros(F + 1, dtype=torch.float64, device=x.device)
+        assert acc.dtype == torch.float64 and acc.numel() >= F + 1 and acc.is_contiguous()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        per = torch.empty(F, dtype=torch.float32, device=x.device)
+        out = torch.empty((), dtype=torch.float32, device=x.device)
+        _lib.call("fpcdr_stretch_penalty", _ptr(x), _ptr(nbr32), _ptr(rest_len), float(target), _ptr(gx), _ptr(acc), _ptr(per), _ptr(out),
+                  float(weight), F, V, nbr32.shape[0], int(n_edges), _stream())
+        if gx is not None:
+            ctx.save_for_backward(gx)
+        ctx.unit = bool(unit)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        gx, = ctx.saved_tensors
+        return (gx if ctx.unit else gx * g.to(torch.float32)), None, None, None, None, None, None, None
+
+
+def stretch_penalty(verts, topo, weight, rest=None, target=0.0, eager_grad=False, unit_upstream=False, acc=None):
+    """weight * mean over the meshes of verts [F,V,3] and over the edges of (|e| - l)^2 ("Stretch rule"): l the edge's length
+    in `rest` (a RestShape), or the constant `target` without one -- stretch_penalty(v, topo, w, target=0.1) is w * mesh_edge_loss(v, topo, 0.1),
+    the reference's term (fit.py:580).  The modes are laplacian_penalty's: lazy, eager_grad, and eager_grad with unit_upstream (the caller
+    guarantees d loss / d value = 1: backward() hands the gradient buffer over).  The one call makes the gradient with the value in every
+    mode, so lazy and eager_grad differ in nothing but the name.  acc: see _laplacian_penalty.forward."""
+    if rest is None:
+        rest_len, n_edges = None, int(topo.edges.shape[0])
+    else:
+        rest_len, n_edges = rest.len, rest.n_edges
+    return _stretch_penalty.apply(verts, topo.nbr32, rest_len, n_edges, target, weight, bool(eager_grad and unit_upstream), acc)
 
 
 def mesh_normal_consistency(verts, topo):
@@ -705,6 +798,12 @@ class FitConfig:
     weight_laplacian: float = 5000.0
     weight_meshedge: float = 0.0
     weight_normalconsistency: float = 0.0
+    laplacian_relative: bool = False    # the Laplacian term measures against the base mesh's own differentials, || L x - L v_base || in
+                                    # place of || L x || ("Rest Laplacian rule"; the reference's unwired
+                                    # laplacian_regularization, fit.py:292-319): zero, with a zero gradient, at the base mesh, where the
+                                    # plain term pulls towards a flat blob.  Existing weights carry over.  False: nothing changes
+    weight_stretch: float = 0.0     # > 0: every edge is held to its length in the base mesh ("Stretch rule"), value and
+                                    # gradient from one call in front of the objective.  0 = off: nothing changes
     cam_idxs: Sequence[int] = (0, 1, 2, 3, 4, 5, 6, 7, 8)
     mode: str = "prior"
     regularize_correctives: bool = False
@@ -918,6 +1017,9 @@ class Fitter:
         # final shapes (fit.py:457); every rank fills the rows of its own frames, gather_result() joins the shards
         self._result_full = torch.zeros(F, self.v_base.shape[0], dtype=torch.float32, device=dev)
         self._lap_acc = torch.zeros(self.frame_hi - self.frame_lo + 1, dtype=torch.float64, device=dev)   # (fpcdr_laplacian_penalty_fwd leaves it zero)
+        # the base mesh as the rest shape of the regularisers that measure against it, and the stretch term's own accumulators
+        self.rest = RestShape(self.topo, self.v_base) if (cfg.laplacian_relative or cfg.weight_stretch) else None
+        self._str_acc = torch.zeros_like(self._lap_acc) if cfg.weight_stretch else None
         self._result_pending = None
         self.iteration = 0
         self._log_file, self._log_t, self._log_it = None, None, 0
@@ -1322,11 +1424,12 @@ class Fitter:
                            or (cfg.regularize_correctives and cfg.mode == 'combined' and i > cfg.max_iter / 2)
                            or (cfg.regularize_prior and cfg.mode == 'prior'))
         reg = self._zero
+        lap_rest = self.rest if cfg.laplacian_relative else None
         if cfg.weight_meshedge:
             reg = reg + cfg.weight_meshedge * mesh_edge_loss(vtx_pos_split, self.topo, 0.1)
         if cfg.weight_laplacian and not cfg.fused_loss:
             # the reference squares the value of ONE mesh per step (fit.py:581): a batch is the mean of the squares
-            reg = reg + cfg.weight_laplacian * (mesh_laplacian_smoothing(vtx_pos_split, self.topo, per_mesh=True) ** 2).mean()
+            reg = reg + cfg.weight_laplacian * (mesh_laplacian_smoothing(vtx_pos_split, self.topo, per_mesh=True, rest=lap_rest) ** 2).mean()
         if cfg.weight_normalconsistency:
             reg = reg + cfg.weight_normalconsistency * mesh_normal_consistency(vtx_pos_split, self.topo)
         if cfg.regularize_correctives and cfg.mode == 'combined' and i > cfg.max_iter / 2:
@@ -1343,7 +1446,12 @@ class Fitter:
         lap = None
         if cfg.weight_laplacian and cfg.fused_loss:
             lap = laplacian_penalty(vtx_pos_split, self.topo, cfg.weight_laplacian / self.world, eager_grad=True, unit_upstream=True,
-                                    acc=self._lap_acc)
+                                    acc=self._lap_acc, rest=lap_rest)
+        # the stretch term against the base mesh, handed over the same way (one call: its gradient comes with its value)
+        strt = None
+        if cfg.weight_stretch:
+            strt = stretch_penalty(vtx_pos_split, self.topo, cfg.weight_stretch / self.world, rest=self.rest, eager_grad=True,
+                                   unit_upstream=True, acc=self._str_acc)
         self.optimizer.zero_grad(set_to_none=True)
         if one_shot:
             bg_sum = None
@@ -1363,12 +1471,14 @@ class Fitter:
                                      queued_backward=cfg.queued_backward and not self.use_graph,
                                      one_pass=cfg.one_pass, unit_upstream=True, zero_extra=zero_buf,      # (the seeds below are 1)
                                      skip_out=self._skip_cur)
-            self._backward(pix, self._one, reg, lap)
+            self._backward(pix, self._one, reg, lap, strt)
             loss = pix.detach()
             if chain_terms:
                 loss = loss + reg.detach()
             if lap is not None:
                 loss = loss + lap.detach()
+            if strt is not None:
+                loss = loss + strt.detach()
         elif cfg.fused_loss:
             if window is None:
                 sum_sq, g_colour = pixel_loss_fused(colour, rast_out, ref, n_total)
@@ -1376,8 +1486,10 @@ class Fitter:
                 sum_sq, g_colour = pixel_loss_blurred(colour, rast_out, ref, window[1], n_total)
             else:
                 sum_sq, g_colour = pixel_loss_normalised(colour, rast_out, ref, window[1], cfg.norm_eps, n_total)
-            self._backward(colour, g_colour, reg, lap)
+            self._backward(colour, g_colour, reg, lap, strt)
             loss = sum_sq[0].to(torch.float32) / n_total + reg.detach() + (lap.detach() if lap is not None else 0.0)
+            if strt is not None:
+                loss = loss + strt.detach()
         else:
             col = torch.where(rast_out[..., 3:] > 0, colour, self._background)
             # the reference holds its target image as float32 on the GPU (fit.py:531-532); the 8-bit batch is converted once
@@ -1385,6 +1497,8 @@ class Fitter:
                 self._targets_f32 = self.targets.to(torch.float32)
             ref_f = self._take(self._targets_f32.reshape(-1, *self.resolution), 0, rows).reshape(Fb * Nc, *self.resolution, 1)
             loss = torch.mean((ref_f - col * 255) ** 2) / self.world + reg + (lap if lap is not None else 0.0)
+            if strt is not None:
+                loss = loss + strt
             loss.backward()
         self._store_result(frame_ids, vtx_pos.detach())
         return loss.detach()
@@ -1514,7 +1628,9 @@ class Fitter:
                 v = self.vertices(frame_ids, validate=False).reshape(self._n(frame_ids), -1, 3)
                 rec = rec or {"it": i}
                 rec["MEL"] = float(cfg.weight_meshedge * mesh_edge_loss(v, self.topo, 0.1))
-                rec["LAP"] = float(cfg.weight_laplacian * (mesh_laplacian_smoothing(v, self.topo, per_mesh=True) ** 2).mean())
+                lap_rest = self.rest if cfg.laplacian_relative else None
+                rec["LAP"] = float(cfg.weight_laplacian * (mesh_laplacian_smoothing(v, self.topo, per_mesh=True, rest=lap_rest) ** 2).mean())
+                rec["STR"] = float(stretch_penalty(v, self.topo, cfg.weight_stretch, rest=self.rest)) if cfg.weight_stretch else 0.0
                 rec["MNC"] = float(cfg.weight_normalconsistency * mesh_normal_consistency(v, self.topo))
         if rec is None:
             return

@@ -401,6 +401,25 @@ int fpcdr_laplacian_penalty_fwd(const float *x, const int32_t *nbr, const float 
 int fpcdr_laplacian_penalty_bwd(const float *lap, const int32_t *nbr, const float *inv_deg, const float *per, const float *upstream,
                                 float *grad_x, float weight, int32_t F, int32_t V, int32_t D, void *stream);
 
+/* The same term measured against a REST shape ("Rest Laplacian rule"): d = L x_f - rest_lap takes the place of L x_f,
+ *   per[f] = mean_v || d_{f,v} ||,   out[0] = weight / F * sum_f per[f]^2;   lap [F,V,3] receives d, and fpcdr_laplacian_penalty_bwd takes
+ * it unchanged.  rest_lap [V,3] = L x_rest, or NULL: the call IS fpcdr_laplacian_penalty_fwd, bit for bit -- and that is how rest_lap
+ * is made (F = 1, x = x_rest, rest_lap = NULL, read `lap`): the same device code, so that d is exactly 0 at x_f = x_rest.       */
+int fpcdr_laplacian_penalty_rest_fwd(const float *x, const int32_t *nbr, const float *inv_deg, const float *rest_lap /* [V,3] or NULL */,
+                                     float *lap, void *acc, float *per, float *out, float weight, int32_t F, int32_t V, int32_t D,
+                                     void *stream);
+
+/* Edge lengths against their rest lengths ("Stretch rule"), value and gradient in one call (two launches):
+ *   s = || x_n - x_v || - l  for every real slot d of vertex v (n = nbr[d][v]),  l = rest_len[d][v], or `target` when rest_len is NULL
+ *   per[f] = 1 / (2 E) * sum_v sum_d s^2   (every edge is seen from both ends),   out[0] = weight / F * sum_f per[f]
+ *   grad_x [F,V,3] = d out / d x for a unit upstream (overwritten; a slot of length 0 contributes 0), or NULL: value only.
+ * rest_len [D,V] float32, slot-major, aligned entry for entry with nbr, pads 0.  E: the number of edges (sum of the degrees / 2);
+ * E = 0 gives value 0 and gradient 0.  acc: (F + 1) * 8 bytes, 8-byte aligned, ZERO on entry; the call leaves it zero again.
+ * With rest_len = NULL and target = 0.1 this is the reference's mesh_edge_loss(mesh, 0.1) (fit.py:580).                         */
+int fpcdr_stretch_penalty(const float *x, const int32_t *nbr, const float *rest_len /* [D,V] or NULL */, float target,
+                          float *grad_x /* [F,V,3] for unit upstream, or NULL: value only */, void *acc /* F+1 doubles, zero in, zero out */,
+                          float *per, float *out, float weight, int32_t F, int32_t V, int32_t D, int32_t E, void *stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* blend -- V = v_base + Bmat . w     reference fit.py:115-122 (prior), :58-62 (free)            */
 /* ------------------------------------------------------------------------------------------ */
