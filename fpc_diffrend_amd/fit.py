@@ -397,6 +397,73 @@ class MeshTopology:
                            torch.tensor(fs[two + 1], dtype=torch.long, device=device))
         self.nbr = torch.tensor(nbr, dtype=torch.long, device=device)
         self.nbr32 = self.nbr.to(torch.int32).t().contiguous()      # [Dmax, V] slot-major for the gather kernel
+        self._hinge_key, self._hinges = ks[two], None      # (the edges of edge_faces, for hinges())
+
+    def hinges(self):
+        """The bending term's tables ("Bend rule"), built on the first call and kept: (hinge_vtx [4,H] int32, hinge_inc [K,V]
+        int32, H, K) on the topology's device.  The hinges are the edges of edge_faces, in that order."""
+        if self._hinges is None:
+            dev = self.faces.device
+            f0, f1 = (t.cpu().numpy() for t in self.edge_faces)
+            hv = hinge_vertices(self.faces.cpu().numpy(), f0, f1, self._hinge_key // (self.n_vertices + 1),
+                                self._hinge_key % (self.n_vertices + 1))
+            inc = hinge_incidence(hv, self.n_vertices)
+            self._hinges = (torch.from_numpy(hv).to(dev), torch.from_numpy(inc).to(dev), int(hv.shape[1]), int(inc.shape[0]))
+        return self._hinges
+
+
+def hinge_vertices(faces, fa, fb, lo, hi):
+    """hinge_vtx [4,H] int32 (role-major: p0, p1, q0, q1) for the hinges with faces (fa, fb) on the edges {lo, hi}: f0 = the lower face
+    index, p0 -> p1 the edge in the direction f0 runs through it, q0 / q1 the third vertex of f0 / f1; a hinge whose f1 runs through the
+    edge in the same direction (sigma = -1) stores -1 - q1.  numpy, no loop over the hinges."""
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    f0, f1 = np.minimum(fa, fb), np.maximum(fa, fb)
+    ar = np.arange(f0.shape[0])
+
+    def locate(tri):      # the corner k at which the face runs tri[k] -> tri[k + 1] along the edge, either way
+        nxt = tri[:, [1, 2, 0]]
+        on = ((tri == lo[:, None]) & (nxt == hi[:, None])) | ((tri == hi[:, None]) & (nxt == lo[:, None]))
+        k = np.argmax(on, axis=1)
+        return tri[ar, k], tri[ar, (k + 1) % 3], tri[ar, (k + 2) % 3]
+
+    p0, p1, q0 = locate(f[f0])
+    b0, _, q1 = locate(f[f1])
+    q1 = np.where(b0 == p1, q1, -1 - q1)
+    return np.stack([p0, p1, q0, q1]).astype(np.int32).reshape(4, -1)
+
+
+def hinge_incidence(hinge_vtx, n_vertices):
+    """hinge_inc [K,V] int32, slot-major: the hinge corners 4 h + role at every vertex, ascending; pads -1 trailing; K = the largest
+    count over the vertices, at least 1."""
+    hv = np.asarray(hinge_vtx, dtype=np.int64)
+    hv = np.where(hv < 0, -1 - hv, hv)
+    at = hv.T.reshape(-1)                                 # the vertex of corner 4 h + role
+    order = np.argsort(at, kind='stable')
+    counts = np.bincount(at, minlength=n_vertices)
+    K = max(int(counts.max()) if counts.size else 0, 1)
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    sorted_at = at[order]
+    inc = np.full((K, n_vertices), -1, dtype=np.int32)
+    inc[np.arange(order.shape[0]) - starts[sorted_at], sorted_at] = order
+    return inc
+
+
+def hinge_rest_cs(hinge_vtx, v_rest):
+    """rest_cs [2,H] float32 = (cos, sin) of every hinge's dihedral angle in the rest shape, by the Bend rule's expressions in float64 from
+    the float32 rest positions [V,3], rounded once; a hinge degenerate at rest gets (1, 0)."""
+    hv = np.asarray(hinge_vtx, dtype=np.int64)
+    x = v_rest.detach().to('cpu', torch.float32).reshape(-1, 3).numpy().astype(np.float64)
+    sigma = np.where(hv[3] < 0, -1.0, 1.0)[:, None]
+    p0, p1, q0, q1 = x[hv[0]], x[hv[1]], x[hv[2]], x[np.where(hv[3] < 0, -1 - hv[3], hv[3])]
+    e = p1 - p0
+    n0, n1 = np.cross(e, q0 - p0), sigma * np.cross(q1 - p0, e)
+    e2, m0, m1 = (e * e).sum(1), (n0 * n0).sum(1), (n1 * n1).sum(1)
+    live = (e2 > 0) & (m0 > 0) & (m1 > 0)
+    safe = lambda a: np.sqrt(np.where(live, a, 1.0))[:, None]
+    u0, u1, eh = n0 / safe(m0), n1 / safe(m1), e / safe(e2)
+    c = np.where(live, (u0 * u1).sum(1), 1.0)
+    s = np.where(live, (np.cross(u0, u1) * eh).sum(1), 0.0)
+    return torch.from_numpy(np.stack([c, s]).astype(np.float32).reshape(2, -1))
 
 
 class _uniform_laplacian(torch.autograd.Function):
@@ -526,8 +593,9 @@ def rest_edge_lengths(nbr32, v_rest):
 
 class RestShape:
     """What the rest-shape regularisers need of a rest mesh, built once: .lap [V,3] = L x_rest, .len [D,V] the rest length of every slot of
-    topo.nbr32, .n_edges.  .lap comes from the device code that forms the term's own L x (fpcdr_laplacian_penalty_rest_fwd without a
-    rest), so that L x - .lap is exactly 0 at the rest shape; on a CPU topology it is None (the Laplacian runs on the GPU only)."""
+    topo.nbr32, .n_edges, and .bend_cs [2,H] the rest dihedral angles of topo.hinges() (made when first asked for).  .lap comes from the
+    device code that forms the term's own L x (fpcdr_laplacian_penalty_rest_fwd without a rest), so that L x - .lap is exactly 0 at the
+    rest shape; on a CPU topology it is None (the Laplacian runs on the GPU only)."""
 
     def __init__(self, topo, v_rest):
         dev = topo.nbr32.device
@@ -537,6 +605,7 @@ class RestShape:
         length, self.n_edges = rest_edge_lengths(topo.nbr32, x)
         self.len = length.to(dev)
         self.lap = None
+        self._topo, self._x_rest, self._bend_cs = topo, x, None      # (for bend_cs: nothing of it is built until somebody asks)
         if dev.type == 'cuda':
             x = x.to(dev)
             lap = torch.empty_like(x)
@@ -545,6 +614,13 @@ class RestShape:
             _lib.call("fpcdr_laplacian_penalty_rest_fwd", _ptr(x), _ptr(topo.nbr32), _ptr(topo.inv_deg), None, _ptr(lap), _ptr(acc),
                       _ptr(per), _ptr(out), 0.0, 1, V, D, _stream())
             self.lap = lap[0]
+
+    @property
+    def bend_cs(self):
+        """[2,H] float32 (cos, sin) of the rest dihedral angle of every hinge of topo.hinges(), built on first use."""
+        if self._bend_cs is None:
+            self._bend_cs = hinge_rest_cs(self._topo.hinges()[0].cpu().numpy(), self._x_rest).to(self._topo.nbr32.device)
+        return self._bend_cs
 
 
 class _stretch_penalty(torch.autograd.Function):
@@ -590,6 +666,55 @@ def stretch_penalty(verts, topo, weight, rest=None, target=0.0, eager_grad=False
     else:
         rest_len, n_edges = rest.len, rest.n_edges
     return _stretch_penalty.apply(verts, topo.nbr32, rest_len, n_edges, target, weight, bool(eager_grad and unit_upstream), acc)
+
+
+class _bend_penalty(torch.autograd.Function):
+    """weight * mean_f mean_hinges (1 - cos(theta - theta_rest)) with its gradient from ONE call (fpcdr_bend_penalty): a pass over the
+    hinges leaves every corner's gradient in a scratch, a gather sums them per vertex.  As with _stretch_penalty the gradient for a unit
+    upstream is made in forward(); backward() multiplies it by the upstream scalar, or hands it over as it is with unit."""
+
+    @staticmethod
+    def forward(ctx, verts, hinge_vtx, hinge_inc, rest_cs, weight, unit=False, acc=None, scratch=None):
+        if not verts.is_cuda:
+            raise RuntimeError("the mesh regularisers run on the GPU only (fpcdr_bend_penalty); there is no CPU fallback")
+        x = verts.contiguous()
+        F, V, _ = x.shape
+        H, K = hinge_vtx.shape[1], hinge_inc.shape[0]
+        assert hinge_vtx.dtype == torch.int32 and hinge_inc.dtype == torch.int32 and hinge_inc.shape[1] == V and hinge_vtx.device == x.device
+        if rest_cs is not None:
+            assert rest_cs.shape == (2, H) and rest_cs.dtype == torch.float32 and rest_cs.is_contiguous() and rest_cs.device == x.device
+        if acc is None:      # F + 1 doubles, zero on entry; the call leaves them zero (see _laplacian_penalty.forward)
+            acc = torch.zeros(F + 1, dtype=torch.float64, device=x.device)
+        assert acc.dtype == torch.float64 and acc.numel() >= F + 1 and acc.is_contiguous()
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            if scratch is None:      # the corners' gradients, F * H * 12 floats (a caller that keeps one saves the allocation per step)
+                scratch = torch.empty(max(F * H * 12, 1), dtype=torch.float32, device=x.device)
+            assert scratch.dtype == torch.float32 and scratch.numel() >= F * H * 12 and scratch.is_contiguous() and scratch.device == x.device
+        per = torch.empty(F, dtype=torch.float32, device=x.device)
+        out = torch.empty((), dtype=torch.float32, device=x.device)
+        _lib.call("fpcdr_bend_penalty", _ptr(x), _ptr(hinge_vtx), _ptr(rest_cs), _ptr(hinge_inc), _ptr(scratch) if gx is not None else None,
+                  _ptr(gx), _ptr(acc), _ptr(per), _ptr(out), float(weight), F, V, H, K, _stream())
+        if gx is not None:
+            ctx.save_for_backward(gx)
+        ctx.unit = bool(unit)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        gx, = ctx.saved_tensors
+        return (gx if ctx.unit else gx * g.to(torch.float32)), None, None, None, None, None, None, None
+
+
+def bend_penalty(verts, topo, weight, rest=None, eager_grad=False, unit_upstream=False, acc=None, scratch=None):
+    """weight * mean over the meshes of verts [F,V,3] and over the hinges of 1 - cos(theta - theta_rest) ("Bend rule"):
+    theta the signed dihedral angle, theta_rest the hinge's angle in `rest` (a RestShape), or 0 without one -- bend_penalty(v, topo, w) is
+    w * mesh_normal_consistency(v, topo), the reference's term (fit.py:582).  The modes and `acc` are stretch_penalty's.  scratch: a float32
+    buffer of at least F * H * 12 elements for the corners' gradients (None: one is allocated per call)."""
+    hinge_vtx, hinge_inc, _, _ = topo.hinges()
+    return _bend_penalty.apply(verts, hinge_vtx, hinge_inc, None if rest is None else rest.bend_cs, weight,
+                               bool(eager_grad and unit_upstream), acc, scratch)
 
 
 def mesh_normal_consistency(verts, topo):
@@ -803,6 +928,8 @@ class FitConfig:
                                     # laplacian_regularization, fit.py:292-319): zero, with a zero gradient, at the base mesh, where the
                                     # plain term pulls towards a flat blob.  Existing weights carry over.  False: nothing changes
     weight_stretch: float = 0.0     # > 0: every edge is held to its length in the base mesh ("Stretch rule"), value and
+                                    # gradient from one call in front of the objective.  0 = off: nothing changes
+    weight_bend: float = 0.0        # > 0: every hinge is held to its dihedral angle in the base mesh ("Bend rule"), value and
                                     # gradient from one call in front of the objective.  0 = off: nothing changes
     cam_idxs: Sequence[int] = (0, 1, 2, 3, 4, 5, 6, 7, 8)
     mode: str = "prior"
@@ -1018,8 +1145,16 @@ class Fitter:
         self._result_full = torch.zeros(F, self.v_base.shape[0], dtype=torch.float32, device=dev)
         self._lap_acc = torch.zeros(self.frame_hi - self.frame_lo + 1, dtype=torch.float64, device=dev)   # (fpcdr_laplacian_penalty_fwd leaves it zero)
         # the base mesh as the rest shape of the regularisers that measure against it, and the stretch term's own accumulators
-        self.rest = RestShape(self.topo, self.v_base) if (cfg.laplacian_relative or cfg.weight_stretch) else None
+        self.rest = RestShape(self.topo, self.v_base) if (cfg.laplacian_relative or cfg.weight_stretch or cfg.weight_bend) else None
         self._str_acc = torch.zeros_like(self._lap_acc) if cfg.weight_stretch else None
+        # the bending term's accumulators, its tables and the scratch of its corner gradients for the most frames a step takes: all made
+        # here, before any capture
+        self._bnd_acc = self._bnd_scratch = None
+        if cfg.weight_bend:
+            self._bnd_acc = torch.zeros_like(self._lap_acc)
+            n_hinges = self.topo.hinges()[2]
+            assert self.rest.bend_cs.shape == (2, n_hinges)      # (built here, not in the first step)
+            self._bnd_scratch = torch.empty(max((self.frame_hi - self.frame_lo) * n_hinges * 12, 1), dtype=torch.float32, device=dev)
         self._result_pending = None
         self.iteration = 0
         self._log_file, self._log_t, self._log_it = None, None, 0
@@ -1452,6 +1587,11 @@ class Fitter:
         if cfg.weight_stretch:
             strt = stretch_penalty(vtx_pos_split, self.topo, cfg.weight_stretch / self.world, rest=self.rest, eager_grad=True,
                                    unit_upstream=True, acc=self._str_acc)
+        # ... and the bending term against the base mesh
+        bnd = None
+        if cfg.weight_bend:
+            bnd = bend_penalty(vtx_pos_split, self.topo, cfg.weight_bend / self.world, rest=self.rest, eager_grad=True,
+                               unit_upstream=True, acc=self._bnd_acc, scratch=self._bnd_scratch)
         self.optimizer.zero_grad(set_to_none=True)
         if one_shot:
             bg_sum = None
@@ -1471,7 +1611,7 @@ class Fitter:
                                      queued_backward=cfg.queued_backward and not self.use_graph,
                                      one_pass=cfg.one_pass, unit_upstream=True, zero_extra=zero_buf,      # (the seeds below are 1)
                                      skip_out=self._skip_cur)
-            self._backward(pix, self._one, reg, lap, strt)
+            self._backward(pix, self._one, reg, lap, strt, bnd)
             loss = pix.detach()
             if chain_terms:
                 loss = loss + reg.detach()
@@ -1479,6 +1619,8 @@ class Fitter:
                 loss = loss + lap.detach()
             if strt is not None:
                 loss = loss + strt.detach()
+            if bnd is not None:
+                loss = loss + bnd.detach()
         elif cfg.fused_loss:
             if window is None:
                 sum_sq, g_colour = pixel_loss_fused(colour, rast_out, ref, n_total)
@@ -1486,10 +1628,12 @@ class Fitter:
                 sum_sq, g_colour = pixel_loss_blurred(colour, rast_out, ref, window[1], n_total)
             else:
                 sum_sq, g_colour = pixel_loss_normalised(colour, rast_out, ref, window[1], cfg.norm_eps, n_total)
-            self._backward(colour, g_colour, reg, lap, strt)
+            self._backward(colour, g_colour, reg, lap, strt, bnd)
             loss = sum_sq[0].to(torch.float32) / n_total + reg.detach() + (lap.detach() if lap is not None else 0.0)
             if strt is not None:
                 loss = loss + strt.detach()
+            if bnd is not None:
+                loss = loss + bnd.detach()
         else:
             col = torch.where(rast_out[..., 3:] > 0, colour, self._background)
             # the reference holds its target image as float32 on the GPU (fit.py:531-532); the 8-bit batch is converted once
@@ -1499,6 +1643,8 @@ class Fitter:
             loss = torch.mean((ref_f - col * 255) ** 2) / self.world + reg + (lap if lap is not None else 0.0)
             if strt is not None:
                 loss = loss + strt
+            if bnd is not None:
+                loss = loss + bnd
             loss.backward()
         self._store_result(frame_ids, vtx_pos.detach())
         return loss.detach()
@@ -1631,6 +1777,7 @@ class Fitter:
                 lap_rest = self.rest if cfg.laplacian_relative else None
                 rec["LAP"] = float(cfg.weight_laplacian * (mesh_laplacian_smoothing(v, self.topo, per_mesh=True, rest=lap_rest) ** 2).mean())
                 rec["STR"] = float(stretch_penalty(v, self.topo, cfg.weight_stretch, rest=self.rest)) if cfg.weight_stretch else 0.0
+                rec["BND"] = float(bend_penalty(v, self.topo, cfg.weight_bend, rest=self.rest)) if cfg.weight_bend else 0.0
                 rec["MNC"] = float(cfg.weight_normalconsistency * mesh_normal_consistency(v, self.topo))
         if rec is None:
             return

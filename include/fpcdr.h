@@ -420,6 +420,21 @@ int fpcdr_stretch_penalty(const float *x, const int32_t *nbr, const float *rest_
                           float *grad_x /* [F,V,3] for unit upstream, or NULL: value only */, void *acc /* F+1 doubles, zero in, zero out */,
                           float *per, float *out, float weight, int32_t F, int32_t V, int32_t D, int32_t E, void *stream);
 
+/* Dihedral angles against their rest angles ("Bend rule"), value and gradient in one call (three launches):
+ *   t_h = 1 - cos(theta_h - theta_rest_h)  for every hinge h (an edge with exactly two faces),   per[f] = 1 / H * sum_h t_h,
+ *   out[0] = weight / F * sum_f per[f];   a hinge with a zero-length edge or a zero-area face has t = 1 and no gradient.
+ * hinge_vtx [4,H] int32, role-major: p0, p1, q0, q1; a hinge whose two faces run through the edge in the same direction stores -1 - q1.
+ * rest_cs [2,H] float32 = (cos, sin) of the rest angles, or NULL: (1, 0) -- the reference's mesh_normal_consistency (fit.py:582).
+ * hinge_inc [K,V] int32, slot-major: the hinge corners 4 h + role at every vertex, ascending, pads -1 trailing.
+ * grad_x [F,V,3] = d out / d x for a unit upstream (overwritten), summed per vertex in slot order from hinge_grad -- caller-owned scratch
+ * of F * H * 12 floats, laid out [F,4,3,H] (role, component, hinge), which the call leaves filled with the corners' gradients; no float atomics: both are
+ * bit-identical from run to run.  grad_x = NULL: value only, hinge_inc and hinge_grad may be NULL.  H = 0 gives value 0 and gradient 0
+ * (hinge_vtx and hinge_grad may then be NULL).  acc: (F + 1) * 8 bytes, 8-byte aligned, ZERO on entry; the call leaves it zero again. */
+int fpcdr_bend_penalty(const float *x, const int32_t *hinge_vtx, const float *rest_cs /* [2,H] or NULL */, const int32_t *hinge_inc,
+                       float *hinge_grad /* scratch, F*H*12 floats */, float *grad_x /* [F,V,3] for unit upstream, or NULL: value only */,
+                       void *acc /* F+1 doubles, zero in, zero out */, float *per, float *out, float weight, int32_t F, int32_t V,
+                       int32_t H, int32_t K, void *stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* blend -- V = v_base + Bmat . w     reference fit.py:115-122 (prior), :58-62 (free)            */
 /* ------------------------------------------------------------------------------------------ */
