@@ -1,4 +1,4 @@
-// transform_clip for a minibatch, forward and backward, for gfx950 (MI355X).
+// transform_clip for a minibatch, forward and backward, and the chain of matrices in front of it (below), for gfx950 (MI355X).
 //
 // Performs the work of reference src/torch/camera.py:11-23 (`posw @ mvp.T` on homogeneous vertices) for all
 // B = F x Nc images of a step at once: image b = f * Nc + c uses vertex buffer f and matrix b.  The reference (and
@@ -146,235 +146,6 @@ __global__ void __launch_bounds__(256) k_clip_bwd_both(const float *__restrict__
         }
 }
 
-// Uniform-Laplacian gather over a static, padded one-ring table (reference regulariser, fit.py:581 via pytorch3d):
-//   mode 0 (forward):   out[f][v] = inv_deg[v] * sum_n x[f][n] - x[f][v]            (L x,   L = D^-1 A - I)
-//   mode 1 (backward):  out[f][v] = sum_n inv_deg[n] * x[f][n] - x[f][v]            (L^T x, L^T = A D^-1 - I)
-// nbr [V,D] holds neighbour indices, entries >= V are padding.  Both directions are gathers: no atomics.
-// ring_walk: one vertex's ring, acc[i] = sum over the ring's slots d (neighbour n) of term(owner, d, n, in, c)[i].  `owner` is the vertex
-// whose ring slot d belongs to (the calling lane's own in the unrolled part, the heavy vertex's in the wave part below), so a term may
-// read per-slot tables [D,V] and the owner's own data; `in` = the slot holds a neighbour -- a pad slot is handed a valid index and must
-// give zeros.
-// Slot-major table: consecutive threads read consecutive entries; a vertex's ring is stored front to back, so the
-// first pad ends it (a UV sphere has two poles of degree ~100 among vertices of degree 6).  Eight slots are
-// fetched together and their neighbours gathered together: the kernel is a chain of dependent loads otherwise
-// (one slot per trip is ~100 dependent round trips for the two pole threads, 40 us of a launch whose other threads are done after 3).
-// Rings longer than the first eight slots (a pole, the centre of a fan) are finished by the WHOLE WAVE, one such vertex at a time: lane l
-// takes slots 8 + l, 72 + l, ..., N DPP sums hand the result to the owner.  (Left to its own thread a ring of 150 is 19 dependent
-// rounds of index load + gather, ~40 us during which the launch's other 480 k threads have long finished.)  Every lane of the wave must
-// call this, `ok` = the lane has a vertex.
-template <int N, typename Term>
-__device__ __forceinline__ void ring_walk(const int32_t *__restrict__ nbr, int V, int D, int v, bool ok, Term term, float (&acc)[N]) {
-    constexpr int U = 8;
-#pragma unroll
-    for (int i = 0; i < N; ++i) acc[i] = 0.f;
-    int nb[U];
-#pragma unroll
-    for (int d = 0; d < U; ++d) nb[d] = (ok && d < D) ? nbr[(size_t)d * V + v] : V;
-    {
-        float c[U][N];
-#pragma unroll
-        for (int d = 0; d < U; ++d) {
-            const bool in = nb[d] < V;
-            term(ok ? v : 0, d, in ? nb[d] : (ok ? v : 0), in, c[d]);
-        }
-#pragma unroll
-        for (int d = 0; d < U; ++d)
-#pragma unroll
-            for (int i = 0; i < N; ++i) acc[i] += c[d][i];
-    }
-    const int lane = threadIdx.x & 63;
-    unsigned long long heavy = __ballot(D > U && nb[U - 1] < V);
-    while (heavy) {
-        const int leader = __builtin_ctzll(heavy);
-        heavy &= heavy - 1;
-        const int hv = __shfl(v, leader, 64);
-        float p[N];
-#pragma unroll
-        for (int i = 0; i < N; ++i) p[i] = 0.f;
-        for (int d = U + lane; d < D; d += 64) {
-            const int n = nbr[(size_t)d * V + hv];
-            if (n < V) {
-                float c[N];
-                term(hv, d, n, true, c);
-#pragma unroll
-                for (int i = 0; i < N; ++i) p[i] += c[i];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const float t = wave_sum_dpp(p[i]);
-            if (lane == leader) acc[i] += t;
-        }
-    }
-}
-
-// The Laplacian's use of the walk: sum over the ring of w_n * fetch(n), w_n = inv_deg[n] (mode 1) or 1 (mode 0).
-template <typename Fetch>
-__device__ __forceinline__ void ring_sum(const int32_t *__restrict__ nbr, const float *__restrict__ inv_deg, int V, int D, int mode, int v, bool ok,
-                                         Fetch fetch, float &sx, float &sy, float &sz) {
-    float acc[3];
-    ring_walk<3>(nbr, V, D, v, ok, [&](int, int, int n, bool in, float (&c)[3]) {
-        const float w = in ? (mode ? inv_deg[n] : 1.0f) : 0.0f;
-        float gx, gy, gz;
-        fetch(n, gx, gy, gz);
-        c[0] = w * gx; c[1] = w * gy; c[2] = w * gz;
-    }, acc);
-    sx = acc[0]; sy = acc[1]; sz = acc[2];
-}
-
-// (MODE is a template argument: as a kernel argument the unrolled ring walk branched on it slot by slot)
-template <int MODE>
-__global__ void __launch_bounds__(256) k_lap_gather(const float *__restrict__ x, const int32_t *__restrict__ nbr,
-                                                    const float *__restrict__ inv_deg, int V, int D, float *__restrict__ out) {
-    const int f = blockIdx.y;
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool ok = v < V;
-    const float *xf = x + (size_t)f * V * 3;
-    float sx, sy, sz;
-    ring_sum(nbr, inv_deg, V, D, MODE, v, ok, [&](int n, float &a, float &b, float &c) { a = xf[3 * n]; b = xf[3 * n + 1]; c = xf[3 * n + 2]; },
-             sx, sy, sz);
-    if (!ok) return;
-    const float s = MODE ? 1.0f : inv_deg[v];
-    float *o = out + ((size_t)f * V + v) * 3;
-    o[0] = s * sx - xf[3 * v]; o[1] = s * sy - xf[3 * v + 1]; o[2] = s * sz - xf[3 * v + 2];
-}
-
-// The Laplacian term of the reference's objective (fit.py:581: weight * mesh_laplacian_smoothing(mesh)^2, one mesh per step; a batch
-// takes the mean of the squares) as ONE launch each way instead of a gather and a dozen torch kernels:
-//   per_f = mean_v || (L x_f)_v ||,   value = weight / F * sum_f per_f^2.
-// Forward: every workgroup adds its vertices' norms to its mesh's double accumulator (one relaxed device-scope add per workgroup);
-// a one-workgroup kernel behind it -- a kernel boundary orders the adds before its loads, no fence or ticket -- forms the value,
-// stores per_f for the backward and zeroes the accumulators for the next call.  (r3 let the last workgroup to finish do that behind
-// a ticket counter with relaxed atomics: correct on gfx950, where agent-scope read-modify-writes execute at the memory side, but
-// not by the memory model; a release fence per workgroup writes the XCD's whole L2 back and slowed a concurrent store stream 4x.)
-// REST: the term measures against a rest shape, d = L x - rest_lap (rest_lap [V,3] = L x_rest, made once by this very kernel without
-// REST, so that d is exactly 0 at x = x_rest); `lap` then holds d, which the backward kernel takes as it takes L x.
-template <bool REST>
-__global__ void __launch_bounds__(256) k_lap_penalty_fwd(const float *__restrict__ x, const int32_t *__restrict__ nbr,
-                                                         const float *__restrict__ inv_deg, const float *__restrict__ rest_lap, int F, int V, int D,
-                                                         float *__restrict__ lap, double *__restrict__ acc) {
-    __shared__ double s_part[4];
-    const int f = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    float nrm = 0.0f;
-    const float *xf = x + (size_t)f * V * 3;
-    float sx, sy, sz;
-    ring_sum(nbr, inv_deg, V, D, 0, v, v < V, [&](int n, float &a, float &b, float &c) { a = xf[3 * n]; b = xf[3 * n + 1]; c = xf[3 * n + 2]; },
-             sx, sy, sz);
-    if (v < V) {
-        const float s = inv_deg[v];
-        float lx = s * sx - xf[3 * v], ly = s * sy - xf[3 * v + 1], lz = s * sz - xf[3 * v + 2];
-        if (REST) { lx -= rest_lap[3 * v]; ly -= rest_lap[3 * v + 1]; lz -= rest_lap[3 * v + 2]; }
-        float *o = lap + ((size_t)f * V + v) * 3;
-        o[0] = lx; o[1] = ly; o[2] = lz;
-        nrm = sqrtf(lx * lx + ly * ly + lz * lz);
-    }
-    const float ws = wave_sum_dpp(nrm);
-    if (lane == 0) s_part[wave] = (double)ws;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        __hip_atomic_fetch_add(&acc[f], s_part[0] + s_part[1] + s_part[2] + s_part[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__global__ void __launch_bounds__(256) k_lap_penalty_finish(double *__restrict__ acc, int F, int V, float weight, float *__restrict__ per,
-                                                            float *__restrict__ out) {
-    __shared__ double s_tot[256];
-    double tot = 0.0;
-    for (int i = threadIdx.x; i < F; i += blockDim.x) {
-        const double p = acc[i] / (double)V;
-        per[i] = (float)p;
-        tot += p * p;
-        acc[i] = 0.0;
-    }
-    s_tot[threadIdx.x] = tot;
-    __syncthreads();
-    for (int o = 128; o >= 1; o >>= 1) {
-        if ((int)threadIdx.x < o) s_tot[threadIdx.x] += s_tot[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (float)((double)weight * s_tot[0] / (double)F);
-}
-
-// Backward: d value / d x = L^T y,  y_v = c_f * lap_v / ||lap_v||,  c_f = upstream * weight * 2 per_f / (F V)  (0 where lap_v = 0,
-// as torch's norm does); y is formed on the fly from the saved Laplacian inside the transposed gather.
-__global__ void __launch_bounds__(256) k_lap_penalty_bwd(const float *__restrict__ lap, const int32_t *__restrict__ nbr,
-                                                         const float *__restrict__ inv_deg, const float *__restrict__ per,
-                                                         const float *__restrict__ upstream, int F, int V, int D, float weight,
-                                                         float *__restrict__ grad_x) {
-    const int f = blockIdx.y;
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool ok = v < V;
-    const float *lf = lap + (size_t)f * V * 3;
-    const float cf = upstream[0] * weight * 2.0f * per[f] / ((float)F * (float)V);
-    auto y = [&](int n, float &a, float &b, float &c) {
-        const float lx = lf[3 * n], ly = lf[3 * n + 1], lz = lf[3 * n + 2];
-        const float nr = sqrtf(lx * lx + ly * ly + lz * lz);
-        const float s = nr > 0.0f ? cf / nr : 0.0f;
-        a = s * lx; b = s * ly; c = s * lz;
-    };
-    float sx, sy, sz, yx, yy, yz;
-    ring_sum(nbr, inv_deg, V, D, 1, v, ok, y, sx, sy, sz);
-    if (!ok) return;
-    y(v, yx, yy, yz);
-    float *o = grad_x + ((size_t)f * V + v) * 3;
-    o[0] = sx - yx; o[1] = sy - yy; o[2] = sz - yz;
-}
-
-// The stretch term ("Stretch rule"): every edge's length against its length in a rest shape (rest_len [D,V], aligned with nbr;
-// null: against the constant `target`, the reference's mesh_edge_loss, fit.py:580),
-//   per_f = 1 / (2 E) sum_v sum_d s^2,  s = |x_n - x_v| - l,   value = weight / F * sum_f per_f   (every edge is seen from both ends).
-// Value partials AND the gradient from one walk of the ring: d value / d x_v = coef * sum_d (s / len) (x_v - x_n), coef = 2 weight / (F E),
-// needs v's own ring only -- a gather, no float atomics; a slot of length 0 gives 0, as torch's norm does.  The value goes the way of
-// k_lap_penalty_fwd: one double add per workgroup, the finish kernel behind the kernel boundary.
-__global__ void __launch_bounds__(256) k_stretch_penalty(const float *__restrict__ x, const int32_t *__restrict__ nbr,
-                                                         const float *__restrict__ rest_len, float target, int V, int D, float coef,
-                                                         float *__restrict__ grad_x, double *__restrict__ acc) {
-    __shared__ double s_part[4];
-    const int f = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool ok = v < V;
-    const float *xf = x + (size_t)f * V * 3;
-    float a[4];      // sum_d (s / len) (x_v - x_n), and sum_d s^2
-    ring_walk<4>(nbr, V, D, v, ok, [&](int o, int d, int n, bool in, float (&c)[4]) {
-        const float ex = xf[3 * n] - xf[3 * o], ey = xf[3 * n + 1] - xf[3 * o + 1], ez = xf[3 * n + 2] - xf[3 * o + 2];
-        const float len = sqrtf(ex * ex + ey * ey + ez * ez);
-        const float l = rest_len ? (in ? rest_len[(size_t)d * V + o] : 0.0f) : target;
-        const float s = len - l;
-        const float q = (in && len > 0.0f) ? s / len : 0.0f;
-        c[0] = -(q * ex); c[1] = -(q * ey); c[2] = -(q * ez);
-        c[3] = in ? s * s : 0.0f;
-    }, a);
-    if (ok && grad_x) {
-        float *o = grad_x + ((size_t)f * V + v) * 3;
-        o[0] = coef * a[0]; o[1] = coef * a[1]; o[2] = coef * a[2];
-    }
-    const float ws = wave_sum_dpp(a[3]);      // (a lane without a vertex has no slot: 0)
-    if (lane == 0) s_part[wave] = (double)ws;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        __hip_atomic_fetch_add(&acc[f], s_part[0] + s_part[1] + s_part[2] + s_part[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// per_f, the value, and the accumulators zeroed for the next call (the contract of k_lap_penalty_finish); E = 0: everything 0
-__global__ void __launch_bounds__(256) k_stretch_finish(double *__restrict__ acc, int F, int E, float weight, float *__restrict__ per,
-                                                        float *__restrict__ out) {
-    __shared__ double s_tot[256];
-    double tot = 0.0;
-    for (int i = threadIdx.x; i < F; i += blockDim.x) {
-        const double p = E > 0 ? acc[i] / (2.0 * (double)E) : 0.0;
-        per[i] = (float)p;
-        tot += p;
-        acc[i] = 0.0;
-    }
-    s_tot[threadIdx.x] = tot;
-    __syncthreads();
-    for (int o = 128; o >= 1; o >>= 1) {
-        if ((int)threadIdx.x < o) s_tot[threadIdx.x] += s_tot[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (float)((double)weight * s_tot[0] / (double)F);
-}
-
 // ---------------------------------------------------------------------------------------------
 // mvp[f,c] = P_c . Rt(q_f, t_f) . (Rt(q_c, t_c) . MV_c)      reference fit.py:541-553, camera.py:117-132 and
 // roma.unitquat_to_rotmat (XYZW, applied WITHOUT normalisation, as the reference does after its whole-tensor
@@ -452,58 +223,30 @@ __device__ __forceinline__ void rigid_bwd(const float *q, const M4 &G, float *gq
     atomicAdd(gt + 0, g[0][3]); atomicAdd(gt + 1, g[1][3]); atomicAdd(gt + 2, g[2][3]);
 }
 
-__global__ void k_mvp_fwd(const float *__restrict__ proj, const float *__restrict__ t_mv, const float *__restrict__ q_cam,
-                          const float *__restrict__ t_cam, const float *__restrict__ q_frame, const float *__restrict__ t_frame,
-                          int Fb, int Nc, float *__restrict__ mvp) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= Fb * Nc) return;
-    const int f = i / Nc, c = i - f * Nc;
-    const M4 B = m4_mul(rigid(q_cam + 4 * c, t_cam + 3 * c), m4_load(t_mv + 16 * c));
-    const M4 X = m4_mul(rigid(q_frame + 4 * f, t_frame + 3 * f), B);
-    const M4 M = m4_mul(m4_load(proj + 16 * c), X);
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) mvp[(size_t)i * 16 + 4 * r + k] = M.m[r][k];
-}
-
-__global__ void k_mvp_bwd(const float *__restrict__ proj, const float *__restrict__ t_mv, const float *__restrict__ q_cam,
-                          const float *__restrict__ t_cam, const float *__restrict__ q_frame, const float *__restrict__ t_frame,
-                          const float *__restrict__ g_mvp, int Fb, int Nc, float *__restrict__ gq_cam, float *__restrict__ gt_cam,
-                          float *__restrict__ gq_frame, float *__restrict__ gt_frame) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= Fb * Nc) return;
-    const int f = i / Nc, c = i - f * Nc;
-    const M4 MV = m4_load(t_mv + 16 * c);
-    const M4 B = m4_mul(rigid(q_cam + 4 * c, t_cam + 3 * c), MV);
-    const M4 A = rigid(q_frame + 4 * f, t_frame + 3 * f);
-    const M4 gX = m4_mul_tn(m4_load(proj + 16 * c), m4_load(g_mvp + (size_t)i * 16));   // P^T dL/dM
-    const M4 gA = m4_mul_nt(gX, B);                                                       // dL/dX B^T
-    const M4 gC = m4_mul_nt(m4_mul_tn(A, gX), MV);                                        // (A^T dL/dX) MV^T
-    rigid_bwd(q_frame + 4 * f, gA, gq_frame + 4 * f, gt_frame + 3 * f);
-    rigid_bwd(q_cam + 4 * c, gC, gq_cam + 4 * c, gt_cam + 3 * c);
-}
-
-// The same with the frames / views of the step given as INDEX arrays into the full parameter tables (the reference's run shape draws one
-// random (camera, frame) per step: as torch ops that was seven index_select launches forward and four zero-fill + index_add pairs backward
-// around kernels that take 3 us).  frame_idx [Fb] or null (frames 0 .. Fb - 1); view_idx [Nc] or null: rows of proj / t_mv; cam_of_view
-// [views] or null: row of q_cam / t_cam for a view (the cameras a Fitter was given).  The backward adds into the FULL tables (zeroed by
-// the caller); two step entries that name the same row add into it, as index_select's backward does.
+// The rows of the parameter tables that step entry (f, c) reads.  IDX = false: frame f, view c, camera c (the entries without index
+// arrays; the three pointers are null and never read).  IDX = true: the frames / views of the step are given as INDEX arrays into the full
+// parameter tables (the reference's run shape draws one random (camera, frame) per step: as torch ops that was seven index_select launches
+// forward and four zero-fill + index_add pairs backward around kernels that take 3 us).  frame_idx [Fb] or null (frames 0 .. Fb - 1);
+// view_idx [Nc] or null: rows of proj / t_mv; cam_of_view [views] or null: row of q_cam / t_cam for a view (the cameras a Fitter was
+// given).  (A template argument, not a test of the pointers at run time: each form keeps the instruction stream it had as a kernel of its own.)
+template <bool IDX>
 __device__ __forceinline__ void mvp_rows(const long long *frame_idx, const long long *view_idx, const long long *cam_of_view, int f, int c,
                                          int &fr, int &cv, int &cp) {
-    fr = frame_idx ? (int)frame_idx[f] : f;
-    cv = view_idx ? (int)view_idx[c] : c;
-    cp = cam_of_view ? (int)cam_of_view[cv] : cv;
+    fr = (IDX && frame_idx) ? (int)frame_idx[f] : f;
+    cv = (IDX && view_idx) ? (int)view_idx[c] : c;
+    cp = (IDX && cam_of_view) ? (int)cam_of_view[cv] : cv;
 }
-__global__ void k_mvp_fwd_idx(const float *__restrict__ proj, const float *__restrict__ t_mv, const float *__restrict__ q_cam,
-                              const float *__restrict__ t_cam, const float *__restrict__ q_frame, const float *__restrict__ t_frame,
-                              const long long *__restrict__ frame_idx, const long long *__restrict__ view_idx,
-                              const long long *__restrict__ cam_of_view, int Fb, int Nc, float *__restrict__ mvp) {
+
+template <bool IDX>
+__global__ void k_mvp_fwd(const float *__restrict__ proj, const float *__restrict__ t_mv, const float *__restrict__ q_cam,
+                          const float *__restrict__ t_cam, const float *__restrict__ q_frame, const float *__restrict__ t_frame,
+                          const long long *__restrict__ frame_idx, const long long *__restrict__ view_idx,
+                          const long long *__restrict__ cam_of_view, int Fb, int Nc, float *__restrict__ mvp) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Fb * Nc) return;
     const int f = i / Nc, c = i - f * Nc;
     int fr, cv, cp;
-    mvp_rows(frame_idx, view_idx, cam_of_view, f, c, fr, cv, cp);
+    mvp_rows<IDX>(frame_idx, view_idx, cam_of_view, f, c, fr, cv, cp);
     const M4 B = m4_mul(rigid(q_cam + 4 * cp, t_cam + 3 * cp), m4_load(t_mv + 16 * cv));
     const M4 X = m4_mul(rigid(q_frame + 4 * fr, t_frame + 3 * fr), B);
     const M4 M = m4_mul(m4_load(proj + 16 * cv), X);
@@ -512,22 +255,26 @@ __global__ void k_mvp_fwd_idx(const float *__restrict__ proj, const float *__res
 #pragma unroll
         for (int k = 0; k < 4; ++k) mvp[(size_t)i * 16 + 4 * r + k] = M.m[r][k];
 }
-__global__ void k_mvp_bwd_idx(const float *__restrict__ proj, const float *__restrict__ t_mv, const float *__restrict__ q_cam,
-                              const float *__restrict__ t_cam, const float *__restrict__ q_frame, const float *__restrict__ t_frame,
-                              const long long *__restrict__ frame_idx, const long long *__restrict__ view_idx,
-                              const long long *__restrict__ cam_of_view, const float *__restrict__ g_mvp, int Fb, int Nc,
-                              float *__restrict__ gq_cam, float *__restrict__ gt_cam, float *__restrict__ gq_frame, float *__restrict__ gt_frame) {
+
+// The backward adds into the FULL tables (zeroed by the caller); two step entries that name the same row add into it, as index_select's
+// backward does.
+template <bool IDX>
+__global__ void k_mvp_bwd(const float *__restrict__ proj, const float *__restrict__ t_mv, const float *__restrict__ q_cam,
+                          const float *__restrict__ t_cam, const float *__restrict__ q_frame, const float *__restrict__ t_frame,
+                          const long long *__restrict__ frame_idx, const long long *__restrict__ view_idx,
+                          const long long *__restrict__ cam_of_view, const float *__restrict__ g_mvp, int Fb, int Nc,
+                          float *__restrict__ gq_cam, float *__restrict__ gt_cam, float *__restrict__ gq_frame, float *__restrict__ gt_frame) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Fb * Nc) return;
     const int f = i / Nc, c = i - f * Nc;
     int fr, cv, cp;
-    mvp_rows(frame_idx, view_idx, cam_of_view, f, c, fr, cv, cp);
+    mvp_rows<IDX>(frame_idx, view_idx, cam_of_view, f, c, fr, cv, cp);
     const M4 MV = m4_load(t_mv + 16 * cv);
     const M4 B = m4_mul(rigid(q_cam + 4 * cp, t_cam + 3 * cp), MV);
     const M4 A = rigid(q_frame + 4 * fr, t_frame + 3 * fr);
-    const M4 gX = m4_mul_tn(m4_load(proj + 16 * cv), m4_load(g_mvp + (size_t)i * 16));
-    const M4 gA = m4_mul_nt(gX, B);
-    const M4 gC = m4_mul_nt(m4_mul_tn(A, gX), MV);
+    const M4 gX = m4_mul_tn(m4_load(proj + 16 * cv), m4_load(g_mvp + (size_t)i * 16));   // P^T dL/dM
+    const M4 gA = m4_mul_nt(gX, B);                                                       // dL/dX B^T
+    const M4 gC = m4_mul_nt(m4_mul_tn(A, gX), MV);                                        // (A^T dL/dX) MV^T
     rigid_bwd(q_frame + 4 * fr, gA, gq_frame + 4 * fr, gt_frame + 3 * fr);
     rigid_bwd(q_cam + 4 * cp, gC, gq_cam + 4 * cp, gt_cam + 3 * cp);
 }
@@ -539,7 +286,7 @@ extern "C" int fpcdr_mvp_fwd_indexed(const float *proj, const float *t_mv, const
                                      float *mvp, int32_t Fb, int32_t Nc, void *stream) {
     FPCDR_REQUIRE(proj && t_mv && q_cam && t_cam && q_frame && t_frame && mvp, "null pointer");
     FPCDR_REQUIRE(Fb > 0 && Nc > 0, "bad sizes");
-    hipLaunchKernelGGL(k_mvp_fwd_idx, dim3(fpcdr_cdiv((long long)Fb * Nc, 64)), dim3(64), 0, (hipStream_t)stream, proj, t_mv, q_cam, t_cam,
+    hipLaunchKernelGGL(k_mvp_fwd<true>, dim3(fpcdr_cdiv((long long)Fb * Nc, 64)), dim3(64), 0, (hipStream_t)stream, proj, t_mv, q_cam, t_cam,
                        q_frame, t_frame, (const long long *)frame_idx, (const long long *)view_idx, (const long long *)cam_of_view, Fb, Nc, mvp);
     FPCDR_CHECK_LAUNCH();
     return FPCDR_OK;
@@ -552,7 +299,7 @@ extern "C" int fpcdr_mvp_bwd_indexed(const float *proj, const float *t_mv, const
     FPCDR_REQUIRE(proj && t_mv && q_cam && t_cam && q_frame && t_frame && grad_mvp && gq_cam && gt_cam && gq_frame && gt_frame,
                   "null pointer");
     FPCDR_REQUIRE(Fb > 0 && Nc > 0, "bad sizes");
-    hipLaunchKernelGGL(k_mvp_bwd_idx, dim3(fpcdr_cdiv((long long)Fb * Nc, 64)), dim3(64), 0, (hipStream_t)stream, proj, t_mv, q_cam, t_cam,
+    hipLaunchKernelGGL(k_mvp_bwd<true>, dim3(fpcdr_cdiv((long long)Fb * Nc, 64)), dim3(64), 0, (hipStream_t)stream, proj, t_mv, q_cam, t_cam,
                        q_frame, t_frame, (const long long *)frame_idx, (const long long *)view_idx, (const long long *)cam_of_view, grad_mvp,
                        Fb, Nc, gq_cam, gt_cam, gq_frame, gt_frame);
     FPCDR_CHECK_LAUNCH();
@@ -563,8 +310,9 @@ extern "C" int fpcdr_mvp_fwd(const float *proj, const float *t_mv, const float *
                              const float *t_frame, float *mvp, int32_t Fb, int32_t Nc, void *stream) {
     FPCDR_REQUIRE(proj && t_mv && q_cam && t_cam && q_frame && t_frame && mvp, "null pointer");
     FPCDR_REQUIRE(Fb > 0 && Nc > 0, "bad sizes");
-    hipLaunchKernelGGL(k_mvp_fwd, dim3(fpcdr_cdiv((long long)Fb * Nc, 64)), dim3(64), 0, (hipStream_t)stream, proj, t_mv, q_cam,
-                       t_cam, q_frame, t_frame, Fb, Nc, mvp);
+    const long long *none = nullptr;
+    hipLaunchKernelGGL(k_mvp_fwd<false>, dim3(fpcdr_cdiv((long long)Fb * Nc, 64)), dim3(64), 0, (hipStream_t)stream, proj, t_mv, q_cam,
+                       t_cam, q_frame, t_frame, none, none, none, Fb, Nc, mvp);
     FPCDR_CHECK_LAUNCH();
     return FPCDR_OK;
 }
@@ -575,77 +323,9 @@ extern "C" int fpcdr_mvp_bwd(const float *proj, const float *t_mv, const float *
     FPCDR_REQUIRE(proj && t_mv && q_cam && t_cam && q_frame && t_frame && grad_mvp && gq_cam && gt_cam && gq_frame && gt_frame,
                   "null pointer");
     FPCDR_REQUIRE(Fb > 0 && Nc > 0, "bad sizes");
-    hipLaunchKernelGGL(k_mvp_bwd, dim3(fpcdr_cdiv((long long)Fb * Nc, 64)), dim3(64), 0, (hipStream_t)stream, proj, t_mv, q_cam,
-                       t_cam, q_frame, t_frame, grad_mvp, Fb, Nc, gq_cam, gt_cam, gq_frame, gt_frame);
-    FPCDR_CHECK_LAUNCH();
-    return FPCDR_OK;
-}
-
-extern "C" int fpcdr_laplacian_gather(const float *x, const int32_t *nbr, const float *inv_deg, float *out, int32_t F, int32_t V,
-                                      int32_t D, int32_t transpose, void *stream) {
-    FPCDR_REQUIRE(x && nbr && inv_deg && out, "null pointer");
-    FPCDR_REQUIRE(F > 0 && V > 0 && D > 0 && F <= 65535, "bad sizes");
-    if (transpose)
-        hipLaunchKernelGGL(k_lap_gather<1>, dim3(fpcdr_cdiv(V, 256), F), dim3(256), 0, (hipStream_t)stream, x, nbr, inv_deg, V, D, out);
-    else
-        hipLaunchKernelGGL(k_lap_gather<0>, dim3(fpcdr_cdiv(V, 256), F), dim3(256), 0, (hipStream_t)stream, x, nbr, inv_deg, V, D, out);
-    FPCDR_CHECK_LAUNCH();
-    return FPCDR_OK;
-}
-
-// (both forward entries; rest_lap null: the plain term)
-static void lap_penalty_fwd(const float *x, const int32_t *nbr, const float *inv_deg, const float *rest_lap, float *lap, void *acc, float *per,
-                            float *out, float weight, int32_t F, int32_t V, int32_t D, void *stream) {
-    // acc: F doubles (+ one spare 8-byte slot: the size of earlier ABI versions), zero on entry and zero again when the call has run
-    const dim3 grid(fpcdr_cdiv(V, 256), F);
-    if (rest_lap)
-        hipLaunchKernelGGL(k_lap_penalty_fwd<true>, grid, dim3(256), 0, (hipStream_t)stream, x, nbr, inv_deg, rest_lap, F, V, D, lap, (double *)acc);
-    else
-        hipLaunchKernelGGL(k_lap_penalty_fwd<false>, grid, dim3(256), 0, (hipStream_t)stream, x, nbr, inv_deg, rest_lap, F, V, D, lap, (double *)acc);
-    hipLaunchKernelGGL(k_lap_penalty_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, (double *)acc, F, V, weight, per, out);
-}
-
-extern "C" int fpcdr_laplacian_penalty_fwd(const float *x, const int32_t *nbr, const float *inv_deg, float *lap, void *acc, float *per,
-                                           float *out, float weight, int32_t F, int32_t V, int32_t D, void *stream) {
-    FPCDR_REQUIRE(x && nbr && inv_deg && lap && acc && per && out, "null pointer");
-    FPCDR_REQUIRE(F > 0 && V > 0 && D > 0 && F <= 65535, "bad sizes");
-    FPCDR_REQUIRE(((size_t)acc & 7) == 0, "acc must be 8-byte aligned");
-    lap_penalty_fwd(x, nbr, inv_deg, nullptr, lap, acc, per, out, weight, F, V, D, stream);
-    FPCDR_CHECK_LAUNCH();
-    return FPCDR_OK;
-}
-
-extern "C" int fpcdr_laplacian_penalty_rest_fwd(const float *x, const int32_t *nbr, const float *inv_deg, const float *rest_lap, float *lap,
-                                                void *acc, float *per, float *out, float weight, int32_t F, int32_t V, int32_t D,
-                                                void *stream) {
-    FPCDR_REQUIRE(x && nbr && inv_deg && lap && acc && per && out, "null pointer");
-    FPCDR_REQUIRE(F > 0 && V > 0 && D > 0 && F <= 65535, "bad sizes");
-    FPCDR_REQUIRE(((size_t)acc & 7) == 0, "acc must be 8-byte aligned");
-    lap_penalty_fwd(x, nbr, inv_deg, rest_lap, lap, acc, per, out, weight, F, V, D, stream);
-    FPCDR_CHECK_LAUNCH();
-    return FPCDR_OK;
-}
-
-extern "C" int fpcdr_stretch_penalty(const float *x, const int32_t *nbr, const float *rest_len, float target, float *grad_x, void *acc,
-                                     float *per, float *out, float weight, int32_t F, int32_t V, int32_t D, int32_t E, void *stream) {
-    FPCDR_REQUIRE(x && nbr && acc && per && out, "null pointer");
-    FPCDR_REQUIRE(F > 0 && V > 0 && D > 0 && F <= 65535 && E >= 0, "bad sizes");
-    FPCDR_REQUIRE(((size_t)acc & 7) == 0, "acc must be 8-byte aligned");
-    const float coef = E > 0 ? 2.0f * weight / ((float)F * (float)E) : 0.0f;
-    hipLaunchKernelGGL(k_stretch_penalty, dim3(fpcdr_cdiv(V, 256), F), dim3(256), 0, (hipStream_t)stream, x, nbr, rest_len, target, V, D, coef,
-                       grad_x, (double *)acc);
-    hipLaunchKernelGGL(k_stretch_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, (double *)acc, F, E, weight, per, out);
-    FPCDR_CHECK_LAUNCH();
-    return FPCDR_OK;
-}
-
-extern "C" int fpcdr_laplacian_penalty_bwd(const float *lap, const int32_t *nbr, const float *inv_deg, const float *per,
-                                           const float *upstream, float *grad_x, float weight, int32_t F, int32_t V, int32_t D,
-                                           void *stream) {
-    FPCDR_REQUIRE(lap && nbr && inv_deg && per && upstream && grad_x, "null pointer");
-    FPCDR_REQUIRE(F > 0 && V > 0 && D > 0 && F <= 65535, "bad sizes");
-    hipLaunchKernelGGL(k_lap_penalty_bwd, dim3(fpcdr_cdiv(V, 256), F), dim3(256), 0, (hipStream_t)stream, lap, nbr, inv_deg, per, upstream,
-                       F, V, D, weight, grad_x);
+    const long long *none = nullptr;
+    hipLaunchKernelGGL(k_mvp_bwd<false>, dim3(fpcdr_cdiv((long long)Fb * Nc, 64)), dim3(64), 0, (hipStream_t)stream, proj, t_mv, q_cam,
+                       t_cam, q_frame, t_frame, none, none, none, grad_mvp, Fb, Nc, gq_cam, gt_cam, gq_frame, gt_frame);
     FPCDR_CHECK_LAUNCH();
     return FPCDR_OK;
 }

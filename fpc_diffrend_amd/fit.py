@@ -34,6 +34,10 @@ import torch
 
 from . import _lib, camera
 from . import ops as dr
+from .mesh_reg import (MeshTopology, RestShape, _uniform_laplacian, bend_penalty, hinge_incidence, hinge_rest_cs, hinge_vertices,
+                       laplacian_penalty, mesh_edge_loss, mesh_laplacian_smoothing, mesh_normal_consistency, rest_edge_lengths,
+                       stretch_penalty)
+from .ops import _ptr, _stream
 
 BACKGROUND = 45.0 / 255.0  # reference fit.py:161
 
@@ -41,14 +45,6 @@ BACKGROUND = 45.0 / 255.0  # reference fit.py:161
 # ----------------------------------------------------------------------------------------------
 # V = v_base + Bmat . w   on the f32 matrix cores
 # ----------------------------------------------------------------------------------------------
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
 
 class ZeroPool:
     """Small zero-filled accumulators for the backward kernels of ONE fit step (gradients of the camera matrices, the poses, the blend
@@ -301,445 +297,50 @@ def _check_window_term(cfg, kind, name, graph_why, sigmas):
 
 
 class _mvp_func(torch.autograd.Function):
-    """Model-view-projection matrices of a minibatch in one kernel each way (fpcdr_mvp_fwd / _bwd)."""
+    """Model-view-projection matrices of a minibatch in one kernel each way.  Without index tensors (fpcdr_mvp_fwd / _bwd): every row of
+    q_frame / t_frame is a frame of the step, every row of q_cam / t_cam a view, Fb and Nc are the table shapes.  With any of them
+    (fpcdr_mvp_fwd_indexed / _bwd_indexed) the step names its Fb frames / Nc views by index into the FULL parameter tables: no
+    index_select launches in front, no zero-fill + index_add pairs behind.  frame_idx [Fb] / view_idx [Nc]: int64 device tensors or None;
+    cam_of_view: the Fitter's cam_sel (view -> row of q_cam / t_cam) or None."""
 
     @staticmethod
-    def forward(ctx, q_cam, t_cam, q_frame, t_frame, proj, t_mv, pool=None):
+    def forward(ctx, q_cam, t_cam, q_frame, t_frame, proj, t_mv, frame_idx=None, view_idx=None, cam_of_view=None, Fb=None, Nc=None, pool=None):
         ctx.pool = pool
         q_cam, t_cam, q_frame, t_frame = (a.contiguous() for a in (q_cam, t_cam, q_frame, t_frame))
-        Fb, Nc = q_frame.shape[0], q_cam.shape[0]
-        out = torch.empty(Fb * Nc, 4, 4, dtype=torch.float32, device=q_cam.device)
-        _lib.call("fpcdr_mvp_fwd", _ptr(proj), _ptr(t_mv), _ptr(q_cam), _ptr(t_cam), _ptr(q_frame), _ptr(t_frame), _ptr(out),
-                  Fb, Nc, _stream())
-        ctx.save_for_backward(q_cam, t_cam, q_frame, t_frame, proj, t_mv)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        q_cam, t_cam, q_frame, t_frame, proj, t_mv = ctx.saved_tensors
-        Fb, Nc = q_frame.shape[0], q_cam.shape[0]
-        grads = _pool_zeros(ctx.pool, (7 * (Fb + Nc),), g.device)
-        gq_cam, gt_cam = grads[:4 * Nc].view(Nc, 4), grads[4 * Nc:7 * Nc].view(Nc, 3)
-        gq_frame, gt_frame = grads[7 * Nc:7 * Nc + 4 * Fb].view(Fb, 4), grads[7 * Nc + 4 * Fb:].view(Fb, 3)
-        _lib.call("fpcdr_mvp_bwd", _ptr(proj), _ptr(t_mv), _ptr(q_cam), _ptr(t_cam), _ptr(q_frame), _ptr(t_frame),
-                  _ptr(g.contiguous()), _ptr(gq_cam), _ptr(gt_cam), _ptr(gq_frame), _ptr(gt_frame), Fb, Nc, _stream())
-        return gq_cam, gt_cam, gq_frame, gt_frame, None, None, None
-
-
-class _mvp_indexed_func(torch.autograd.Function):
-    """_mvp_func for a step that names its frames / views by index tensors into the FULL parameter tables (fpcdr_mvp_fwd_indexed /
-    _bwd_indexed): no index_select launches in front, no zero-fill + index_add pairs behind.  frame_idx [Fb] / view_idx [Nc]: int64 device
-    tensors or None; cam_of_view: the Fitter's cam_sel (view -> row of q_cam / t_cam) or None."""
-
-    @staticmethod
-    def forward(ctx, q_cam, t_cam, q_frame, t_frame, proj, t_mv, frame_idx, view_idx, cam_of_view, Fb, Nc, pool=None):
-        ctx.pool = pool
-        q_cam, t_cam, q_frame, t_frame = (a.contiguous() for a in (q_cam, t_cam, q_frame, t_frame))
-        out = torch.empty(Fb * Nc, 4, 4, dtype=torch.float32, device=q_cam.device)
-        _lib.call("fpcdr_mvp_fwd_indexed", _ptr(proj), _ptr(t_mv), _ptr(q_cam), _ptr(t_cam), _ptr(q_frame), _ptr(t_frame), _ptr(frame_idx),
-                  _ptr(view_idx), _ptr(cam_of_view), _ptr(out), Fb, Nc, _stream())
-        ctx.save_for_backward(q_cam, t_cam, q_frame, t_frame, proj, t_mv, *(t for t in (frame_idx, view_idx, cam_of_view) if t is not None))
-        ctx.have = (frame_idx is not None, view_idx is not None, cam_of_view is not None)
+        idx = (frame_idx, view_idx, cam_of_view)
+        ctx.have = tuple(t is not None for t in idx)
+        if not any(ctx.have):
+            Fb, Nc = q_frame.shape[0], q_cam.shape[0]
         ctx.dims = (Fb, Nc)
+        out = torch.empty(Fb * Nc, 4, 4, dtype=torch.float32, device=q_cam.device)
+        tables = (_ptr(proj), _ptr(t_mv), _ptr(q_cam), _ptr(t_cam), _ptr(q_frame), _ptr(t_frame))
+        if any(ctx.have):
+            _lib.call("fpcdr_mvp_fwd_indexed", *tables, *(_ptr(t) for t in idx), _ptr(out), Fb, Nc, _stream())
+        else:
+            _lib.call("fpcdr_mvp_fwd", *tables, _ptr(out), Fb, Nc, _stream())
+        ctx.save_for_backward(q_cam, t_cam, q_frame, t_frame, proj, t_mv, *(t for t in idx if t is not None))
         return out
 
     @staticmethod
     def backward(ctx, g):
         q_cam, t_cam, q_frame, t_frame, proj, t_mv = ctx.saved_tensors[:6]
         rest = list(ctx.saved_tensors[6:])
-        frame_idx, view_idx, cam_of_view = (rest.pop(0) if h else None for h in ctx.have)
+        idx = [rest.pop(0) if h else None for h in ctx.have]
         Fb, Nc = ctx.dims
-        nq, nf = q_cam.shape[0], q_frame.shape[0]
+        nq, nf = q_cam.shape[0], q_frame.shape[0]      # the gradients cover the whole tables (without index tensors: Nc and Fb rows)
         grads = _pool_zeros(ctx.pool, (7 * (nq + nf),), g.device)
         gq_cam, gt_cam = grads[:4 * nq].view(nq, 4), grads[4 * nq:7 * nq].view(nq, 3)
         gq_frame, gt_frame = grads[7 * nq:7 * nq + 4 * nf].view(nf, 4), grads[7 * nq + 4 * nf:].view(nf, 3)
-        _lib.call("fpcdr_mvp_bwd_indexed", _ptr(proj), _ptr(t_mv), _ptr(q_cam), _ptr(t_cam), _ptr(q_frame), _ptr(t_frame), _ptr(frame_idx),
-                  _ptr(view_idx), _ptr(cam_of_view), _ptr(g.contiguous()), _ptr(gq_cam), _ptr(gt_cam), _ptr(gq_frame), _ptr(gt_frame), Fb, Nc,
-                  _stream())
+        tables = (_ptr(proj), _ptr(t_mv), _ptr(q_cam), _ptr(t_cam), _ptr(q_frame), _ptr(t_frame))
+        outs = (_ptr(gq_cam), _ptr(gt_cam), _ptr(gq_frame), _ptr(gt_frame), Fb, Nc, _stream())
+        if any(ctx.have):
+            _lib.call("fpcdr_mvp_bwd_indexed", *tables, *(_ptr(t) for t in idx), _ptr(g.contiguous()), *outs)
+        else:
+            _lib.call("fpcdr_mvp_bwd", *tables, _ptr(g.contiguous()), *outs)
         return (gq_cam, gt_cam, gq_frame, gt_frame) + (None,) * 8
 
 
-# ----------------------------------------------------------------------------------------------
-# mesh regularisers (pytorch3d in the reference: fit.py:16-19, 578-582) -- torch restatement
-# ----------------------------------------------------------------------------------------------
-
-class MeshTopology:
-    """Edges and uniform-Laplacian structure of a triangle list, built once (the reference rebuilds a
-    pytorch3d Meshes object every iteration, fit.py:578)."""
-
-    def __init__(self, faces, n_vertices, device):
-        f = np.asarray(faces, dtype=np.int64)
-        e = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]], axis=0)
-        e = np.unique(np.sort(e, axis=1), axis=0)
-        self.edges = torch.tensor(e, dtype=torch.long, device=device)
-        deg = np.bincount(e.reshape(-1), minlength=n_vertices).astype(np.int64)
-        self.inv_deg = torch.tensor(np.where(deg > 0, 1.0 / np.maximum(deg, 1), 0.0), dtype=torch.float32, device=device)
-        self.n_vertices = n_vertices
-        # padded one-ring table [V, Dmax]; the pad index V points at an all-zero row appended to the vertex buffer
-        dmax = int(deg.max()) if deg.size else 0
-        nbr = np.full((n_vertices, max(dmax, 1)), n_vertices, dtype=np.int64)
-        fill = np.zeros(n_vertices, dtype=np.int64)
-        for a, b in e:
-            nbr[a, fill[a]] = b; fill[a] += 1
-            nbr[b, fill[b]] = a; fill[b] += 1
-        # interior edges (exactly two incident faces) with those faces, for the normal-consistency term
-        self.faces = torch.tensor(f, dtype=torch.long, device=device)
-        fe = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]], axis=0), axis=1)
-        fid = np.tile(np.arange(f.shape[0]), 3)
-        key = fe[:, 0] * (n_vertices + 1) + fe[:, 1]
-        order = np.argsort(key, kind='stable')
-        ks, fs = key[order], fid[order]
-        first = np.concatenate([[True], ks[1:] != ks[:-1]])
-        starts = np.nonzero(first)[0]
-        counts = np.diff(np.concatenate([starts, [len(ks)]]))
-        two = starts[counts == 2]
-        self.edge_faces = (torch.tensor(fs[two], dtype=torch.long, device=device),
-                           torch.tensor(fs[two + 1], dtype=torch.long, device=device))
-        self.nbr = torch.tensor(nbr, dtype=torch.long, device=device)
-        self.nbr32 = self.nbr.to(torch.int32).t().contiguous()      # [Dmax, V] slot-major for the gather kernel
-        self._hinge_key, self._hinges = ks[two], None      # (the edges of edge_faces, for hinges())
-
-    def hinges(self):
-        """The bending term's tables ("Bend rule"), built on the first call and kept: (hinge_vtx [4,H] int32, hinge_inc [K,V]
-        int32, H, K) on the topology's device.  The hinges are the edges of edge_faces, in that order."""
-        if self._hinges is None:
-            dev = self.faces.device
-            f0, f1 = (t.cpu().numpy() for t in self.edge_faces)
-            hv = hinge_vertices(self.faces.cpu().numpy(), f0, f1, self._hinge_key // (self.n_vertices + 1),
-                                self._hinge_key % (self.n_vertices + 1))
-            inc = hinge_incidence(hv, self.n_vertices)
-            self._hinges = (torch.from_numpy(hv).to(dev), torch.from_numpy(inc).to(dev), int(hv.shape[1]), int(inc.shape[0]))
-        return self._hinges
-
-
-def hinge_vertices(faces, fa, fb, lo, hi):
-    """hinge_vtx [4,H] int32 (role-major: p0, p1, q0, q1) for the hinges with faces (fa, fb) on the edges {lo, hi}: f0 = the lower face
-    index, p0 -> p1 the edge in the direction f0 runs through it, q0 / q1 the third vertex of f0 / f1; a hinge whose f1 runs through the
-    edge in the same direction (sigma = -1) stores -1 - q1.  numpy, no loop over the hinges."""
-    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
-    f0, f1 = np.minimum(fa, fb), np.maximum(fa, fb)
-    ar = np.arange(f0.shape[0])
-
-    def locate(tri):      # the corner k at which the face runs tri[k] -> tri[k + 1] along the edge, either way
-        nxt = tri[:, [1, 2, 0]]
-        on = ((tri == lo[:, None]) & (nxt == hi[:, None])) | ((tri == hi[:, None]) & (nxt == lo[:, None]))
-        k = np.argmax(on, axis=1)
-        return tri[ar, k], tri[ar, (k + 1) % 3], tri[ar, (k + 2) % 3]
-
-    p0, p1, q0 = locate(f[f0])
-    b0, _, q1 = locate(f[f1])
-    q1 = np.where(b0 == p1, q1, -1 - q1)
-    return np.stack([p0, p1, q0, q1]).astype(np.int32).reshape(4, -1)
-
-
-def hinge_incidence(hinge_vtx, n_vertices):
-    """hinge_inc [K,V] int32, slot-major: the hinge corners 4 h + role at every vertex, ascending; pads -1 trailing; K = the largest
-    count over the vertices, at least 1."""
-    hv = np.asarray(hinge_vtx, dtype=np.int64)
-    hv = np.where(hv < 0, -1 - hv, hv)
-    at = hv.T.reshape(-1)                                 # the vertex of corner 4 h + role
-    order = np.argsort(at, kind='stable')
-    counts = np.bincount(at, minlength=n_vertices)
-    K = max(int(counts.max()) if counts.size else 0, 1)
-    starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
-    sorted_at = at[order]
-    inc = np.full((K, n_vertices), -1, dtype=np.int32)
-    inc[np.arange(order.shape[0]) - starts[sorted_at], sorted_at] = order
-    return inc
-
-
-def hinge_rest_cs(hinge_vtx, v_rest):
-    """rest_cs [2,H] float32 = (cos, sin) of every hinge's dihedral angle in the rest shape, by the Bend rule's expressions in float64 from
-    the float32 rest positions [V,3], rounded once; a hinge degenerate at rest gets (1, 0)."""
-    hv = np.asarray(hinge_vtx, dtype=np.int64)
-    x = v_rest.detach().to('cpu', torch.float32).reshape(-1, 3).numpy().astype(np.float64)
-    sigma = np.where(hv[3] < 0, -1.0, 1.0)[:, None]
-    p0, p1, q0, q1 = x[hv[0]], x[hv[1]], x[hv[2]], x[np.where(hv[3] < 0, -1 - hv[3], hv[3])]
-    e = p1 - p0
-    n0, n1 = np.cross(e, q0 - p0), sigma * np.cross(q1 - p0, e)
-    e2, m0, m1 = (e * e).sum(1), (n0 * n0).sum(1), (n1 * n1).sum(1)
-    live = (e2 > 0) & (m0 > 0) & (m1 > 0)
-    safe = lambda a: np.sqrt(np.where(live, a, 1.0))[:, None]
-    u0, u1, eh = n0 / safe(m0), n1 / safe(m1), e / safe(e2)
-    c = np.where(live, (u0 * u1).sum(1), 1.0)
-    s = np.where(live, (np.cross(u0, u1) * eh).sum(1), 0.0)
-    return torch.from_numpy(np.stack([c, s]).astype(np.float32).reshape(2, -1))
-
-
-class _uniform_laplacian(torch.autograd.Function):
-    """L X with L = D^-1 A - I for a batch of vertex buffers [F,V,3].  Forward and backward are both GATHERS over the
-    static one-ring table (L^T = A D^-1 - I), so no scatter / index_put runs in the step (fpcdr_laplacian_gather)."""
-
-    @staticmethod
-    def _apply(x, nbr, nbr32, inv_deg, transpose):
-        if not x.is_cuda:
-            raise RuntimeError("the mesh regularisers run on the GPU only (fpcdr_laplacian_gather); there is no CPU fallback")
-        x = x.contiguous()
-        out = torch.empty_like(x)
-        _lib.call("fpcdr_laplacian_gather", _ptr(x), _ptr(nbr32), _ptr(inv_deg), _ptr(out), x.shape[0], x.shape[1],
-                  nbr32.shape[0], 1 if transpose else 0, _stream())
-        return out
-
-    @staticmethod
-    def forward(ctx, verts, nbr, nbr32, inv_deg):
-        ctx.save_for_backward(nbr, nbr32, inv_deg)
-        return _uniform_laplacian._apply(verts, nbr, nbr32, inv_deg, False)
-
-    @staticmethod
-    def backward(ctx, g):
-        nbr, nbr32, inv_deg = ctx.saved_tensors
-        return _uniform_laplacian._apply(g, nbr, nbr32, inv_deg, True), None, None, None
-
-
-def mesh_laplacian_smoothing(verts, topo, per_mesh=False, rest=None):
-    """Uniform Laplacian smoothing (pytorch3d mesh_laplacian_smoothing(method='uniform'), reference fit.py:581):
-    mean_v || mean_{n in N(v)} x_n - x_v || of every mesh of verts [F,V,3]; per_mesh=True returns the [F] values, else
-    their mean.  rest (a RestShape): the differentials are measured against the rest shape's, || L x - L x_rest ||."""
-    lap = _uniform_laplacian.apply(verts, topo.nbr, topo.nbr32, topo.inv_deg)
-    if rest is not None:
-        lap = lap - rest.lap[None]
-    per = lap.norm(dim=2).mean(dim=1)
-    return per if per_mesh else per.mean()
-
-
-class _laplacian_penalty(torch.autograd.Function):
-    """weight * mean_f (mean_v ||(L x_f)_v||)^2 in one launch each way (fpcdr_laplacian_penalty_fwd / _bwd).
-    eager: the gradient kernel runs in forward() already (the term depends on the vertices only), backward() hands the buffer over --
-    times the upstream scalar, or as it is with unit (the caller guarantees d loss / d value = 1)."""
-
-    @staticmethod
-    def forward(ctx, verts, nbr32, inv_deg, weight, eager=False, unit=False, acc=None, rest_lap=None):
-        if not verts.is_cuda:
-            raise RuntimeError("the mesh regularisers run on the GPU only (fpcdr_laplacian_penalty_fwd); there is no CPU fallback")
-        x = verts.contiguous()
-        F, V, _ = x.shape
-        eager = bool(eager and ctx.needs_input_grad[0])
-        lap = torch.empty_like(x)
-        # acc: F + 1 doubles, zero on entry -- and the call leaves them zero again, so a caller that hands over its own buffer (the
-        # Fitter: one per instance) saves the fill launch of a fresh one per step
-        if acc is None:
-            acc = torch.zeros(F + 1, dtype=torch.float64, device=x.device)
-        assert acc.dtype == torch.float64 and acc.numel() >= F + 1 and acc.is_contiguous()
-        per = torch.empty(F, dtype=torch.float32, device=x.device)
-        out = torch.empty((), dtype=torch.float32, device=x.device)
-        if rest_lap is None:
-            _lib.call("fpcdr_laplacian_penalty_fwd", _ptr(x), _ptr(nbr32), _ptr(inv_deg), _ptr(lap), _ptr(acc), _ptr(per), _ptr(out),
-                      float(weight), F, V, nbr32.shape[0], _stream())
-        else:      # lap = L x - L x_rest; the backward kernel takes it as it takes L x
-            assert rest_lap.shape == (V, 3) and rest_lap.dtype == torch.float32 and rest_lap.is_contiguous() and rest_lap.device == x.device
-            _lib.call("fpcdr_laplacian_penalty_rest_fwd", _ptr(x), _ptr(nbr32), _ptr(inv_deg), _ptr(rest_lap), _ptr(lap), _ptr(acc),
-                      _ptr(per), _ptr(out), float(weight), F, V, nbr32.shape[0], _stream())
-        gx = None
-        if eager:
-            gx = torch.empty_like(lap)
-            _lib.call("fpcdr_laplacian_penalty_bwd", _ptr(lap), _ptr(nbr32), _ptr(inv_deg), _ptr(per), _ptr(_unit_scalar(x.device)),
-                      _ptr(gx), float(weight), F, V, nbr32.shape[0], _stream())
-        if eager:
-            ctx.save_for_backward(gx)
-        else:
-            ctx.save_for_backward(lap, nbr32, inv_deg, per)
-        ctx.weight, ctx.eager, ctx.unit = float(weight), eager, bool(unit)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.eager:
-            gx, = ctx.saved_tensors
-            return (gx if ctx.unit else gx * g.to(torch.float32)), None, None, None, None, None, None, None
-        lap, nbr32, inv_deg, per = ctx.saved_tensors
-        F, V, _ = lap.shape
-        gx = torch.empty_like(lap)
-        _lib.call("fpcdr_laplacian_penalty_bwd", _ptr(lap), _ptr(nbr32), _ptr(inv_deg), _ptr(per), _ptr(g.to(torch.float32).contiguous()),
-                  _ptr(gx), ctx.weight, F, V, nbr32.shape[0], _stream())
-        return gx, None, None, None, None, None, None, None
-
-
-_unit_scalars = {}
-
-
-def _unit_scalar(dev):
-    """A device-resident 1.0f (the upstream of a gradient computed ahead of backward())."""
-    t = _unit_scalars.get(dev)
-    if t is None:
-        t = _unit_scalars[dev] = torch.ones((), dtype=torch.float32, device=dev)
-    return t
-
-
-def laplacian_penalty(verts, topo, weight, eager_grad=False, unit_upstream=False, acc=None, rest=None):
-    """weight * mean over the meshes of verts [F,V,3] of mesh_laplacian_smoothing(mesh)^2 -- the reference's term (fit.py:581 squares
-    the value of the ONE mesh of its step) -- as two launches per step instead of a gather and fifteen torch kernels.
-    eager_grad: the gradient is computed with the value (backward() only multiplies by the upstream scalar, or not at all with
-    unit_upstream).  acc: see _laplacian_penalty.forward.  rest (a RestShape): the term measures against the rest shape, L x - L x_rest
-    in place of L x ("Rest Laplacian rule"): exactly 0, value and gradient, at the rest shape itself."""
-    return _laplacian_penalty.apply(verts, topo.nbr32, topo.inv_deg, weight, eager_grad, unit_upstream, acc,
-                                    None if rest is None else rest.lap)
-
-
-def rest_edge_lengths(nbr32, v_rest):
-    """rest_len [D,V] float32 for the slot-major one-ring table nbr32 [D,V] (MeshTopology.nbr32): || x_rest[nbr[d][v]] - x_rest[v] ||,
-    formed in float64 on the host from the float32 rest positions [V,3] and rounded once -- both ends of an edge hold the same number;
-    pads 0.  Also the number of edges (sum of the degrees / 2)."""
-    nbr = nbr32.detach().cpu().numpy().astype(np.int64)
-    x = v_rest.detach().to('cpu', torch.float32).reshape(-1, 3).numpy().astype(np.float64)
-    V = x.shape[0]
-    assert nbr.shape[1] == V
-    real = nbr < V
-    d = x[np.where(real, nbr, 0)] - x[None]
-    length = np.where(real, np.sqrt((d * d).sum(axis=2)), 0.0)
-    n_real = int(real.sum())
-    assert n_real % 2 == 0
-    return torch.from_numpy(length.astype(np.float32)), n_real // 2
-
-
-class RestShape:
-    """What the rest-shape regularisers need of a rest mesh, built once: .lap [V,3] = L x_rest, .len [D,V] the rest length of every slot of
-    topo.nbr32, .n_edges, and .bend_cs [2,H] the rest dihedral angles of topo.hinges() (made when first asked for).  .lap comes from the
-    device code that forms the term's own L x (fpcdr_laplacian_penalty_rest_fwd without a rest), so that L x - .lap is exactly 0 at the
-    rest shape; on a CPU topology it is None (the Laplacian runs on the GPU only)."""
-
-    def __init__(self, topo, v_rest):
-        dev = topo.nbr32.device
-        x = v_rest.detach().to(torch.float32).reshape(1, -1, 3).contiguous()
-        V, D = x.shape[1], topo.nbr32.shape[0]
-        assert V == topo.n_vertices
-        length, self.n_edges = rest_edge_lengths(topo.nbr32, x)
-        self.len = length.to(dev)
-        self.lap = None
-        self._topo, self._x_rest, self._bend_cs = topo, x, None      # (for bend_cs: nothing of it is built until somebody asks)
-        if dev.type == 'cuda':
-            x = x.to(dev)
-            lap = torch.empty_like(x)
-            acc = torch.zeros(2, dtype=torch.float64, device=dev)
-            per, out = torch.empty(1, dtype=torch.float32, device=dev), torch.empty((), dtype=torch.float32, device=dev)
-            _lib.call("fpcdr_laplacian_penalty_rest_fwd", _ptr(x), _ptr(topo.nbr32), _ptr(topo.inv_deg), None, _ptr(lap), _ptr(acc),
-                      _ptr(per), _ptr(out), 0.0, 1, V, D, _stream())
-            self.lap = lap[0]
-
-    @property
-    def bend_cs(self):
-        """[2,H] float32 (cos, sin) of the rest dihedral angle of every hinge of topo.hinges(), built on first use."""
-        if self._bend_cs is None:
-            self._bend_cs = hinge_rest_cs(self._topo.hinges()[0].cpu().numpy(), self._x_rest).to(self._topo.nbr32.device)
-        return self._bend_cs
-
-
-class _stretch_penalty(torch.autograd.Function):
-    """weight * mean_f mean_edges (|e| - l)^2 with its gradient from ONE call (fpcdr_stretch_penalty): the kernel that walks a vertex's
-    ring for the value has everything the gradient at that vertex needs, so the gradient for a unit upstream is always made in
-    forward(); backward() multiplies it by the upstream scalar, or hands it over as it is with unit."""
-
-    @staticmethod
-    def forward(ctx, verts, nbr32, rest_len, n_edges, target, weight, unit=False, acc=None):
-        if not verts.is_cuda:
-            raise RuntimeError("the mesh regularisers run on the GPU only (fpcdr_stretch_penalty); there is no CPU fallback")
-        x = verts.contiguous()
-        F, V, _ = x.shape
-        if rest_len is not None:
-            assert rest_len.shape == nbr32.shape and rest_len.dtype == torch.float32 and rest_len.is_contiguous() and rest_len.device == x.device
-        if acc is None:      # F + 1 doubles, zero on entry; the call leaves them zero (see _laplacian_penalty.forward)
-            acc = torch.zeros(F + 1, dtype=torch.float64, device=x.device)
-        assert acc.dtype == torch.float64 and acc.numel() >= F + 1 and acc.is_contiguous()
-        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        per = torch.empty(F, dtype=torch.float32, device=x.device)
-        out = torch.empty((), dtype=torch.float32, device=x.device)
-        _lib.call("fpcdr_stretch_penalty", _ptr(x), _ptr(nbr32), _ptr(rest_len), float(target), _ptr(gx), _ptr(acc), _ptr(per), _ptr(out),
-                  float(weight), F, V, nbr32.shape[0], int(n_edges), _stream())
-        if gx is not None:
-            ctx.save_for_backward(gx)
-        ctx.unit = bool(unit)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        gx, = ctx.saved_tensors
-        return (gx if ctx.unit else gx * g.to(torch.float32)), None, None, None, None, None, None, None
-
-
-def stretch_penalty(verts, topo, weight, rest=None, target=0.0, eager_grad=False, unit_upstream=False, acc=None):
-    """weight * mean over the meshes of verts [F,V,3] and over the edges of (|e| - l)^2 ("Stretch rule"): l the edge's length
-    in `rest` (a RestShape), or the constant `target` without one -- stretch_penalty(v, topo, w, target=0.1) is w * mesh_edge_loss(v, topo, 0.1),
-    the reference's term (fit.py:580).  The modes are laplacian_penalty's: lazy, eager_grad, and eager_grad with unit_upstream (the caller
-    guarantees d loss / d value = 1: backward() hands the gradient buffer over).  The one call makes the gradient with the value in every
-    mode, so lazy and eager_grad differ in nothing but the name.  acc: see _laplacian_penalty.forward."""
-    if rest is None:
-        rest_len, n_edges = None, int(topo.edges.shape[0])
-    else:
-        rest_len, n_edges = rest.len, rest.n_edges
-    return _stretch_penalty.apply(verts, topo.nbr32, rest_len, n_edges, target, weight, bool(eager_grad and unit_upstream), acc)
-
-
-class _bend_penalty(torch.autograd.Function):
-    """weight * mean_f mean_hinges (1 - cos(theta - theta_rest)) with its gradient from ONE call (fpcdr_bend_penalty): a pass over the
-    hinges leaves every corner's gradient in a scratch, a gather sums them per vertex.  As with _stretch_penalty the gradient for a unit
-    upstream is made in forward(); backward() multiplies it by the upstream scalar, or hands it over as it is with unit."""
-
-    @staticmethod
-    def forward(ctx, verts, hinge_vtx, hinge_inc, rest_cs, weight, unit=False, acc=None, scratch=None):
-        if not verts.is_cuda:
-            raise RuntimeError("the mesh regularisers run on the GPU only (fpcdr_bend_penalty); there is no CPU fallback")
-        x = verts.contiguous()
-        F, V, _ = x.shape
-        H, K = hinge_vtx.shape[1], hinge_inc.shape[0]
-        assert hinge_vtx.dtype == torch.int32 and hinge_inc.dtype == torch.int32 and hinge_inc.shape[1] == V and hinge_vtx.device == x.device
-        if rest_cs is not None:
-            assert rest_cs.shape == (2, H) and rest_cs.dtype == torch.float32 and rest_cs.is_contiguous() and rest_cs.device == x.device
-        if acc is None:      # F + 1 doubles, zero on entry; the call leaves them zero (see _laplacian_penalty.forward)
-            acc = torch.zeros(F + 1, dtype=torch.float64, device=x.device)
-        assert acc.dtype == torch.float64 and acc.numel() >= F + 1 and acc.is_contiguous()
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            if scratch is None:      # the corners' gradients, F * H * 12 floats (a caller that keeps one saves the allocation per step)
-                scratch = torch.empty(max(F * H * 12, 1), dtype=torch.float32, device=x.device)
-            assert scratch.dtype == torch.float32 and scratch.numel() >= F * H * 12 and scratch.is_contiguous() and scratch.device == x.device
-        per = torch.empty(F, dtype=torch.float32, device=x.device)
-        out = torch.empty((), dtype=torch.float32, device=x.device)
-        _lib.call("fpcdr_bend_penalty", _ptr(x), _ptr(hinge_vtx), _ptr(rest_cs), _ptr(hinge_inc), _ptr(scratch) if gx is not None else None,
-                  _ptr(gx), _ptr(acc), _ptr(per), _ptr(out), float(weight), F, V, H, K, _stream())
-        if gx is not None:
-            ctx.save_for_backward(gx)
-        ctx.unit = bool(unit)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        gx, = ctx.saved_tensors
-        return (gx if ctx.unit else gx * g.to(torch.float32)), None, None, None, None, None, None, None
-
-
-def bend_penalty(verts, topo, weight, rest=None, eager_grad=False, unit_upstream=False, acc=None, scratch=None):
-    """weight * mean over the meshes of verts [F,V,3] and over the hinges of 1 - cos(theta - theta_rest) ("Bend rule"):
-    theta the signed dihedral angle, theta_rest the hinge's angle in `rest` (a RestShape), or 0 without one -- bend_penalty(v, topo, w) is
-    w * mesh_normal_consistency(v, topo), the reference's term (fit.py:582).  The modes and `acc` are stretch_penalty's.  scratch: a float32
-    buffer of at least F * H * 12 elements for the corners' gradients (None: one is allocated per call)."""
-    hinge_vtx, hinge_inc, _, _ = topo.hinges()
-    return _bend_penalty.apply(verts, hinge_vtx, hinge_inc, None if rest is None else rest.bend_cs, weight,
-                               bool(eager_grad and unit_upstream), acc, scratch)
-
-
-def mesh_normal_consistency(verts, topo):
-    """pytorch3d.loss.mesh_normal_consistency restated (reference fit.py:582; weight 0 in main.py:40): for every edge
-    shared by exactly two faces, 1 - cos of the angle between the two face normals (oriented by the faces' own vertex
-    order, as pytorch3d does through the edge's two opposite vertices); mean over those edges and over the batch.
-    verts [F,V,3]."""
-    f0, f1 = topo.edge_faces
-    if f0.numel() == 0:
-        return verts.sum() * 0.0
-    tri = topo.faces
-
-    def normals(fid):
-        a, b, c = verts[:, tri[fid, 0]], verts[:, tri[fid, 1]], verts[:, tri[fid, 2]]
-        return torch.cross(b - a, c - a, dim=-1)
-
-    n0, n1 = normals(f0), normals(f1)
-    cos = torch.nn.functional.cosine_similarity(n0, n1, dim=-1, eps=1e-8)
-    return (1.0 - cos).mean()
-
-
-def mesh_edge_loss(verts, topo, target_length=0.0):
-    """mean over edges (and meshes) of (|e| - target)^2."""
-    d = verts[:, topo.edges[:, 0]] - verts[:, topo.edges[:, 1]]
-    return ((d.norm(dim=2) - target_length) ** 2).mean()
+_mvp_indexed_func = _mvp_func      # (the name under which the tests call it with index tensors)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1143,18 +744,29 @@ class Fitter:
         self.rng = np.random.default_rng(cfg.seed + 1000 * rank)
         # final shapes (fit.py:457); every rank fills the rows of its own frames, gather_result() joins the shards
         self._result_full = torch.zeros(F, self.v_base.shape[0], dtype=torch.float32, device=dev)
-        self._lap_acc = torch.zeros(self.frame_hi - self.frame_lo + 1, dtype=torch.float64, device=dev)   # (fpcdr_laplacian_penalty_fwd leaves it zero)
-        # the base mesh as the rest shape of the regularisers that measure against it, and the stretch term's own accumulators
+        # the base mesh as the rest shape of the regularisers that measure against it
         self.rest = RestShape(self.topo, self.v_base) if (cfg.laplacian_relative or cfg.weight_stretch or cfg.weight_bend) else None
-        self._str_acc = torch.zeros_like(self._lap_acc) if cfg.weight_stretch else None
-        # the bending term's accumulators, its tables and the scratch of its corner gradients for the most frames a step takes: all made
-        # here, before any capture
-        self._bnd_acc = self._bnd_scratch = None
+        # the bending term's tables and the scratch of its corner gradients for the most frames a step takes: made here, before any capture
+        self._bnd_scratch = None
         if cfg.weight_bend:
-            self._bnd_acc = torch.zeros_like(self._lap_acc)
             n_hinges = self.topo.hinges()[2]
             assert self.rest.bend_cs.shape == (2, n_hinges)      # (built here, not in the first step)
             self._bnd_scratch = torch.empty(max((self.frame_hi - self.frame_lo) * n_hinges * 12, 1), dtype=torch.float32, device=dev)
+        # The step's eager terms, vtx [Fb,V,3] -> scalar, in the fixed order Laplacian, stretch, bend.  Each makes its gradient with its
+        # value (it depends on the vertices only) and hands the buffer over in backward(); its weight carries the 1 / world, so that
+        # d loss / d term = 1 exactly.  ONE accumulator buffer serves all three: the calls are ordered on the step's one stream, and each
+        # leaves the buffer zero (the finish kernel of csrc/mesh_reg.hip).
+        self._reg_acc = torch.zeros(self.frame_hi - self.frame_lo + 1, dtype=torch.float64, device=dev)
+        eager = dict(eager_grad=True, unit_upstream=True, acc=self._reg_acc)
+        self._reg_terms = []
+        if cfg.weight_laplacian and cfg.fused_loss:      # (two launches, ~25 us in front of the objective)
+            lap_rest = self.rest if cfg.laplacian_relative else None
+            self._reg_terms.append(lambda vtx: laplacian_penalty(vtx, self.topo, cfg.weight_laplacian / world, rest=lap_rest, **eager))
+        if cfg.weight_stretch:
+            self._reg_terms.append(lambda vtx: stretch_penalty(vtx, self.topo, cfg.weight_stretch / world, rest=self.rest, **eager))
+        if cfg.weight_bend:
+            self._reg_terms.append(lambda vtx: bend_penalty(vtx, self.topo, cfg.weight_bend / world, rest=self.rest,
+                                                            scratch=self._bnd_scratch, **eager))
         self._result_pending = None
         self.iteration = 0
         self._log_file, self._log_t, self._log_it = None, None, 0
@@ -1281,10 +893,11 @@ class Fitter:
             else:
                 f_idx = frame_ids
             Nc = len(self.cam_idxs) if view_ids is None else int(view_ids.shape[0])
-            return _mvp_indexed_func.apply(self.q_opt, self.t_opt, self.per_frame_q, self.per_frame_t, self.proj, self.t_mv, f_idx.contiguous(),
-                                           view_ids, None if all_cams else self.cam_sel, int(f_idx.shape[0]), Nc, pool)
+            return _mvp_func.apply(self.q_opt, self.t_opt, self.per_frame_q, self.per_frame_t, self.proj, self.t_mv, f_idx.contiguous(),
+                                   view_ids, None if all_cams else self.cam_sel, int(f_idx.shape[0]), Nc, pool)
         q_c, t_c = (self.q_opt, self.t_opt) if all_cams else (self.q_opt[self.cam_sel], self.t_opt[self.cam_sel])
-        return _mvp_func.apply(q_c, t_c, self._take(self.per_frame_q, 0, frame_ids), self._take(self.per_frame_t, 0, frame_ids), self.proj, self.t_mv, pool)
+        return _mvp_func.apply(q_c, t_c, self._take(self.per_frame_q, 0, frame_ids), self._take(self.per_frame_t, 0, frame_ids), self.proj, self.t_mv,
+                               None, None, None, None, None, pool)
 
     @staticmethod
     def _take(t, dim, ids):
@@ -1575,23 +1188,8 @@ class Fitter:
             reg = reg + torch.mean(mi ** 2)
         if self.world > 1 and chain_terms:
             reg = reg / self.world
-        # the Laplacian term as two launches, its gradient computed with the value (it depends on the vertices only): backward() hands the
-        # buffer over.  Its weight carries the 1 / world, so that d loss / d term = 1 exactly.  (The two launches are ~25 us in front of
-        # the objective.)
-        lap = None
-        if cfg.weight_laplacian and cfg.fused_loss:
-            lap = laplacian_penalty(vtx_pos_split, self.topo, cfg.weight_laplacian / self.world, eager_grad=True, unit_upstream=True,
-                                    acc=self._lap_acc, rest=lap_rest)
-        # the stretch term against the base mesh, handed over the same way (one call: its gradient comes with its value)
-        strt = None
-        if cfg.weight_stretch:
-            strt = stretch_penalty(vtx_pos_split, self.topo, cfg.weight_stretch / self.world, rest=self.rest, eager_grad=True,
-                                   unit_upstream=True, acc=self._str_acc)
-        # ... and the bending term against the base mesh
-        bnd = None
-        if cfg.weight_bend:
-            bnd = bend_penalty(vtx_pos_split, self.topo, cfg.weight_bend / self.world, rest=self.rest, eager_grad=True,
-                               unit_upstream=True, acc=self._bnd_acc, scratch=self._bnd_scratch)
+        # the eager terms (Laplacian, stretch, bend: __init__), their gradients made here with their values
+        terms = [term(vtx_pos_split) for term in self._reg_terms]
         self.optimizer.zero_grad(set_to_none=True)
         if one_shot:
             bg_sum = None
@@ -1611,16 +1209,12 @@ class Fitter:
                                      queued_backward=cfg.queued_backward and not self.use_graph,
                                      one_pass=cfg.one_pass, unit_upstream=True, zero_extra=zero_buf,      # (the seeds below are 1)
                                      skip_out=self._skip_cur)
-            self._backward(pix, self._one, reg, lap, strt, bnd)
+            self._backward(pix, self._one, reg, *terms)
             loss = pix.detach()
-            if chain_terms:
+            if chain_terms:      # (an add is a launch: none for a reg that is the constant 0)
                 loss = loss + reg.detach()
-            if lap is not None:
-                loss = loss + lap.detach()
-            if strt is not None:
-                loss = loss + strt.detach()
-            if bnd is not None:
-                loss = loss + bnd.detach()
+            for term in terms:
+                loss = loss + term.detach()
         elif cfg.fused_loss:
             if window is None:
                 sum_sq, g_colour = pixel_loss_fused(colour, rast_out, ref, n_total)
@@ -1628,23 +1222,19 @@ class Fitter:
                 sum_sq, g_colour = pixel_loss_blurred(colour, rast_out, ref, window[1], n_total)
             else:
                 sum_sq, g_colour = pixel_loss_normalised(colour, rast_out, ref, window[1], cfg.norm_eps, n_total)
-            self._backward(colour, g_colour, reg, lap, strt, bnd)
-            loss = sum_sq[0].to(torch.float32) / n_total + reg.detach() + (lap.detach() if lap is not None else 0.0)
-            if strt is not None:
-                loss = loss + strt.detach()
-            if bnd is not None:
-                loss = loss + bnd.detach()
+            self._backward(colour, g_colour, reg, *terms)
+            loss = sum_sq[0].to(torch.float32) / n_total + reg.detach()
+            for term in terms:
+                loss = loss + term.detach()
         else:
             col = torch.where(rast_out[..., 3:] > 0, colour, self._background)
             # the reference holds its target image as float32 on the GPU (fit.py:531-532); the 8-bit batch is converted once
             if self._targets_f32 is None:
                 self._targets_f32 = self.targets.to(torch.float32)
             ref_f = self._take(self._targets_f32.reshape(-1, *self.resolution), 0, rows).reshape(Fb * Nc, *self.resolution, 1)
-            loss = torch.mean((ref_f - col * 255) ** 2) / self.world + reg + (lap if lap is not None else 0.0)
-            if strt is not None:
-                loss = loss + strt
-            if bnd is not None:
-                loss = loss + bnd
+            loss = torch.mean((ref_f - col * 255) ** 2) / self.world + reg
+            for term in terms:
+                loss = loss + term
             loss.backward()
         self._store_result(frame_ids, vtx_pos.detach())
         return loss.detach()

@@ -5,7 +5,8 @@
 Unbundles the device image of each hipcc object, disassembles it, and compares every kernel whose name matches NAME_REGEX (default: all)
 after stripping what a move of source text changes without changing the code: symbol names (the anonymous namespace's hash, template
 arguments' spelling), addresses, encodings and comments.  Prints identical / DIFFERENT with the instruction counts, and VGPR / SGPR /
-LDS / private-segment figures of both from the code-object notes.  Needs no GPU."""
+LDS / private-segment figures of both from the code-object notes.  ISA_AB_RENAME="old=new,..." compares a renamed kernel pairwise (short
+names as printed); ISA_AB_DIFF=N prints the first N lines of each difference.  Needs no GPU."""
 import difflib
 import os
 import re
@@ -26,11 +27,11 @@ def device_image(obj, tmp, tag):
 
 def short(name):
     """k_name or k_name<0|1> of a mangled kernel symbol (one bool template argument at the most); anything else as it is"""
-    m = re.search(r"_GLOBAL__N_1(\d+)(k_\w+)", name)
+    m = re.search(r"(?:_GLOBAL__N_1|^_Z)(\d+)(k_\w+)", name)
     if not m:
         return name
     n = int(m.group(1))
-    t = re.match(r"ILb([01])E", m.group(2)[n:])
+    t = re.match(r"IL[bi]([01])E", m.group(2)[n:])
     return m.group(2)[:n] + (f"<{t.group(1)}>" if t else "")
 
 
@@ -57,6 +58,9 @@ def kernels(co):
         ins = re.sub(r"<[^>]*>", "<L>", ins)              # branch targets by symbol
         ins = re.sub(r"\s+", " ", ins)
         code[cur].append(ins)
+    for v in code.values():                               # the padding behind a kernel's last instruction
+        while v and v[-1] in ("s_nop 0", "..."):
+            v.pop()
     return {k: v for k, v in code.items() if k in res}, res
 
 
@@ -66,6 +70,9 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         co, ro = kernels(device_image(old, tmp, "old"))
         cn, rn = kernels(device_image(new, tmp, "new"))
+    for pair in filter(None, os.environ.get("ISA_AB_RENAME", "").split(",")):      # a kernel of OLD under its name in NEW
+        was, now = pair.split("=")
+        co[now], ro[now] = co.pop(was), ro.pop(was)
     same = True
     for k in sorted(set(co) | set(cn)):
         if not pat.search(k):

@@ -1,4 +1,4 @@
-"""HIP-event times of the bending term (csrc/bend.hip) at F = 32 meshes of the 15002-vertex UV sphere (45000 hinges, two poles with 240
+"""HIP-event times of the bending term (csrc/mesh_reg.hip) at F = 32 meshes of the 15002-vertex UV sphere (45000 hinges, two poles with 240
 hinge corners each), the variants taking turns in one process:
 
   fpcdr_bend_penalty                        value and gradient: the hinge pass, the per-vertex gather, the finish kernel

@@ -1,4 +1,4 @@
-"""HIP-event times of the rest-shape regularisers (csrc/clip.hip) at F = 32 meshes of the 15002-vertex UV sphere (two poles of degree 120),
+"""HIP-event times of the rest-shape regularisers (csrc/mesh_reg.hip) at F = 32 meshes of the 15002-vertex UV sphere (two poles of degree 120),
 the variants taking turns in one process:
 
   fpcdr_laplacian_penalty_fwd           the existing forward (gather + norms, then the finish kernel)

@@ -1,4 +1,4 @@
-"""float64 statement on the CPU of the bending term ("Bend rule"; csrc/bend.hip k_bend_*): the yardstick of
+"""float64 statement on the CPU of the bending term ("Bend rule"; csrc/mesh_reg.hip k_bend_*): the yardstick of
 tests/test_gpu_bend.py, itself checked on the CPU by tests/test_bend_ref.py.  Nothing here imports fpc_diffrend_amd.
 
 The convention is tests/rest_ref.py's: every function evaluates in `dtype` (float64 by default; float32 gives "the same formula in

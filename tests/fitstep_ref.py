@@ -1,4 +1,4 @@
-"""float64 restatements on the CPU of the small kernels of a fit step (csrc/blend.hip, clip.hip, loss.hip): the yardstick of
+"""float64 restatements on the CPU of the small kernels of a fit step (csrc/blend.hip, clip.hip, mesh_reg.hip, loss.hip): the yardstick of
 tests/test_gpu_fitstep.py, itself checked on the CPU by tests/test_fitstep_ref.py.  Nothing here imports fpc_diffrend_amd.
 
 Every function takes tensors of any float dtype and evaluates in `dtype` (float64 by default; float32 gives "the same formula in

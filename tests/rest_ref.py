@@ -1,5 +1,5 @@
 """float64 statements on the CPU of the two rest-shape regularisers ("Rest Laplacian rule" and "Stretch rule";
-csrc/clip.hip k_lap_penalty_fwd<true>, k_stretch_*): the yardstick of tests/test_gpu_rest.py, itself checked on the CPU by
+csrc/mesh_reg.hip k_lap_penalty_fwd<true>, k_stretch_penalty): the yardstick of tests/test_gpu_rest.py, itself checked on the CPU by
 tests/test_rest_ref.py.  Nothing here imports fpc_diffrend_amd.
 
 The convention is tests/fitstep_ref.py's: every function evaluates in `dtype` (float64 by default; float32 gives "the same formula in

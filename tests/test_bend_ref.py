@@ -225,12 +225,14 @@ def test_bad_arguments_give_an_error_code_before_any_launch():
 def test_bend_kernels_have_no_private_segment():
     """read from the built object (tests/codeobj.py).  The gather keeps a running sum, not an indexed local array."""
     import codeobj
-    recs = codeobj.kernels("bend.o")
+    recs = codeobj.kernels("mesh_reg.o")
     if recs is None:
         pytest.skip("no built objects / llvm tools")
     bend = {name: private for name, private, _ in recs if "k_bend_" in name}
-    assert len(bend) == 3 and all(p == 0 for p in bend.values()), bend
-    assert all(any(k in name for name in bend) for k in ("k_bend_hinges", "k_bend_gather", "k_bend_finish"))
+    assert len(bend) == 2 and all(p == 0 for p in bend.values()), bend
+    assert all(any(k in name for name in bend) for k in ("k_bend_hinges", "k_bend_gather"))
+    finish = {name: private for name, private, _ in recs if "k_penalty_finish" in name}      # the finish kernel it shares with the other terms
+    assert len(finish) == 2 and all(p == 0 for p in finish.values()), finish
 
 
 def test_the_readmes_table_rows_come_from_the_statement():

@@ -1,4 +1,4 @@
-"""GPU: the bending term (csrc/bend.hip k_bend_hinges, k_bend_gather, k_bend_finish; fit.MeshTopology.hinges(), RestShape.bend_cs,
+"""GPU: the bending term (csrc/mesh_reg.hip k_bend_hinges, k_bend_gather, k_penalty_finish; fit.MeshTopology.hinges(), RestShape.bend_cs,
 fit.bend_penalty, FitConfig.weight_bend) entry by entry against float64 (tests/bend_ref.py), and inside a Fitter: eager, under a captured
 graph, on two ranks.
 
@@ -292,7 +292,7 @@ def _flat_grads(ft):
 
 def test_fitter_without_the_weight_builds_nothing():
     ft = _fitter()
-    assert ft.cfg.weight_bend == 0.0 and ft.rest is None and ft.topo._hinges is None and ft._bnd_acc is None and ft._bnd_scratch is None
+    assert ft.cfg.weight_bend == 0.0 and ft.rest is None and ft.topo._hinges is None and ft._reg_terms == [] and ft._bnd_scratch is None
     ft.loss_and_backward(slice(0, 4))
     assert ft.rest is None and ft.topo._hinges is None
 
@@ -307,7 +307,7 @@ def test_fitter_gradient_is_the_pixel_terms_plus_the_op(path):
     ft_on, ft_off = _fitter(weight_bend=W_BND, **kw), _fitter(**kw)
     assert ft_off.rest is None and ft_on.rest is not None and ft_on._bnd_scratch.numel() == 4 * 1536 * 12
     l_on, l_off = float(ft_on.loss_and_backward(frames)), float(ft_off.loss_and_backward(frames))
-    assert bool((ft_on._bnd_acc == 0).all())
+    assert bool((ft_on._reg_acc == 0).all())
     g_on, g_off = _flat_grads(ft_on), _flat_grads(ft_off)
     ft_on.optimizer.zero_grad(set_to_none=True)
     v = ft_on.vertices(frames).reshape(4, -1, 3)
@@ -340,7 +340,7 @@ def test_hip_graph_steps_equal_eager_steps_with_the_bend_term(mode, fps):
         traj[graph] = [float(ft.step()) for _ in range(14)]
         if graph:
             assert ft._graphs is not None
-        assert bool((ft._lap_acc == 0).all()) and bool((ft._bnd_acc == 0).all())
+        assert bool((ft._reg_acc == 0).all())      # (the one buffer of the Laplacian and the bending term)
     a, b = np.asarray(traj[False]), np.asarray(traj[True])
     assert np.isfinite(b).all()
     assert np.allclose(a, b, rtol=2e-3), (a, b)

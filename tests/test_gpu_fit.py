@@ -311,7 +311,7 @@ def test_laplacian_gather_form_matches_dense():
 
 
 def test_laplacian_penalty_one_launch_matches_the_torch_chain():
-    """(Both sides of this comparison run ring_sum() of csrc/clip.hip -- fit.mesh_laplacian_smoothing goes through fpcdr_laplacian_gather --
+    """(Both sides of this comparison run ring_sum() of csrc/mesh_reg.hip -- fit.mesh_laplacian_smoothing goes through fpcdr_laplacian_gather --
     so it shows that two users of that function agree, not that the function is right: the independent check, against a float64 Laplacian
     built from the face list, is tests/test_gpu_fitstep.py.)
     fit.laplacian_penalty (fpcdr_laplacian_penalty_fwd / _bwd: value by the last workgroup, transposed gather of the normalised
@@ -794,7 +794,7 @@ def test_laplacian_penalty_eager_gradient_and_heavy_rings():
     """(i) eager_grad=True (the gradient kernel runs with the value; backward() hands the buffer over, times the upstream scalar unless
     unit_upstream) == the lazy form; (ii) a fan whose hub has 200 neighbours -- rings beyond
     eight slots are finished by the whole wave, here in four rounds of 64 slots -- against the torch chain, value and gradient.
-    (That chain, fit.mesh_laplacian_smoothing, runs the same ring_sum() of csrc/clip.hip through fpcdr_laplacian_gather: the fan case compares
+    (That chain, fit.mesh_laplacian_smoothing, runs the same ring_sum() of csrc/mesh_reg.hip through fpcdr_laplacian_gather: the fan case compares
     two users of that function with each other.  The independent check of the whole-wave path, against a float64 Laplacian built from the
     face list, is tests/test_gpu_fitstep.py.)"""
     from fpc_diffrend_amd import fit, scene

@@ -1,4 +1,4 @@
-"""GPU: the small kernels of a fit step (csrc/blend.hip, clip.hip, loss.hip) entry by entry against float64 (tests/fitstep_ref.py).
+"""GPU: the small kernels of a fit step (csrc/blend.hip, clip.hip, mesh_reg.hip, loss.hip) entry by entry against float64 (tests/fitstep_ref.py).
 
 Each kernel is compared with float64 arithmetic on the float32 inputs that this kernel read (the Laplacian's backward from the
 forward's own float32 lap and per).  The error of an output x with float64 reference r is e = max_i |x_i - r_i| / S_i in units of
@@ -230,8 +230,8 @@ def test_mvp_chain_entries_against_float64(Fb, Nc, kind):
         leaves = [t.cuda().requires_grad_(True) for t in (qc, tc, qf, tf)]
         if form == 'plain':
             out = fit._mvp_func.apply(*leaves, P.cuda(), MV.cuda())
-        else:
-            out = fit._mvp_indexed_func.apply(*leaves, P.cuda(), MV.cuda(), None, None, None, Fb, Nc)
+        else:      # (an identity frame index: without any index tensor the call is the plain one)
+            out = fit._mvp_indexed_func.apply(*leaves, P.cuda(), MV.cuda(), torch.arange(Fb).cuda(), None, None, Fb, Nc)
         out.backward(go.cuda())
         _mvp_check(f"mvp({Fb},{Nc}){kind}/{form}", [out] + [t.grad for t in leaves], ref, Fb, Nc, (0, 0))
 
@@ -261,6 +261,22 @@ def test_mvp_indexed_tables_against_float64(kind):
             assert rep_f == 2 and rep_c == 2 and sorted(cv) != cv
         zeros = (ncam - len(set(cp)), nf - len(set(fr)))
         _mvp_check(f"mvp_idx/{name}/{kind}", [out] + [t.grad for t in leaves], ref, Fb * rep_c, Nc * rep_f, zeros)
+
+
+@pytest.mark.parametrize("Fb,Nc", [(1, 1), (2, 2)])
+def test_mvp_plain_call_equals_the_indexed_call_with_identity_indices(Fb, Nc):
+    """The two instantiations of k_mvp_fwd / k_mvp_bwd (csrc/clip.hip) run the same arithmetic: the matrices agree to the bit, and so do
+    the four gradient tables -- at these sizes a gradient row receives at most two atomic adds into zero, and a + b = b + a."""
+    from fpc_diffrend_amd import fit
+    qc, tc, qf, tf, P, MV, go = _mvp_tables(Fb, Nc, 'randn')
+    res = []
+    for idx in ((None, None, None), (torch.arange(Fb).cuda(), torch.arange(Nc).cuda(), torch.arange(Nc).cuda())):
+        leaves = [t.cuda().requires_grad_(True) for t in (qc, tc, qf, tf)]
+        out = fit._mvp_func.apply(*leaves, P.cuda(), MV.cuda(), *idx, Fb, Nc)
+        out.backward(go.cuda())
+        res.append([out.detach()] + [t.grad for t in leaves])
+    for name, a, b in zip(('mvp', 'g_q_cam', 'g_t_cam', 'g_q_frame', 'g_t_frame'), *res):
+        assert torch.equal(a, b), (name, a, b)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -395,7 +411,7 @@ def test_laplacian_entries_against_float64_small_meshes():
         for F in (1, 3):
             _lap_case(name, faces, V, pos, F, g, degs, exact=(name == 'grid'))
     faces, V, pos, degs = R.lap_meshes(g)['fan73']
-    _lap_case('fan73', faces, V, pos, 300, g, degs)       # more meshes than the 256 threads of k_lap_penalty_finish
+    _lap_case('fan73', faces, V, pos, 300, g, degs)       # more meshes than the 256 threads of k_penalty_finish
 
 
 def test_laplacian_entries_against_float64_cfg1_and_sphere():

@@ -201,10 +201,12 @@ def test_rest_and_stretch_kernels_have_no_private_segment():
     """read from the built object (tests/codeobj.py).  The per-slot terms of the unrolled ring walk are indexed by
     compile-time constants only."""
     import codeobj
-    recs = codeobj.kernels("clip.o")
+    recs = codeobj.kernels("mesh_reg.o")
     if recs is None:
         pytest.skip("no built objects / llvm tools")
     stretch = {name: private for name, private, _ in recs if "k_stretch_" in name}
-    assert len(stretch) == 2 and all(p == 0 for p in stretch.values()), stretch
+    assert len(stretch) == 1 and all(p == 0 for p in stretch.values()), stretch       # k_stretch_penalty
     fwd = {name: private for name, private, _ in recs if "k_lap_penalty_fwd" in name}
     assert len(fwd) == 2 and all(p == 0 for p in fwd.values()), fwd       # <false> and <true>
+    finish = {name: private for name, private, _ in recs if "k_penalty_finish" in name}      # the finish kernel of all three terms
+    assert len(finish) == 2 and all(p == 0 for p in finish.values()), finish       # <false> (stretch, bend) and <true> (Laplacian)
