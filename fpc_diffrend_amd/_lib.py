@@ -131,6 +131,16 @@ class NormLoss(ctypes.Structure):
                 ("loss_sum", _p), ("grad_color", _p)]
 
 
+ROBUST_KIND = {'l2': 0, 'charbonnier': 1, 'geman_mcclure': 2}      # FPCDR_ROBUST_*
+
+
+class RobustLoss(ctypes.Structure):
+    _fields_ = [("color", _p), ("rast", _p), ("ref", _p), ("B", _i), ("H", _i), ("W", _i), ("C", _i),
+                ("bg", ctypes.c_float), ("color_scale", ctypes.c_float), ("grad_scale", ctypes.c_float), ("kind", _i),
+                ("inv_c", ctypes.c_float), ("w_outside", ctypes.c_float), ("sat", _i), ("mask", _p), ("face_w", _p), ("T", _i),
+                ("sums", _p), ("grad_color", _p)]
+
+
 ADAM_MAX_TENSORS = 16     # FPCDR_ADAM_MAX_TENSORS
 
 
@@ -198,6 +208,7 @@ SYMBOLS = {
     "fpcdr_blur_loss": (_int, [ctypes.POINTER(BlurLoss), _p]),
     "fpcdr_norm_loss_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "fpcdr_norm_loss": (_int, [ctypes.POINTER(NormLoss), _p]),
+    "fpcdr_robust_loss": (_int, [ctypes.POINTER(RobustLoss), _p]),
     "fpcdr_adam_step": (_int, [ctypes.POINTER(AdamParams), _p]),
     "fpcdr_undistort_u8": (_int, [_p, _p, _p, ctypes.c_int64, _i, _i, _i, _i, _i, _p]),
     "fpcdr_compare_u8": (_int, [_p, _int, ctypes.c_float, _p, _p, _p, ctypes.c_int64, _i, _i, _i, _i, _i, _i, _p]),

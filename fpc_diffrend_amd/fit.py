@@ -286,6 +286,33 @@ def pixel_loss_normalised(colour, rast_out, ref_u8, taps, eps, n_total=None):
     return acc, grad
 
 
+def pixel_loss_robust(colour, rast_out, ref_u8, kind, scale, n_total=None, mask=None, face_weights=None, weight_outside=1.0, saturation=0):
+    """pixel_loss_fused with every residual passed through the robust function `kind` ('l2' | 'charbonnier' | 'geman_mcclure', scale c in
+    grey levels) and weighted by the mask byte, the face weight of its triangle, weight_outside off the mesh and 0 from `saturation` on
+    ("Robust loss rule"; fpcdr_robust_loss): returns (sums [2] f64 tensor = (sum of w * rho, sum of w), d mean / d colour
+    [B,H,W,C]) with mean over n_total elements -- not over the sum of the weights."""
+    n_total = n_total or colour.numel()
+    return dr.robust_loss_call(colour, rast_out, ref_u8, kind, scale, 1.0 / n_total, mask=mask, face_weights=face_weights,
+                               weight_outside=weight_outside, saturation=saturation, background=BACKGROUND, check_weights=False)
+
+
+def load_face_weights(face_weights, n_faces):
+    """FitConfig.face_weights -- an array-like [T] or the path of a text file with one number per face -- as a float32 array [T], or
+    ValueError: another length than the mesh has faces, an entry that is not finite or is negative."""
+    if isinstance(face_weights, (str, os.PathLike)):
+        try:
+            w = np.loadtxt(face_weights, dtype=np.float64, ndmin=1)
+        except (OSError, ValueError) as e:
+            raise ValueError(f"FitConfig.face_weights: cannot read {face_weights}: {e}")
+    else:
+        w = np.asarray(face_weights, dtype=np.float64)
+    if w.ndim != 1 or w.shape[0] != n_faces:
+        raise ValueError(f"FitConfig.face_weights holds one number per face: expected [{n_faces}], got shape {tuple(w.shape)}")
+    if not (np.isfinite(w).all() and (w >= 0).all()):
+        raise ValueError("FitConfig.face_weights must be finite and not negative")
+    return w.astype(np.float32)
+
+
 def _check_window_term(cfg, kind, name, graph_why, sigmas):
     """What FitConfig.blur_sigma > 0 and norm_sigma > 0 (kind 'blur' / 'norm') both ask of the other options, or ValueError."""
     if not cfg.fused_loss:
@@ -590,13 +617,48 @@ class FitConfig:
                                     # says for full size; False: enable_mip everywhere.  On by default because the coarse levels are useless
                                     # without it: the texture aliases under the 4-8 x larger pixel footprints, and on the CPU oracle's scan
                                     #  the gradient at factor 8 then has the WRONG sign from 3 pixels of offset on
-    log_interval: int = 0           # every n steps one JSON line {it, loss, lr, frames_per_s} (reference print, fit.py:621-623)
+    robust: str = ''                # 'l2' | 'charbonnier' | 'geman_mcclure': the pixel term is the WEIGHTED ROBUST loss (fit.pixel_loss_robust;
+                                    # DESIGN.md 3, "Robust loss rule") on the operator path: like d^2 for residuals far below robust_scale,
+                                    # 2 c |d| (Charbonnier) or c^2 (Geman-McClure) far above it, so highlights and occluders stop outweighing
+                                    # the pixels the model can explain.  '' = off
+    robust_scale: Optional[float] = None     # the scale c in grey levels, finite and > 0.  No default -- nobody has measured one: required
+                                    # when robust is 'charbonnier' or 'geman_mcclure' (ValueError without), ignored for 'l2'
+    robust_iters: int = 0           # 0 = every iteration uses `robust`; n = iterations i < n, then the run continues on the path the other
+                                    # flags select (with weights on: the same term with kind 'l2')
+    weight_outside: float = 1.0     # the weight of pixels the mesh does not cover (they are compared with the background), finite, >= 0
+    saturation: int = 0             # 1..255: a capture pixel at or above it counts nothing (scene.from_take clips at 140); 0 = off
+    face_weights: object = None     # one weight per triangle, finite and >= 0 (0: mouth socket, eyeballs, scalp): an array-like [T] or the
+                                    # path of a text file with one number per face
+    use_masks: bool = True          # a Scene with masks (scene.from_take(maskdir=...)) weights every pixel by its mask byte / 255
+                                    # Any of these -- robust inside robust_iters, masks in use, face_weights, saturation > 0, weight_outside
+                                    # != 1 -- makes the iteration run render_from_clip + pixel_loss_robust in the place of the one-pass
+                                    # objective (kind 'l2' when only weights are on).  Not together with blur_sigma > 0 or norm_sigma > 0,
+                                    # nor with hip_graph (ValueError).  All off: a step is exactly the path it was
+    log_interval: int = 0           # every n steps one JSON line {it, loss, lr, frames_per_s} (reference print, fit.py:621-623); an
+                                    # iteration on the robust term adds "wsum", the sum of its weights over rank 0's batch
     reg_log_interval: int = 500     # every n steps the regulariser breakdown MEL / LAP / MNC (reference fit.py:597-601)
     log_path: Optional[str] = None  # JSON-lines file (appended); None with log_interval > 0 = stdout
 
     def __post_init__(self):
         if self.blur_sigma > 0 and self.norm_sigma > 0:
             raise ValueError("FitConfig.blur_sigma > 0 and norm_sigma > 0 exclude each other: an iteration has one pixel term")
+        if self.robust not in ('', 'l2', 'charbonnier', 'geman_mcclure'):
+            raise ValueError(f"FitConfig.robust must be '', 'l2', 'charbonnier' or 'geman_mcclure' (got {self.robust!r})")
+        if self.robust not in ('', 'l2') and self.robust_scale is None:
+            raise ValueError(f"FitConfig.robust={self.robust!r} needs robust_scale, in grey levels: there is no default")
+        try:
+            dr.robust_args(self.robust or 'l2', self.robust_scale, self.weight_outside, self.saturation)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"FitConfig (robust_scale, weight_outside, saturation): {e}")
+        if isinstance(self.robust_iters, bool) or int(self.robust_iters) != self.robust_iters or self.robust_iters < 0:
+            raise ValueError(f"FitConfig.robust_iters must be an integer >= 0 (got {self.robust_iters!r})")
+        if self.weights_configured() and (self.blur_sigma > 0 or self.norm_sigma > 0):
+            raise ValueError("FitConfig: robust, face_weights, saturation > 0 and weight_outside != 1 cannot be combined with blur_sigma > 0 "
+                             "or norm_sigma > 0: weighting the windowed losses is a different rule")
+
+    def weights_configured(self):
+        """Whether the options alone (without a Scene's masks) put iterations on the weighted robust pixel term."""
+        return bool(self.robust) or self.face_weights is not None or self.saturation > 0 or float(self.weight_outside) != 1.0
 
 
 def setup_dataset(blendshapes, n_frames, device):
@@ -696,6 +758,21 @@ class Fitter:
                                "iteration to the next", (cfg.norm_sigma,))
             if not (float(cfg.norm_eps) > 0.0 and float(cfg.norm_eps) < float('inf')):
                 raise ValueError(f"FitConfig.norm_eps must be finite and positive (got {cfg.norm_eps})")
+        # the weighted robust pixel term ("Robust loss rule"): what its options and a Scene's masks ask of the others
+        sc_masks = sc.masks if cfg.use_masks else None
+        self.face_w = None
+        if cfg.face_weights is not None:
+            self.face_w = torch.from_numpy(load_face_weights(cfg.face_weights, int(sc.pos_idx.shape[0]))).to(dev)
+        if cfg.weights_configured() or sc_masks is not None:
+            why = "the Scene's masks (use_masks=False ignores them)" if not cfg.weights_configured() else \
+                "robust / face_weights / saturation / weight_outside"
+            if not cfg.fused_loss:
+                raise ValueError(f"FitConfig: {why} need fused_loss=True: the robust loss replaces pixel_loss_fused")
+            if cfg.hip_graph:
+                raise ValueError(f"FitConfig: {why} cannot be combined with hip_graph: the step leaves the captured path, as a blurred one does")
+            if cfg.blur_sigma > 0 or cfg.norm_sigma > 0:
+                raise ValueError(f"FitConfig: {why} cannot be combined with blur_sigma > 0 or norm_sigma > 0: weighting the windowed losses "
+                                 "is a different rule")
         if cfg.hip_graph == 'auto':
             self.use_graph = self.auto_graph((cfg.frames_per_step or (self.frame_hi - self.frame_lo)) * (cfg.views_per_step or len(self.cam_idxs)),
                                              self.resolution)
@@ -785,14 +862,28 @@ class Fitter:
         self.target_bg_sumsq = dr.reference_background_sumsq(t.reshape(-1, *self.resolution), BACKGROUND).reshape(t.shape[:2])
         self._bg_sum_key = None      # (the cached sum over the whole shard, loss_and_backward)
         self.full_targets = self.targets      # (always the captures; `targets` is the active pyramid level's, the same tensor without one)
-        # ---- pyramid levels: per factor in use (targets, (H, W), target_bg_sumsq), each made from this rank's full-size targets ----
+        # ---- the masks of the captures, sharded and reduced exactly as the targets: 8 bit [F_local, n_cam, H, W], or None ----
+        self.masks = None
+        if sc_masks is not None:
+            take_res = tuple(sc.images.shape[2:]) if sc.images is not None else tuple(sc.resolution)
+            if tuple(sc_masks.shape) != (F, len(sc.cams)) + take_res or sc_masks.dtype != np.uint8:
+                raise ValueError(f"Scene.masks must be uint8 {(F, len(sc.cams)) + take_res} (got {sc_masks.dtype} {tuple(sc_masks.shape)})")
+            self.masks = torch.from_numpy(np.ascontiguousarray(sc_masks[self.frame_lo:self.frame_hi][:, self.cam_idxs])).to(dev)
+            if take_res != self.resolution:       # a fixed reduced size: the box mean is the fractional weight of a coarse pixel
+                self.masks = dr.downsample_images(self.masks, self._take_factor(take_res, self.resolution))
+            if tuple(self.masks.shape) != tuple(self.targets.shape):
+                raise ValueError(f"the masks {tuple(self.masks.shape)} do not match the targets {tuple(self.targets.shape)}")
+        self.full_masks = self.masks
+        self._wsum = None                     # (the sum of the weights of the last iteration on the robust term, for the step log)
+        # ---- pyramid levels: per factor in use (targets, (H, W), target_bg_sumsq, masks), each made from this rank's full-size targets ----
         self._levels, self._level = None, 1
         if self._pyramid:
-            self._levels = {1: (self.targets, self.resolution, self.target_bg_sumsq)}
+            self._levels = {1: (self.targets, self.resolution, self.target_bg_sumsq, self.masks)}
             for s in sorted({s for s, _ in self._pyramid if s > 1}):
                 lt = dr.downsample_images(self.full_targets, s)
                 lres = (self.resolution[0] // s, self.resolution[1] // s)
-                self._levels[s] = (lt, lres, dr.reference_background_sumsq(lt.reshape(-1, *lres), BACKGROUND).reshape(lt.shape[:2]))
+                lm = dr.downsample_images(self.full_masks, s) if self.full_masks is not None else None
+                self._levels[s] = (lt, lres, dr.reference_background_sumsq(lt.reshape(-1, *lres), BACKGROUND).reshape(lt.shape[:2]), lm)
         if cfg.init_texture == 'bake':
             self.bake_texture()
         if self._levels is not None:
@@ -846,7 +937,7 @@ class Fitter:
         caches keyed to them are dropped.  full_resolution / full_targets keep naming the captures."""
         if s == self._level:
             return
-        self.targets, self.resolution, self.target_bg_sumsq = self._levels[s]
+        self.targets, self.resolution, self.target_bg_sumsq, self.masks = self._levels[s]
         self.enable_mip = bool(self.cfg.enable_mip or (s > 1 and self.cfg.pyramid_mip))
         self._bg_sum_key, self._targets_f32 = None, None
         self._level = s
@@ -1119,6 +1210,18 @@ class Fitter:
         normalised.  A function of the iteration alone, so a resumed run continues on the right side of the switch."""
         return self._window_taps('norm', i)
 
+    def robust_term(self, i=None):
+        """(kind, scale) of the weighted robust pixel term at iteration i (default: the current one), or None when that iteration does not
+        use it: FitConfig.robust inside robust_iters, or kind 'l2' when only weights are on (masks in use, face_weights, saturation > 0,
+        weight_outside != 1).  A function of the iteration alone, so a resumed run continues on the right side of the switch."""
+        cfg = self.cfg
+        i = self.iteration if i is None else i
+        if cfg.robust and not (cfg.robust_iters and i >= cfg.robust_iters):
+            return cfg.robust, cfg.robust_scale
+        if self.full_masks is not None or self.face_w is not None or cfg.saturation > 0 or float(cfg.weight_outside) != 1.0:
+            return 'l2', None
+        return None
+
     def loss_and_backward(self, frame_ids, view_ids=None, validate=True):
         """Forward + backward of fit.py:556-611 for a batch of frames x cameras (view_ids: see mvp).  Returns the loss (tensor).
         validate: check a caller's index tensors on the host first (check_indices); step() passes False for its own draws."""
@@ -1140,8 +1243,10 @@ class Fitter:
         window = ('blur', self.blur_taps(i)) if cfg.blur_sigma > 0 else ('norm', self.norm_taps(i)) if cfg.norm_sigma > 0 else None
         if window is not None and window[1] is None:
             window = None
-        if window is not None:
-            one_shot = False           # a windowed loss needs the image in memory: the operator path
+        robust = self.robust_term(i)   # (kind, scale) of the weighted robust pixel term, or None (never together with a window: __init__)
+        self._wsum = None
+        if window is not None or robust is not None:
+            one_shot = False           # a windowed or a weighted loss needs the image in memory: the operator path
         # one flat buffer for the small accumulators of this step's backward kernels, zero-filled by the objective's first kernel; the
         # pool around it goes to the functions whose backward takes views of it
         zero_buf, pool = None, None
@@ -1216,7 +1321,12 @@ class Fitter:
             for term in terms:
                 loss = loss + term.detach()
         elif cfg.fused_loss:
-            if window is None:
+            if robust is not None:
+                mask = self._take(self.masks.reshape(-1, *self.resolution), 0, rows) if self.masks is not None else None
+                sum_sq, g_colour = pixel_loss_robust(colour, rast_out, ref, robust[0], robust[1], n_total, mask=mask, face_weights=self.face_w,
+                                                     weight_outside=cfg.weight_outside, saturation=cfg.saturation)
+                self._wsum = sum_sq[1]
+            elif window is None:
                 sum_sq, g_colour = pixel_loss_fused(colour, rast_out, ref, n_total)
             elif window[0] == 'blur':
                 sum_sq, g_colour = pixel_loss_blurred(colour, rast_out, ref, window[1], n_total)
@@ -1356,6 +1466,8 @@ class Fitter:
             now = time.perf_counter()
             rec = {"it": i, "frames": self._n(frame_ids) * self.world, "loss": float(loss),
                    "lr": [float(x) for x in self.scheduler.get_last_lr()]}
+            if self._wsum is not None:      # an iteration on the robust term: the sum of its weights (the effective entry count)
+                rec["wsum"] = float(self._wsum)
             if self._log_t is not None and i > self._log_it:
                 rec["frames_per_s"] = self._n(frame_ids) * self.world * (i - self._log_it) / (now - self._log_t)
             self._log_t, self._log_it = time.perf_counter(), i

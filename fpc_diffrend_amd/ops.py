@@ -30,7 +30,7 @@ from . import _lib
 
 __all__ = ['RasterizeGLContext', 'RasterizeCudaContext', 'RasterizeHipContext', 'rasterize', 'interpolate', 'texture',
            'texture_construct_mip', 'antialias', 'antialias_construct_topology_hash', 'render_textured', 'pixel_objective', 'undistort_images', 'compare_images',
-           'gaussian_taps', 'blurred_pixel_loss', 'normalised_pixel_loss', 'bake_accumulate', 'bake_resolve', 'downsample_images']
+           'gaussian_taps', 'blurred_pixel_loss', 'normalised_pixel_loss', 'robust_pixel_loss', 'bake_accumulate', 'bake_resolve', 'downsample_images']
 
 
 def _stream():
@@ -771,6 +771,95 @@ def normalised_pixel_loss(colour, rast, ref_u8, sigma=None, kernel_size=31, eps=
         taps = gaussian_taps(kernel_size, sigma)
     return _windowed_pixel_loss_func.apply(norm_loss_call, float(n_total or colour.numel()), colour, rast, ref_u8, taps, float(eps), True,
                                            background)
+
+
+def robust_args(kind, scale, weight_outside=1.0, saturation=0):
+    """The scalar arguments of the robust loss checked on the host: -> (kind number, inv_c as the float32 the kernel is handed,
+    weight_outside, saturation), or ValueError.  Needs no GPU."""
+    if kind not in _lib.ROBUST_KIND:
+        raise ValueError(f"kind must be one of {sorted(_lib.ROBUST_KIND)} (got {kind!r})")
+    inv_c = 0.0
+    if kind != 'l2':
+        if scale is None:
+            raise ValueError(f"kind {kind!r} needs a scale in grey levels: there is no default")
+        with np.errstate(over='ignore'):
+            inv_c = float(np.float32(1.0 / float(scale))) if float(scale) > 0.0 else 0.0      # float32(1 / c): the statement's number too
+        if not (float(scale) > 0.0 and float(scale) < float('inf') and 0.0 < inv_c < float('inf')):
+            raise ValueError(f"scale must be finite and positive, in grey levels (got {scale})")
+    weight_outside = float(weight_outside)
+    if not (weight_outside >= 0.0 and weight_outside < float('inf')):
+        raise ValueError(f"weight_outside must be finite and not negative (got {weight_outside})")
+    if isinstance(saturation, bool) or not isinstance(saturation, (int, np.integer)) or not 0 <= int(saturation) <= 255:
+        raise ValueError(f"saturation must be an integer in 0..255, 0 = off (got {saturation!r})")
+    return _lib.ROBUST_KIND[kind], inv_c, weight_outside, int(saturation)
+
+
+def robust_loss_call(colour, rast, ref_u8, kind, scale, grad_scale, mask=None, face_weights=None, weight_outside=1.0, saturation=0,
+                     background=45.0 / 255.0, want_grad=True, check_weights=True):
+    """One fpcdr_robust_loss call ("Robust loss rule"): -> (sums [2] f64 = (sum of w * rho, sum of w), grad_scale * d sums[0] /
+    d colour [B,H,W,C] or None).  kind 'l2' | 'charbonnier' | 'geman_mcclure', scale c in grey levels (ignored for 'l2'); mask uint8
+    [B,H,W], 255 = trust, 0 = ignore; face_weights float32 [T], finite and >= 0, looked up through the triangle id of rast (the check
+    of its values is a read-back; check_weights=False for a caller that has checked them once, as the Fitter has); weight_outside for
+    uncovered pixels; saturation 1..255: capture pixels at or above it count nothing.  The weights are constants: they get no gradient."""
+    kind_no, inv_c, weight_outside, saturation = robust_args(kind, scale, weight_outside, saturation)
+    if not (torch.is_tensor(colour) and colour.dim() == 4):
+        raise ValueError("colour must be a [B,H,W,C] tensor")
+    B, H, W, C = colour.shape
+    _check_tensor('colour', colour, torch.float32, 4)
+    _check_tensor('rast', rast, torch.float32, 4)
+    _check_tensor('ref_u8', ref_u8, torch.uint8, 3)
+    if tuple(rast.shape) != (B, H, W, 4) or tuple(ref_u8.shape) != (B, H, W):
+        raise ValueError(f"rast must be [B,H,W,4] and ref_u8 [B,H,W] for colour {tuple(colour.shape)}")
+    if mask is not None:
+        _check_tensor('mask', mask, torch.uint8, 3)
+        if tuple(mask.shape) != (B, H, W):
+            raise ValueError(f"mask must be [B,H,W] = {(B, H, W)} (got {tuple(mask.shape)})")
+        mask = mask.contiguous()
+    T = 0
+    if face_weights is not None:
+        _check_tensor('face_weights', face_weights, torch.float32, 1)
+        T = int(face_weights.shape[0])
+        if T == 0:
+            raise ValueError("face_weights must have one entry per triangle (got none)")
+        face_weights = face_weights.detach().contiguous()
+        if check_weights and not bool((torch.isfinite(face_weights) & (face_weights >= 0)).all()):
+            raise ValueError("face_weights must be finite and not negative")
+    colour, rast, ref_u8 = colour.detach().contiguous(), rast.detach().contiguous(), ref_u8.contiguous()
+    with torch.cuda.device(colour.device):
+        sums = torch.zeros(2, dtype=torch.float64, device=colour.device)
+        grad = torch.empty_like(colour) if want_grad else None
+        p = _lib.RobustLoss(color=_ptr(colour), rast=_ptr(rast), ref=_ptr(ref_u8), B=B, H=H, W=W, C=C, bg=float(background),
+                            color_scale=255.0, grad_scale=float(grad_scale), kind=kind_no, inv_c=inv_c, w_outside=weight_outside,
+                            sat=saturation, mask=_ptr(mask), face_w=_ptr(face_weights), T=T, sums=_ptr(sums), grad_color=_ptr(grad))
+        _lib.call("fpcdr_robust_loss", ctypes.byref(p), _stream())
+    return sums, grad
+
+
+class _robust_pixel_loss_func(torch.autograd.Function):
+    """The mean over n_total of one robust_loss_call, and the gradient the same call computed, times the upstream scalar, as the backward."""
+    @staticmethod
+    def forward(ctx, colour, rast, ref_u8, n_total, kind, scale, kwargs):
+        sums, grad = robust_loss_call(colour, rast, ref_u8, kind, scale, 1.0 / n_total, **kwargs)
+        ctx.save_for_backward(grad)
+        return (sums[0] / n_total).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        return (grad * upstream, None, None, None, None, None, None)
+
+
+def robust_pixel_loss(colour, rast, ref_u8, kind='charbonnier', scale=None, n_total=None, mask=None, face_weights=None, weight_outside=1.0,
+                      saturation=0, background=45.0 / 255.0):
+    """sum of w * rho(ref - 255 * (rast.w > 0 ? colour : background)) over n_total elements (default: all of colour), rho the robust
+    function `kind` with scale c = `scale` in grey levels -- like d^2 for |d| << c, 2 c |d| ('charbonnier') or c^2 ('geman_mcclure') for
+    |d| >> c -- and w the product of the weights given ("Robust loss rule"; fpcdr_robust_loss).  The division is by
+    n_total, not by the sum of the weights.  A float32 scalar whose backward is the closed-form gradient the same call computed, times
+    the upstream scalar.  There is no default scale: nobody has measured one."""
+    kwargs = dict(mask=mask, face_weights=face_weights, weight_outside=weight_outside, saturation=saturation, background=background)
+    if not (torch.is_tensor(colour) and colour.dim() == 4):
+        raise ValueError("colour must be a [B,H,W,C] tensor")
+    return _robust_pixel_loss_func.apply(colour, rast, ref_u8, float(n_total or colour.numel()), kind, scale, kwargs)
 
 
 def undistort_images(images, intr, dist, clip_max=255, flip_rows=False):

@@ -41,6 +41,8 @@ class Scene:
     images: Optional[np.ndarray] = None      # [F,Ncam,H,W] uint8: reference images as the reference's loader leaves them
                                              # (fit.py:529-533: clipped to [0,140], row 0 = bottom)
     frames: int = 0                          # number of frames when there is no ground truth to count
+    masks: Optional[np.ndarray] = None       # [F,Ncam,H,W] uint8, row 0 = bottom: 255 = trust this pixel of the capture, 0 = ignore it
+                                             # (the robust pixel loss, DESIGN.md 3 "Robust loss rule"); None = no masks
 
     @property
     def n_vertices(self):
@@ -212,7 +214,29 @@ def _undistorted_chunks(imdir, cams, lookup, n_frames, digits, device, clip_max,
         yield f0, out.cpu().numpy()
 
 
-def from_take(basemeshpath, localblpath, calibpath, imdir, texpath="", texshape=(1024, 1024, 1), seed=0, undistort=False, device='cuda'):
+def load_masks(maskdir, cams, n_frames, digits, resolution):
+    """The masks of a take, laid out like its images (the same camera directories and file names): 8-bit single channel, 255 = trust,
+    0 = ignore -> [F,Nc,H,W] uint8 with the rows flipped like the images and the values as they are (never clipped).  A missing file, a
+    file that is not 8-bit single channel or a size other than the images' is a ValueError that names the file."""
+    from PIL import Image
+    H, W = resolution
+    masks = np.empty((n_frames, len(cams), H, W), dtype=np.uint8)
+    for c, cam in enumerate(cams):
+        for f in range(n_frames):
+            path = os.path.join(maskdir, cam, f"{cam}_{f:0{digits}d}.tif")
+            if not os.path.isfile(path):
+                raise ValueError(f"{path}: the mask of camera {cam}, frame {f} is missing")
+            m = np.array(Image.open(path))
+            if m.dtype != np.uint8 or m.ndim != 2:
+                raise ValueError(f"{path}: a mask is an 8-bit single-channel image (got dtype {m.dtype}, shape {m.shape})")
+            if m.shape != (H, W):
+                raise ValueError(f"{path}: the mask is {m.shape[0]} x {m.shape[1]}, the images are {H} x {W}")
+            masks[f, c] = np.flip(m, 0)
+    return masks
+
+
+def from_take(basemeshpath, localblpath, calibpath, imdir, texpath="", texshape=(1024, 1024, 1), seed=0, undistort=False, device='cuda',
+              maskdir=''):
     """A take on disk in the reference's layout -> Scene (reference fit.py:415-439, 461, 514-533):
 
       basemeshpath  base mesh .obj (v / vt / f v/vt triangles)                       fit.py:424-432, data.py:7-39
@@ -230,7 +254,11 @@ def from_take(basemeshpath, localblpath, calibpath, imdir, texpath="", texshape=
     distortion currently handled as preprocess in reference images", fit.py:540); here each chunk of frames goes through
     ops.undistort_images on `device` with the calibration's five `distortion` coefficients -- before the clip and the flip, as there
     -- and comes back into the Scene's host array.  It needs the GPU (RuntimeError without one).  Off by default: the reference's
-    shipped calibration has all-zero coefficients and its takes are undistorted already."""
+    shipped calibration has all-zero coefficients and its takes are undistorted already.
+
+    maskdir: a directory laid out like imdir (the same camera directories and file names) of 8-bit single-channel masks, 255 = trust
+    this pixel, 0 = ignore it (load_masks): flipped like the images, never clipped, kept in Scene.masks for the robust pixel loss.  They
+    belong to the images as they are read: with undistort=True supply masks of the undistorted views."""
     cams = sorted(os.listdir(imdir))
     n_frames, digits = data.assert_num_frames(cams, imdir)
     base = data.MeshData(basemeshpath)
@@ -258,8 +286,9 @@ def from_take(basemeshpath, localblpath, calibpath, imdir, texpath="", texshape=
     else:
         tex = np.random.default_rng(seed).uniform(low=0.0, high=1.0, size=texshape)   # fit.py:438 (seeded here)
     blend = data.load_blendshape_deltas(localblpath, base.vertices)
+    masks = load_masks(maskdir, cams, n_frames, digits, (H, W)) if maskdir else None
     return Scene(v_base=base.vertices, pos_idx=base.faces, uv=base.uv, uv_idx=base.fuv, blendshapes=blend,
-                 texture=np.ascontiguousarray(tex, dtype=np.float32), cams=lookup, resolution=(H, W), images=images)
+                 texture=np.ascontiguousarray(tex, dtype=np.float32), cams=lookup, resolution=(H, W), images=images, masks=masks)
 
 
 def undistort_take(imdir, calibpath, out_dir, device='cuda'):
@@ -278,12 +307,13 @@ def undistort_take(imdir, calibpath, out_dir, device='cuda'):
     return out_dir
 
 
-def write_take(sc, directory, images, cam_idxs=None, blendshape_scale=1.0, distortion=None):
+def write_take(sc, directory, images, cam_idxs=None, blendshape_scale=1.0, distortion=None, masks=None):
     """Write a Scene + reference images [F,Nc,H,W] uint8 (row 0 = bottom) to `directory` in the layout `from_take`
     reads (the reference's, fit.py:415-432, 514-533): basemesh.obj, blendshapes/*.obj, calibration.json,
     images/cam_<name>/cam_<name>_<frame>.tif.  Returns the four paths.  (Test / example helper: the reference ships
     no data.)  distortion: optional [Nc,5] (k1, k2, p1, p2, k3), one row per camera of cam_idxs, written as each camera's
-    `distortion`; None writes zeros."""
+    `distortion`; None writes zeros.  masks: optional [F,Nc,H,W] uint8 (row 0 = bottom), written to <directory>/masks under the
+    images' camera directories and file names -- the `maskdir` of from_take; the four returned paths stay what they were."""
     import json
     from PIL import Image
     cam_idxs = list(range(len(sc.cams))) if cam_idxs is None else list(cam_idxs)
@@ -324,6 +354,15 @@ def write_take(sc, directory, images, cam_idxs=None, blendshape_scale=1.0, disto
         os.makedirs(os.path.join(imdir, name), exist_ok=True)
         for fr in range(F):
             Image.fromarray(np.flip(np.asarray(images[fr, j]), 0)).save(os.path.join(imdir, name, f"{name}_{fr:0{digits}d}.tif"))
+    if masks is not None:
+        masks = np.asarray(masks)
+        assert masks.dtype == np.uint8 and masks.shape == tuple(np.asarray(images).shape), \
+            f"masks must be uint8 {tuple(np.asarray(images).shape)} like the images, got {masks.dtype} {masks.shape}"
+        for j, c in enumerate(cam_idxs):
+            name = f"cam_{sc.cams[c]['cam']}"
+            os.makedirs(os.path.join(directory, "masks", name), exist_ok=True)
+            for fr in range(F):
+                Image.fromarray(np.flip(masks[fr, j], 0)).save(os.path.join(directory, "masks", name, f"{name}_{fr:0{digits}d}.tif"))
     return base, bldir, calibpath, imdir
 
 

@@ -713,6 +713,50 @@ struct fpcdr_norm_loss_params {
 size_t fpcdr_norm_loss_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t C);
 int fpcdr_norm_loss(const fpcdr_norm_loss_params *p, void *stream);
 
+/* Weighted robust pixel loss: a pixel term that can be told "do not trust these pixels", "do not trust these triangles" and "large
+ * residuals are outliers" (the reference's only defence is np.clip(img, 0, 140) at src/torch/fit.py:531; utils.py:12-35 carries
+ * reduceHighlights / normalize_highlights and wires neither).  A pure addition: FPCDR_ABI_VERSION stays 16.  DESIGN.md 3, "Robust loss
+ * rule".  Per image, pixel and channel, in float32, unfused, every operation rounded once (IEEE square root and divisions):
+ *   covered = rast.w > 0        a = color_scale * (covered ? color : bg)        d = (float)ref - a        z = d * inv_c        t = z * z
+ *   L2:             rho = d * d                                  s = 1
+ *   CHARBONNIER:    h = sqrt(1 + t),  rho = (2 (d * d)) / (1 + h),  s = 1 / h           = 2 c^2 (sqrt(1 + d^2 / c^2) - 1), without the cancellation
+ *   GEMAN_MCCLURE:  k = 1 + t,        rho = (d * d) / k,            s = 1 / (k * k)
+ *   psi = d * s                                                                          = rho'(d) / 2
+ *   wm  = mask ? (float)mask * float32(1 / 255) : 1;   wm = 0 where sat > 0 and ref >= sat
+ *   w   = covered ? wm * (face_w ? (0 <= id - 1 < T ? face_w[id - 1] : 0) : 1) : wm * w_outside,      id = (int)rast.w
+ *   sums[0] += w * rho,  sums[1] += w                 two float64, accumulated with atomics (lane float32 -> wave -> block, as fpcdr_pixel_loss)
+ *   grad_color = covered ? (-2 * color_scale * grad_scale) * (w * psi) : 0
+ * The weights are constants of the call.  With kind L2, no mask, no face_w, sat 0 and w_outside 1 the gradient is fpcdr_pixel_loss's bit
+ * for bit.  grad_color may be NULL: then only the sums are computed.  grad_color is written by plain stores, every entry once:
+ * bit-identical from run to run.  The byte buffers may sit at any address (16-byte loads are used where base and length allow), the
+ * float buffers at any multiple of 4.
+ * Errors, before any launch: a NULL params, color, rast, ref or sums; sizes <= 0; an unknown kind; inv_c not finite or <= 0 for a kind
+ * other than L2; w_outside negative or not finite; sat outside 0 .. 255; face_w with T <= 0; a float buffer that is not 4-byte aligned
+ * or sums not 8-byte aligned. */
+#define FPCDR_ROBUST_L2 0
+#define FPCDR_ROBUST_CHARBONNIER 1
+#define FPCDR_ROBUST_GEMAN_MCCLURE 2
+typedef struct fpcdr_robust_loss_params fpcdr_robust_loss_params;
+struct fpcdr_robust_loss_params {
+    const float *color;    /* [B,H,W,C] */
+    const float *rast;     /* [B,H,W,4]; covered = rast.w > 0, rast.w = triangle id + 1 */
+    const uint8_t *ref;    /* [B,H,W] 8-bit capture, broadcast over C */
+    int32_t B, H, W, C;
+    float bg;              /* background colour, reference 45/255 */
+    float color_scale;     /* reference 255 */
+    float grad_scale;      /* 1 / (number of elements of the global mean) */
+    int32_t kind;          /* FPCDR_ROBUST_* */
+    float inv_c;           /* float32(1 / c), c the scale in grey levels; ignored for L2 */
+    float w_outside;       /* weight of uncovered pixels, finite and >= 0; 1 = as fpcdr_pixel_loss */
+    int32_t sat;           /* 1 .. 255: capture pixels >= sat get weight 0; 0 = off */
+    const uint8_t *mask;   /* [B,H,W] 255 = trust, 0 = ignore, or NULL */
+    const float *face_w;   /* [T] one weight per triangle, finite and >= 0, or NULL */
+    int32_t T;             /* entries of face_w */
+    double *sums;          /* accumulated, two f64: sum of w * rho, sum of w */
+    float *grad_color;     /* out [B,H,W,C], or NULL */
+};
+int fpcdr_robust_loss(const fpcdr_robust_loss_params *p, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
