@@ -1,8 +1,10 @@
 // The mesh regularisers of the fit step for gfx950 (MI355X): the uniform Laplacian (gather, and the penalty forward and backward), the
-// stretch term and the bending term.  The three penalties share one contract: the value kernel's workgroups add float partials to their
-// mesh's double accumulator (block_add_f64), and one finish kernel behind the kernel boundary (k_penalty_finish) forms per_f and the
-// value and leaves the accumulators zero for the next call.
+// stretch term, the bending term and the motion term across the frames.  The penalties share one contract: the value kernel's workgroups
+// add float partials to their mesh's double accumulator (block_add_f64), and one finish kernel behind the kernel boundary
+// (k_penalty_finish) forms per_f and the value and leaves the accumulators zero for the next call.
 #include "common.h"
+
+#include <cmath>
 
 namespace {
 
@@ -341,6 +343,78 @@ __global__ void __launch_bounds__(256) k_bend_gather(const float *__restrict__ h
     o[0] = sx; o[1] = sy; o[2] = sz;
 }
 
+// The motion term ("Motion rule"): the step's meshes held smooth in TIME, a difference across the frames of one vertex,
+//   ORDER 2: a_f = x_{f-1} - 2 x_f + x_{f+1}   (m_f = 1 iff both neighbours are in the call and one frame number away)
+//   ORDER 1: a_f = x_{f+1} - x_f               (m_f = 1 iff frame f + 1 is in the call and one frame number away)
+//   s = |a|^2,  rho(s) = s  (ic = 0)  or  2 c^2 (sqrt(1 + s / c^2) - 1) in the form without the cancellation (csrc/robust.hip),
+//   per_f = m_f / V sum_v w_v rho(s_{f,v}),   value = weight / F * sum_f per_f.
+// One lane per (frame, vertex), not one per vertex walking the frames: at V = 15 k the walk is 59 workgroups for 256 CUs, each a chain
+// of F dependent rounds; the grid of F x V / 256 workgroups fills the chip at every size the fit uses, and the price -- every position is
+// read by the lanes of up to 2 ORDER + 1 frames -- is paid in L2 (32 x 15002 x 12 bytes = 5.8 MB).  The lane forms the stencils centred
+// on f - 1, f, f + 1 (ORDER 1: on f - 1, f) from x at f - ORDER .. f + ORDER of its own vertex: its own stencil gives the value partial,
+// all of them give the gradient  coef * (b_{f-1} - 2 b_f + b_{f+1})  (ORDER 1: coef * (b_{f-1} - b_f)),  b = m w rho'(s) a,
+// coef = 2 weight / (F V) -- a gather: no float atomics, no scratch, every entry stored once.  The frame numbers are read here, on the
+// device (frame_t null: consecutive), block-uniform: a captured step whose subset changes per replay replays correctly.  A frame index
+// outside 0 .. F - 1 is clamped for the load (in bounds, whatever the flags) and its stencils are switched off by SELECTS, not by a
+// product with 0, so that a NaN in a frame no valid stencil reaches stays where it is.  Constant indices only: no private segment.
+template <int ORDER>
+__global__ void __launch_bounds__(256) k_motion_penalty(const float *__restrict__ x, const int64_t *__restrict__ frame_t,
+                                                        const float *__restrict__ vertex_w, float ic, int F, int V, float coef,
+                                                        float *__restrict__ grad_x, double *__restrict__ acc) {
+    constexpr int NF = 2 * ORDER + 1;      // the frames f - ORDER .. f + ORDER, slot k = frame f - ORDER + k
+    const int f = blockIdx.y;
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    // step[k]: the slots k and k + 1 are both frames of the call, one frame number apart
+    bool step[NF - 1];
+#pragma unroll
+    for (int k = 0; k < NF - 1; ++k) {
+        const int g = f - ORDER + k;
+        const bool in = g >= 0 && g + 1 < F;
+        const int gc = in ? g : 0;
+        step[k] = in && (frame_t ? frame_t[gc + 1] - frame_t[gc] == 1 : true);
+    }
+    float value = 0.0f;      // (a lane without a vertex: 0)
+    if (v < V) {
+        float p[NF][3];
+#pragma unroll
+        for (int k = 0; k < NF; ++k) {
+            const int g = min(max(f - ORDER + k, 0), F - 1);
+            const float *xg = x + ((size_t)g * V + v) * 3;
+            p[k][0] = xg[0]; p[k][1] = xg[1]; p[k][2] = xg[2];
+        }
+        const float w = vertex_w ? vertex_w[v] : 1.0f;
+        // the stencils: ORDER 2 centred on the slots 1, 2, 3 (the lane's own: 2), ORDER 1 from the slots 0, 1 (the lane's own: 1)
+        constexpr int NS = ORDER == 2 ? 3 : 2, OWN = 1;
+        float b[NS][3];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const bool m = ORDER == 2 ? (step[j] && step[j + 1]) : step[j];
+            float a[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)      // (two differences of neighbouring positions, each exact where the positions are within a factor of 2)
+                a[i] = ORDER == 2 ? (p[j][i] - p[j + 1][i]) + (p[j + 2][i] - p[j + 1][i]) : p[j + 1][i] - p[j][i];
+            const float s = a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
+            float rho = s, d = 1.0f;
+            if (ic > 0.0f) {
+                const float zx = a[0] * ic, zy = a[1] * ic, zz = a[2] * ic;
+                const float h = sqrtf(1.0f + (zx * zx + zy * zy + zz * zz));
+                rho = (2.0f * s) / (1.0f + h);
+                d = 1.0f / h;
+            }
+            const float q = w * d;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) b[j][i] = m ? q * a[i] : 0.0f;
+            if (j == OWN) value = m ? w * rho : 0.0f;
+        }
+        if (grad_x) {
+            float *o = grad_x + ((size_t)f * V + v) * 3;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) o[i] = coef * (ORDER == 2 ? (b[0][i] + b[2][i]) - 2.0f * b[1][i] : b[0][i] - b[1][i]);
+        }
+    }
+    block_add_f64(value, &acc[f]);
+}
+
 // (both Laplacian forward entries; rest_lap null: the plain term)
 void lap_penalty_fwd(const float *x, const int32_t *nbr, const float *inv_deg, const float *rest_lap, float *lap, void *acc, float *per,
                      float *out, float weight, int32_t F, int32_t V, int32_t D, void *stream) {
@@ -411,6 +485,26 @@ extern "C" int fpcdr_stretch_penalty(const float *x, const int32_t *nbr, const f
     hipLaunchKernelGGL(k_stretch_penalty, dim3(fpcdr_cdiv(V, 256), F), dim3(256), 0, (hipStream_t)stream, x, nbr, rest_len, target, V, D, coef,
                        grad_x, (double *)acc);
     hipLaunchKernelGGL(k_penalty_finish<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, (double *)acc, F, 2.0 * (double)E, weight, per, out);
+    FPCDR_CHECK_LAUNCH();
+    return FPCDR_OK;
+}
+
+extern "C" int fpcdr_motion_penalty(const float *x, const int64_t *frame_t, const float *vertex_w, float inv_c, int32_t order, float *grad_x,
+                                    void *acc, float *per, float *out, float weight, int32_t F, int32_t V, void *stream) {
+    FPCDR_REQUIRE(x && acc && per && out, "null pointer");
+    FPCDR_REQUIRE(F > 0 && V > 0 && F <= 65535, "bad sizes");
+    FPCDR_REQUIRE(order == 1 || order == 2, "order must be 1 or 2");
+    FPCDR_REQUIRE(std::isfinite(inv_c) && inv_c >= 0.0f, "inv_c = 1 / scale must be finite and not negative (0: L2)");
+    FPCDR_REQUIRE(((size_t)acc & 7) == 0, "acc must be 8-byte aligned");
+    const float coef = 2.0f * weight / ((float)F * (float)V);
+    const dim3 grid(fpcdr_cdiv(V, 256), F);
+    if (order == 2)
+        hipLaunchKernelGGL(k_motion_penalty<2>, grid, dim3(256), 0, (hipStream_t)stream, x, frame_t, vertex_w, inv_c, F, V, coef, grad_x,
+                           (double *)acc);
+    else
+        hipLaunchKernelGGL(k_motion_penalty<1>, grid, dim3(256), 0, (hipStream_t)stream, x, frame_t, vertex_w, inv_c, F, V, coef, grad_x,
+                           (double *)acc);
+    hipLaunchKernelGGL(k_penalty_finish<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, (double *)acc, F, (double)V, weight, per, out);
     FPCDR_CHECK_LAUNCH();
     return FPCDR_OK;
 }

@@ -35,8 +35,8 @@ import torch
 from . import _lib, camera
 from . import ops as dr
 from .mesh_reg import (MeshTopology, RestShape, _uniform_laplacian, bend_penalty, hinge_incidence, hinge_rest_cs, hinge_vertices,
-                       laplacian_penalty, mesh_edge_loss, mesh_laplacian_smoothing, mesh_normal_consistency, rest_edge_lengths,
-                       stretch_penalty)
+                       laplacian_penalty, mesh_edge_loss, mesh_laplacian_smoothing, mesh_normal_consistency, motion_inv_scale,
+                       motion_penalty, rest_edge_lengths, stretch_penalty)
 from .ops import _ptr, _stream
 
 BACKGROUND = 45.0 / 255.0  # reference fit.py:161
@@ -296,21 +296,44 @@ def pixel_loss_robust(colour, rast_out, ref_u8, kind, scale, n_total=None, mask=
                                weight_outside=weight_outside, saturation=saturation, background=BACKGROUND, check_weights=False)
 
 
+def _load_weights(weights, n, option, item):
+    """FitConfig.<option> -- an array-like [n] or the path of a text file with one number per <item> -- as a float32 array [n], or
+    ValueError: another length, an entry that is not finite or is negative."""
+    if isinstance(weights, (str, os.PathLike)):
+        try:
+            w = np.loadtxt(weights, dtype=np.float64, ndmin=1)
+        except (OSError, ValueError) as e:
+            raise ValueError(f"FitConfig.{option}: cannot read {weights}: {e}")
+    else:
+        w = np.asarray(weights, dtype=np.float64)
+    if w.ndim != 1 or w.shape[0] != n:
+        raise ValueError(f"FitConfig.{option} holds one number per {item}: expected [{n}], got shape {tuple(w.shape)}")
+    if not (np.isfinite(w).all() and (w >= 0).all()):
+        raise ValueError(f"FitConfig.{option} must be finite and not negative")
+    return w.astype(np.float32)
+
+
 def load_face_weights(face_weights, n_faces):
     """FitConfig.face_weights -- an array-like [T] or the path of a text file with one number per face -- as a float32 array [T], or
     ValueError: another length than the mesh has faces, an entry that is not finite or is negative."""
-    if isinstance(face_weights, (str, os.PathLike)):
-        try:
-            w = np.loadtxt(face_weights, dtype=np.float64, ndmin=1)
-        except (OSError, ValueError) as e:
-            raise ValueError(f"FitConfig.face_weights: cannot read {face_weights}: {e}")
-    else:
-        w = np.asarray(face_weights, dtype=np.float64)
-    if w.ndim != 1 or w.shape[0] != n_faces:
-        raise ValueError(f"FitConfig.face_weights holds one number per face: expected [{n_faces}], got shape {tuple(w.shape)}")
-    if not (np.isfinite(w).all() and (w >= 0).all()):
-        raise ValueError("FitConfig.face_weights must be finite and not negative")
-    return w.astype(np.float32)
+    return _load_weights(face_weights, n_faces, 'face_weights', 'face')
+
+
+def load_motion_vertex_weights(vertex_weights, n_vertices):
+    """FitConfig.motion_vertex_weights -- an array-like [V] or the path of a text file with one number per vertex, read as
+    load_face_weights reads its file -- as a float32 array [V], or ValueError."""
+    return _load_weights(vertex_weights, n_vertices, 'motion_vertex_weights', 'vertex')
+
+
+def motion_options(cfg, n_vertices, n_local):
+    """What FitConfig.weight_motion > 0 asks of the other options, of the mesh (n_vertices) and of a rank's shard (n_local frames), or
+    ValueError; -> (inv_c: the float32 inverse of motion_scale, 0.0 without one; the vertex weights as a float32 array [V], or None)."""
+    need = cfg.motion_order + 1
+    if n_local < need:
+        raise ValueError(f"FitConfig.weight_motion > 0 with motion_order={cfg.motion_order} needs at least {need} frames in a rank's shard "
+                         f"(this one has {n_local}): the stencils end at the shard's borders")
+    w = None if cfg.motion_vertex_weights is None else load_motion_vertex_weights(cfg.motion_vertex_weights, n_vertices)
+    return motion_inv_scale(cfg.motion_scale), w
 
 
 def _check_window_term(cfg, kind, name, graph_why, sigmas):
@@ -559,6 +582,17 @@ class FitConfig:
                                     # gradient from one call in front of the objective.  0 = off: nothing changes
     weight_bend: float = 0.0        # > 0: every hinge is held to its dihedral angle in the base mesh ("Bend rule"), value and
                                     # gradient from one call in front of the objective.  0 = off: nothing changes
+    weight_motion: float = 0.0      # > 0: the step's meshes are held smooth in TIME ("Motion rule"): every vertex's
+                                    # acceleration (or velocity) across adjacent frames of the step is penalised, in head-local space -- the
+                                    # per-frame pose is not touched.  Frames of different ranks are not coupled; a random subset
+                                    # (frames_per_step) couples only the frames it draws that are adjacent in the take.  0 = off: nothing
+                                    # changes, no launch, no allocation
+    motion_order: int = 2           # 2: acceleration x_{f-1} - 2 x_f + x_{f+1} (constant velocity is free);  1: velocity x_{f+1} - x_f
+    motion_scale: Optional[float] = None     # the Charbonnier scale c in the mesh's length units, finite and > 0: quadratic below c, linear
+                                    # above it, so that a blink or a plosive is not smoothed away.  None: plain squares.  No default value --
+                                    # nobody has measured one
+    motion_vertex_weights: object = None     # one weight per vertex, finite and >= 0 (0: lips and eyelids left free; large: skull and neck
+                                    # held stiff): an array-like [V] or the path of a text file with one number per vertex
     cam_idxs: Sequence[int] = (0, 1, 2, 3, 4, 5, 6, 7, 8)
     mode: str = "prior"
     regularize_correctives: bool = False
@@ -655,6 +689,15 @@ class FitConfig:
         if self.weights_configured() and (self.blur_sigma > 0 or self.norm_sigma > 0):
             raise ValueError("FitConfig: robust, face_weights, saturation > 0 and weight_outside != 1 cannot be combined with blur_sigma > 0 "
                              "or norm_sigma > 0: weighting the windowed losses is a different rule")
+        if isinstance(self.motion_order, bool) or self.motion_order not in (1, 2):
+            raise ValueError(f"FitConfig.motion_order must be 1 (velocity) or 2 (acceleration) (got {self.motion_order!r})")
+        try:
+            motion_inv_scale(self.motion_scale)
+        except ValueError as e:
+            raise ValueError(f"FitConfig.motion_scale: {e}")
+        if self.weight_motion and 0 < self.frames_per_step < self.motion_order + 1:
+            raise ValueError(f"FitConfig.weight_motion > 0 with motion_order={self.motion_order} needs frames_per_step = 0 or >= "
+                             f"{self.motion_order + 1} (got {self.frames_per_step}): fewer frames hold no stencil")
 
     def weights_configured(self):
         """Whether the options alone (without a Scene's masks) put iterations on the weighted robust pixel term."""
@@ -697,6 +740,7 @@ class Fitter:
         from . import dist as _fdist
         self.n_frames = F
         self.frame_lo, self.frame_hi = _fdist.shard_frames(F, rank, world)      # (raises when F does not divide evenly over the ranks)
+        motion = motion_options(cfg, sc.n_vertices, self.frame_hi - self.frame_lo) if cfg.weight_motion else None      # (or ValueError)
         self.resolution = tuple(cfg.resolution or sc.resolution)
         self.full_resolution = self.resolution      # (the captures' size; `resolution` is the active pyramid level's, the same without one)
         self._pyramid = self._check_pyramid(cfg, self.resolution)
@@ -829,21 +873,31 @@ class Fitter:
             n_hinges = self.topo.hinges()[2]
             assert self.rest.bend_cs.shape == (2, n_hinges)      # (built here, not in the first step)
             self._bnd_scratch = torch.empty(max((self.frame_hi - self.frame_lo) * n_hinges * 12, 1), dtype=torch.float32, device=dev)
-        # The step's eager terms, vtx [Fb,V,3] -> scalar, in the fixed order Laplacian, stretch, bend.  Each makes its gradient with its
-        # value (it depends on the vertices only) and hands the buffer over in backward(); its weight carries the 1 / world, so that
-        # d loss / d term = 1 exactly.  ONE accumulator buffer serves all three: the calls are ordered on the step's one stream, and each
-        # leaves the buffer zero (the finish kernel of csrc/mesh_reg.hip).
+        # The step's eager terms, (vtx [Fb,V,3], the step's frame numbers: None for the whole contiguous shard, else the sorted int64 device
+        # tensor) -> scalar, in the fixed order Laplacian, stretch, bend, motion.  Each makes its gradient with its value (it depends on the
+        # vertices only) and hands the buffer over in backward(); its weight carries the 1 / world, so that d loss / d term = 1 exactly.
+        # ONE accumulator buffer serves them all: the calls are ordered on the step's one stream, and each leaves the buffer zero (the
+        # finish kernel of csrc/mesh_reg.hip).
         self._reg_acc = torch.zeros(self.frame_hi - self.frame_lo + 1, dtype=torch.float64, device=dev)
         eager = dict(eager_grad=True, unit_upstream=True, acc=self._reg_acc)
         self._reg_terms = []
         if cfg.weight_laplacian and cfg.fused_loss:      # (two launches, ~25 us in front of the objective)
             lap_rest = self.rest if cfg.laplacian_relative else None
-            self._reg_terms.append(lambda vtx: laplacian_penalty(vtx, self.topo, cfg.weight_laplacian / world, rest=lap_rest, **eager))
+            self._reg_terms.append(lambda vtx, ids: laplacian_penalty(vtx, self.topo, cfg.weight_laplacian / world, rest=lap_rest, **eager))
         if cfg.weight_stretch:
-            self._reg_terms.append(lambda vtx: stretch_penalty(vtx, self.topo, cfg.weight_stretch / world, rest=self.rest, **eager))
+            self._reg_terms.append(lambda vtx, ids: stretch_penalty(vtx, self.topo, cfg.weight_stretch / world, rest=self.rest, **eager))
         if cfg.weight_bend:
-            self._reg_terms.append(lambda vtx: bend_penalty(vtx, self.topo, cfg.weight_bend / world, rest=self.rest,
-                                                            scratch=self._bnd_scratch, **eager))
+            self._reg_terms.append(lambda vtx, ids: bend_penalty(vtx, self.topo, cfg.weight_bend / world, rest=self.rest,
+                                                                 scratch=self._bnd_scratch, **eager))
+        # the motion term couples the step's own meshes: this rank's frames only (its stencils end at the shard's borders), and of a random
+        # subset the frames adjacent in the take (the kernel reads the frame numbers on the device: pick_frames' are sorted and distinct)
+        self._motion_w = None
+        if cfg.weight_motion:
+            _, w = motion
+            self._motion_w = None if w is None else torch.from_numpy(w).to(dev)
+            self._reg_terms.append(lambda vtx, ids: motion_penalty(vtx, cfg.weight_motion / world, frame_ids=ids, order=cfg.motion_order,
+                                                                   scale=cfg.motion_scale, vertex_weights=self._motion_w, validate=False,
+                                                                   **eager))
         self._result_pending = None
         self.iteration = 0
         self._log_file, self._log_t, self._log_it = None, None, 0
@@ -1293,8 +1347,10 @@ class Fitter:
             reg = reg + torch.mean(mi ** 2)
         if self.world > 1 and chain_terms:
             reg = reg / self.world
-        # the eager terms (Laplacian, stretch, bend: __init__), their gradients made here with their values
-        terms = [term(vtx_pos_split) for term in self._reg_terms]
+        # the eager terms (Laplacian, stretch, bend, motion: __init__), their gradients made here with their values; a slice of frames is
+        # consecutive (no frame numbers to hand over), an index tensor names them
+        step_ids = frame_ids if torch.is_tensor(frame_ids) else None
+        terms = [term(vtx_pos_split, step_ids) for term in self._reg_terms]
         self.optimizer.zero_grad(set_to_none=True)
         if one_shot:
             bg_sum = None
@@ -1481,6 +1537,10 @@ class Fitter:
                 rec["STR"] = float(stretch_penalty(v, self.topo, cfg.weight_stretch, rest=self.rest)) if cfg.weight_stretch else 0.0
                 rec["BND"] = float(bend_penalty(v, self.topo, cfg.weight_bend, rest=self.rest)) if cfg.weight_bend else 0.0
                 rec["MNC"] = float(cfg.weight_normalconsistency * mesh_normal_consistency(v, self.topo))
+                if cfg.weight_motion:      # (only with the term on: without it a record is what it was)
+                    rec["MOT"] = float(motion_penalty(v, cfg.weight_motion, frame_ids=frame_ids if torch.is_tensor(frame_ids) else None,
+                                                      order=cfg.motion_order, scale=cfg.motion_scale, vertex_weights=self._motion_w,
+                                                      validate=False))
         if rec is None:
             return
         line = json.dumps(rec)

@@ -1,8 +1,8 @@
 """
 Mesh regularisers (pytorch3d in the reference: fit.py:16-19, 578-582): the static tables of a triangle list (MeshTopology, the hinge
-tables, RestShape), the torch restatements of the reference's terms, and the three penalties whose device code is csrc/mesh_reg.hip
-(laplacian_penalty, stretch_penalty, bend_penalty).  fit.py imports these names: fit.MeshTopology, fit.laplacian_penalty, ... remain the
-documented spelling.
+tables, RestShape), the torch restatements of the reference's terms, and the penalties whose device code is csrc/mesh_reg.hip
+(laplacian_penalty, stretch_penalty, bend_penalty within a mesh, motion_penalty across the frames).  fit.py imports these names:
+fit.MeshTopology, fit.laplacian_penalty, ... remain the documented spelling.
 """
 import numpy as np
 import torch
@@ -157,7 +157,7 @@ def mesh_laplacian_smoothing(verts, topo, per_mesh=False, rest=None):
 
 
 class _penalty(torch.autograd.Function):
-    """The host path the three penalties share.  Each is one C-ABI call that ends in the finish kernel (csrc/mesh_reg.hip), and each can
+    """The host path the penalties share.  Each is one C-ABI call that ends in the finish kernel (csrc/mesh_reg.hip), and each can
     make its gradient for a unit upstream in forward() already (the terms depend on the vertices only)."""
 
     @staticmethod
@@ -360,6 +360,82 @@ def bend_penalty(verts, topo, weight, rest=None, eager_grad=False, unit_upstream
     hinge_vtx, hinge_inc, _, _ = topo.hinges()
     return _bend_penalty.apply(verts, hinge_vtx, hinge_inc, None if rest is None else rest.bend_cs, weight,
                                bool(eager_grad and unit_upstream), acc, scratch)
+
+
+def motion_inv_scale(scale):
+    """1 / scale as the float32 the kernel is handed (fpcdr_motion_penalty's inv_c), 0.0 for None (L2); ValueError for a scale that is
+    not finite and positive, or whose inverse is not a finite positive float32."""
+    if scale is None:
+        return 0.0
+    try:
+        c = float(scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"the motion term's scale must be a number (got {scale!r})")
+    if not (np.isfinite(c) and c > 0.0):
+        raise ValueError(f"the motion term's scale must be finite and positive (got {scale!r})")
+    with np.errstate(over='ignore'):
+        inv = float(np.float32(1.0 / c))
+    if not (np.isfinite(inv) and inv > 0.0):
+        raise ValueError(f"the motion term's scale {scale!r} has no finite positive inverse in float32")
+    return inv
+
+
+def _check_motion_order(order):
+    if isinstance(order, bool) or order not in (1, 2):
+        raise ValueError(f"the motion term's order must be 1 (velocity) or 2 (acceleration) (got {order!r})")
+    return int(order)
+
+
+class _motion_penalty(_penalty):
+    """weight / F * sum_f m_f mean_v w_v rho(|a_{f,v}|^2) with its gradient from ONE call (fpcdr_motion_penalty): the lane of a (frame,
+    vertex) reads the frames around its own, so the gradient for a unit upstream is always made in forward(); backward() is _penalty's."""
+
+    @staticmethod
+    def forward(ctx, verts, frame_ids, vertex_w, inv_c, order, weight, unit=False, acc=None):
+        x, acc, per, out = _penalty.begin(ctx, 8, "fpcdr_motion_penalty", verts, acc, unit)
+        F, V, _ = x.shape
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        _lib.call("fpcdr_motion_penalty", _ptr(x), _ptr(frame_ids), _ptr(vertex_w), float(inv_c), int(order), _ptr(gx), _ptr(acc),
+                  _ptr(per), _ptr(out), float(weight), F, V, _stream())
+        if gx is not None:
+            ctx.save_for_backward(gx)
+        return out
+
+
+def motion_penalty(verts, weight, frame_ids=None, order=2, scale=None, vertex_weights=None, eager_grad=False, unit_upstream=False,
+                   acc=None, validate=True):
+    """weight / F * sum over the meshes of verts [F,V,3] of m_f * mean_v w_v rho(|a_{f,v}|^2) ("Motion rule"): a the
+    acceleration x_{f-1} - 2 x_f + x_{f+1} (order 2) or the velocity x_{f+1} - x_f (order 1) of a vertex across the frames, m_f = 1 where
+    the frames the difference needs are in the call and one frame number apart.  frame_ids: the meshes' frame numbers, int64 [F] on the
+    device of verts, strictly increasing (None: consecutive); they are read on the device.  scale c (None: rho(s) = s): rho(s) =
+    2 c^2 (sqrt(1 + s / c^2) - 1), quadratic below c and linear above it, in the length units of verts.  vertex_weights: float32 [V] on
+    the device of verts, finite and >= 0 (None: 1).  Fewer than order + 1 meshes, or no valid stencil: value and gradient exactly 0.
+    The modes and `acc` are stretch_penalty's.  validate: check frame_ids and vertex_weights on the host (two read-backs; skipped while
+    a stream is capturing)."""
+    order = _check_motion_order(order)
+    inv_c = motion_inv_scale(scale)
+    if verts.dim() != 3 or verts.shape[2] != 3 or verts.dtype != torch.float32:
+        raise ValueError(f"motion_penalty: verts must be float32 [F,V,3] (got {verts.dtype} {tuple(verts.shape)})")
+    F, V = int(verts.shape[0]), int(verts.shape[1])
+    if F < 1 or V < 1:
+        raise ValueError(f"motion_penalty: verts must hold at least one mesh and one vertex (got {tuple(verts.shape)})")
+    live = validate and not (verts.is_cuda and torch.cuda.is_current_stream_capturing())
+    if frame_ids is not None:
+        if not torch.is_tensor(frame_ids) or frame_ids.dtype != torch.int64 or tuple(frame_ids.shape) != (F,):
+            raise ValueError(f"motion_penalty: frame_ids must be an int64 tensor [{F}], one frame number per mesh")
+        if frame_ids.device != verts.device:
+            raise ValueError(f"motion_penalty: frame_ids must be on the device of verts ({verts.device}), they are read there")
+        if live and F > 1 and not bool((frame_ids[1:] > frame_ids[:-1]).all()):
+            raise ValueError("motion_penalty: frame_ids must be strictly increasing")
+        frame_ids = frame_ids.contiguous()
+    if vertex_weights is not None:
+        if (not torch.is_tensor(vertex_weights) or vertex_weights.dtype != torch.float32 or tuple(vertex_weights.shape) != (V,)
+                or vertex_weights.device != verts.device):
+            raise ValueError(f"motion_penalty: vertex_weights must be a float32 tensor [{V}] on the device of verts")
+        if live and not bool((torch.isfinite(vertex_weights) & (vertex_weights >= 0)).all()):
+            raise ValueError("motion_penalty: vertex_weights must be finite and not negative")
+        vertex_weights = vertex_weights.contiguous()
+    return _motion_penalty.apply(verts, frame_ids, vertex_weights, inv_c, order, weight, bool(eager_grad and unit_upstream), acc)
 
 
 def mesh_normal_consistency(verts, topo):

@@ -435,6 +435,21 @@ int fpcdr_bend_penalty(const float *x, const int32_t *hinge_vtx, const float *re
                        void *acc /* F+1 doubles, zero in, zero out */, float *per, float *out, float weight, int32_t F, int32_t V,
                        int32_t H, int32_t K, void *stream);
 
+/* The meshes of a call held smooth in TIME ("Motion rule"), value and gradient in one call (two launches):
+ *   order 2:  a_{f,v} = x_{f-1,v} - 2 x_{f,v} + x_{f+1,v},  m_f = 1 iff 1 <= f <= F - 2, t_f - t_{f-1} = 1 and t_{f+1} - t_f = 1
+ *   order 1:  a_{f,v} = x_{f+1,v} - x_{f,v},                m_f = 1 iff f <= F - 2 and t_{f+1} - t_f = 1          (m_f = 0 otherwise)
+ *   s = || a ||^2,   rho(s) = s  (inv_c = 0: L2)   or   2 c^2 (sqrt(1 + s / c^2) - 1),  c = 1 / inv_c  (Charbonnier, as fpcdr_robust_loss)
+ *   per[f] = m_f / V * sum_v w_v rho(s_{f,v}),   out[0] = weight / F * sum_f per[f]   (divided by F, not by the number of valid stencils)
+ *   grad_x [F,V,3] = d out / d x for a unit upstream (overwritten: a gather over f - order .. f + order of the entry's own vertex, no
+ *   float atomics, bit-identical from run to run), or NULL: value only.
+ * frame_t [F] int64, strictly increasing: the frame numbers of the meshes, read on the device; NULL: consecutive.  vertex_w [V] float32,
+ * finite and >= 0, or NULL: 1.  F < order + 1, or no valid stencil: value 0, per 0, gradient 0.  An order outside {1, 2} or an inv_c that
+ * is negative or not finite is an error.  acc: (F + 1) * 8 bytes, 8-byte aligned, ZERO on entry; the call leaves it zero again.     */
+int fpcdr_motion_penalty(const float *x, const int64_t *frame_t /* [F] or NULL */, const float *vertex_w /* [V] or NULL */,
+                         float inv_c /* 0: L2 */, int32_t order, float *grad_x /* [F,V,3] or NULL: value only */,
+                         void *acc /* F+1 doubles, zero in, zero out */, float *per, float *out, float weight, int32_t F, int32_t V,
+                         void *stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* blend -- V = v_base + Bmat . w     reference fit.py:115-122 (prior), :58-62 (free)            */
 /* ------------------------------------------------------------------------------------------ */
