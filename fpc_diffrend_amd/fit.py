@@ -257,17 +257,9 @@ def render(glctx, mtx, pos, pos_idx, uv, uv_idx, tex, resolution, enable_mip, ma
 
 def pixel_loss_fused(colour, rast_out, ref_u8, n_total=None):
     """Background composite (fit.py:161) + sum((ref - 255 colour)^2) (fit.py:579) and its gradient in one
-    pass.  Returns (sum_sq [1] f64 tensor, d mean / d colour [B,H,W,C]) with mean over n_total elements."""
-    lib = _lib.load()
-    B, H, W, C = colour.shape
+    pass (ops.pixel_loss_call).  Returns (sum_sq [1] f64 tensor, d mean / d colour [B,H,W,C]) with mean over n_total elements."""
     n_total = n_total or colour.numel()
-    acc = torch.zeros(1, dtype=torch.float64, device=colour.device)
-    grad = torch.empty_like(colour)
-    colour = colour.detach().contiguous()
-    p = _lib.PixelLoss(color=_ptr(colour), rast=_ptr(rast_out), ref=_ptr(ref_u8), B=B, H=H, W=W, C=C, bg=BACKGROUND,
-                       color_scale=255.0, grad_scale=1.0 / n_total, loss_sum=_ptr(acc), grad_color=_ptr(grad))
-    _lib.call("fpcdr_pixel_loss", ctypes.byref(p), _stream())
-    return acc, grad
+    return dr.pixel_loss_call(colour, rast_out, ref_u8, 1.0 / n_total, BACKGROUND)
 
 
 def pixel_loss_blurred(colour, rast_out, ref_u8, taps, n_total=None):
@@ -336,14 +328,55 @@ def motion_options(cfg, n_vertices, n_local):
     return motion_inv_scale(cfg.motion_scale), w
 
 
-def _check_window_term(cfg, kind, name, graph_why, sigmas):
-    """What FitConfig.blur_sigma > 0 and norm_sigma > 0 (kind 'blur' / 'norm') both ask of the other options, or ValueError."""
-    if not cfg.fused_loss:
-        raise ValueError(f"FitConfig.{kind}_sigma > 0 needs fused_loss=True: the {name} loss replaces pixel_loss_fused")
-    if cfg.hip_graph:
-        raise ValueError(f"FitConfig.{kind}_sigma > 0 cannot be combined with hip_graph: {graph_why}")
-    for sigma in sigmas:
-        dr.gaussian_taps(getattr(cfg, kind + '_kernel_size'), sigma)                     # (raises for a bad kernel size or sigma)
+def pixel_term(cfg, i, weighted=False):
+    """The pixel term of iteration i under FitConfig cfg ("Which pixel term an iteration runs"), a function of the iteration
+    alone, so that a resumed run continues on the right side of every switch.  weighted: masks in use, face weights, saturation > 0 or
+    weight_outside != 1.  ->  None: the path the other flags select;  ('blur', taps);  ('norm', taps, norm_eps);  ('robust', kind,
+    scale): cfg.robust inside robust_iters, ('robust', 'l2', None) when only weights are on.  The name and the arguments that
+    pixel_loss_blurred / _normalised / _robust take between ref_u8 and n_total.  Needs no GPU."""
+    for kind in ('blur', 'norm'):
+        sigma, iters = float(getattr(cfg, kind + '_sigma')), getattr(cfg, kind + '_iters')
+        if sigma > 0 and not (iters and i >= iters):
+            if kind == 'blur' and cfg.blur_sigma_end is not None:      # geometrically from blur_sigma to blur_sigma_end
+                n = iters or cfg.max_iter
+                sigma = sigma * (float(cfg.blur_sigma_end) / sigma) ** (min(i, n - 1) / max(n - 1, 1))
+            taps = dr.gaussian_taps(getattr(cfg, kind + '_kernel_size'), sigma)
+            return ('blur', taps) if kind == 'blur' else ('norm', taps, cfg.norm_eps)
+    if cfg.robust and not (cfg.robust_iters and i >= cfg.robust_iters):
+        return 'robust', cfg.robust, cfg.robust_scale
+    return ('robust', 'l2', None) if weighted else None
+
+
+def pixel_term_loss(term, colour, rast_out, ref_u8, n_total, **weights):
+    """(sums f64, d mean / d colour) of `term` (pixel_term's answer; None: the plain L2); weights: pixel_loss_robust's keyword arguments."""
+    if term is None:
+        return pixel_loss_fused(colour, rast_out, ref_u8, n_total)
+    call = {'blur': pixel_loss_blurred, 'norm': pixel_loss_normalised, 'robust': pixel_loss_robust}[term[0]]
+    return call(colour, rast_out, ref_u8, *term[1:], n_total, **weights)
+
+
+def check_pixel_terms(cfg, has_masks=False):
+    """What a windowed (blur_sigma > 0, norm_sigma > 0) or a weighted pixel term (FitConfig.weights_configured(), or has_masks: the Scene
+    has masks, and use_masks takes them) asks of the other options, or ValueError.  FitConfig itself refuses what it can see without a
+    Scene; this is the whole statement once the Scene is known.  Needs no GPU."""
+    weights = "robust / face_weights / saturation / weight_outside" if cfg.weights_configured() else \
+        "the Scene's masks (use_masks=False ignores them)" if (has_masks and cfg.use_masks) else None
+    windows = [kind for kind in ('blur', 'norm') if getattr(cfg, kind + '_sigma') > 0]
+    for what, loss in [(k + "_sigma > 0", {'blur': "blurred", 'norm': "normalised"}[k]) for k in windows] + [(weights, "robust")] * bool(weights):
+        if not cfg.fused_loss:
+            raise ValueError(f"FitConfig: {what} needs fused_loss=True: the {loss} loss replaces pixel_loss_fused")
+        if cfg.hip_graph:      # ('auto' counts as on)
+            raise ValueError(f"FitConfig: {what} cannot be combined with hip_graph: the term, and with it the step's launches, changes from "
+                             "one iteration to the next, and the step leaves the captured path")
+    for kind in windows:      # (raises for a bad kernel size or sigma)
+        dr.gaussian_taps(getattr(cfg, kind + '_kernel_size'), getattr(cfg, kind + '_sigma'))
+        if kind == 'blur' and cfg.blur_sigma_end is not None:
+            dr.gaussian_taps(cfg.blur_kernel_size, cfg.blur_sigma_end)
+    if 'norm' in windows and not (float(cfg.norm_eps) > 0.0 and float(cfg.norm_eps) < float('inf')):
+        raise ValueError(f"FitConfig.norm_eps must be finite and positive (got {cfg.norm_eps})")
+    if windows and weights:
+        raise ValueError(f"FitConfig: {weights} cannot be combined with blur_sigma > 0 or norm_sigma > 0: weighting the windowed losses "
+                         "is a different rule")
 
 
 class _mvp_func(torch.autograd.Function):
@@ -794,29 +827,13 @@ class Fitter:
                   {"params": self.maps_intermediate['local'], 'lr': cfg.lr_base}, {"params": self.t_opt, 'lr': cfg.lr_t},
                   {"params": self.q_opt, 'lr': cfg.lr_q}, {"params": self.per_frame_t, 'lr': cfg.lr_t},
                   {"params": self.per_frame_q, 'lr': cfg.lr_q}, {"params": self.tex_opt, 'lr': cfg.lr_base * cfg.lr_tex_coef}]
-        if cfg.blur_sigma > 0:
-            _check_window_term(cfg, 'blur', "blurred", "sigma and the switch back to the one-pass objective change from one iteration to the next",
-                               (cfg.blur_sigma,) + (() if cfg.blur_sigma_end is None else (cfg.blur_sigma_end,)))
-        if cfg.norm_sigma > 0:
-            _check_window_term(cfg, 'norm', "normalised", "the switch back to the path the other flags select changes the step from one "
-                               "iteration to the next", (cfg.norm_sigma,))
-            if not (float(cfg.norm_eps) > 0.0 and float(cfg.norm_eps) < float('inf')):
-                raise ValueError(f"FitConfig.norm_eps must be finite and positive (got {cfg.norm_eps})")
-        # the weighted robust pixel term ("Robust loss rule"): what its options and a Scene's masks ask of the others
+        # the pixel terms ("Which pixel term an iteration runs"): what they and a Scene's masks ask of the other options
         sc_masks = sc.masks if cfg.use_masks else None
         self.face_w = None
         if cfg.face_weights is not None:
             self.face_w = torch.from_numpy(load_face_weights(cfg.face_weights, int(sc.pos_idx.shape[0]))).to(dev)
-        if cfg.weights_configured() or sc_masks is not None:
-            why = "the Scene's masks (use_masks=False ignores them)" if not cfg.weights_configured() else \
-                "robust / face_weights / saturation / weight_outside"
-            if not cfg.fused_loss:
-                raise ValueError(f"FitConfig: {why} need fused_loss=True: the robust loss replaces pixel_loss_fused")
-            if cfg.hip_graph:
-                raise ValueError(f"FitConfig: {why} cannot be combined with hip_graph: the step leaves the captured path, as a blurred one does")
-            if cfg.blur_sigma > 0 or cfg.norm_sigma > 0:
-                raise ValueError(f"FitConfig: {why} cannot be combined with blur_sigma > 0 or norm_sigma > 0: weighting the windowed losses "
-                                 "is a different rule")
+        check_pixel_terms(cfg, sc.masks is not None)
+        self._weighted = sc_masks is not None or self.face_w is not None or cfg.saturation > 0 or float(cfg.weight_outside) != 1.0
         if cfg.hip_graph == 'auto':
             self.use_graph = self.auto_graph((cfg.frames_per_step or (self.frame_hi - self.frame_lo)) * (cfg.views_per_step or len(self.cam_idxs)),
                                              self.resolution)
@@ -867,6 +884,7 @@ class Fitter:
         self._result_full = torch.zeros(F, self.v_base.shape[0], dtype=torch.float32, device=dev)
         # the base mesh as the rest shape of the regularisers that measure against it
         self.rest = RestShape(self.topo, self.v_base) if (cfg.laplacian_relative or cfg.weight_stretch or cfg.weight_bend) else None
+        self._lap_rest = self.rest if cfg.laplacian_relative else None      # (the Laplacian term's: the plain one has no rest shape)
         # the bending term's tables and the scratch of its corner gradients for the most frames a step takes: made here, before any capture
         self._bnd_scratch = None
         if cfg.weight_bend:
@@ -882,8 +900,7 @@ class Fitter:
         eager = dict(eager_grad=True, unit_upstream=True, acc=self._reg_acc)
         self._reg_terms = []
         if cfg.weight_laplacian and cfg.fused_loss:      # (two launches, ~25 us in front of the objective)
-            lap_rest = self.rest if cfg.laplacian_relative else None
-            self._reg_terms.append(lambda vtx, ids: laplacian_penalty(vtx, self.topo, cfg.weight_laplacian / world, rest=lap_rest, **eager))
+            self._reg_terms.append(lambda vtx, ids: laplacian_penalty(vtx, self.topo, cfg.weight_laplacian / world, rest=self._lap_rest, **eager))
         if cfg.weight_stretch:
             self._reg_terms.append(lambda vtx, ids: stretch_penalty(vtx, self.topo, cfg.weight_stretch / world, rest=self.rest, **eager))
         if cfg.weight_bend:
@@ -1243,38 +1260,22 @@ class Fitter:
             for m in (self.m1, self.m2, self.m3):
                 m.requires_grad = True
 
-    def _window_taps(self, kind, i, sigma_at=None):
-        """The taps of the windowed pixel term `kind` ('blur' / 'norm') at iteration i (default: the current one), or None when that
-        iteration does not use it.  sigma_at(i, n), n the iterations the term lasts, overrides the constant sigma."""
-        cfg = self.cfg
-        i = self.iteration if i is None else i
-        sigma, iters = getattr(cfg, kind + '_sigma'), getattr(cfg, kind + '_iters')
-        if not sigma > 0 or (iters and i >= iters):
-            return None
-        return dr.gaussian_taps(getattr(cfg, kind + '_kernel_size'), sigma_at(i, iters or cfg.max_iter) if sigma_at else float(sigma))
+    def _term_args(self, name, i=None):
+        """pixel_term's arguments of the term `name` at iteration i (default: the current one), or None when that iteration runs another."""
+        term = pixel_term(self.cfg, self.iteration if i is None else i, self._weighted)
+        return term[1:] if term is not None and term[0] == name else None
 
     def blur_taps(self, i=None):
-        """The taps of the blurred pixel loss at iteration i (default: the current one), or None when that iteration is not blurred.
-        A function of the iteration alone, so a resumed run continues on the right side of the switch."""
-        s0, s1 = float(self.cfg.blur_sigma), self.cfg.blur_sigma_end
-        return self._window_taps('blur', i, None if s1 is None else lambda i, n: s0 * (float(s1) / s0) ** (min(i, n - 1) / max(n - 1, 1)))
+        """The taps of the blurred pixel loss at iteration i (default: the current one), or None when that iteration is not blurred."""
+        return (self._term_args('blur', i) or (None,))[0]
 
     def norm_taps(self, i=None):
-        """The taps of the normalised pixel loss at iteration i (default: the current one), or None when that iteration is not
-        normalised.  A function of the iteration alone, so a resumed run continues on the right side of the switch."""
-        return self._window_taps('norm', i)
+        """The taps of the normalised pixel loss at iteration i (default: the current one), or None when that iteration is not normalised."""
+        return (self._term_args('norm', i) or (None,))[0]
 
     def robust_term(self, i=None):
-        """(kind, scale) of the weighted robust pixel term at iteration i (default: the current one), or None when that iteration does not
-        use it: FitConfig.robust inside robust_iters, or kind 'l2' when only weights are on (masks in use, face_weights, saturation > 0,
-        weight_outside != 1).  A function of the iteration alone, so a resumed run continues on the right side of the switch."""
-        cfg = self.cfg
-        i = self.iteration if i is None else i
-        if cfg.robust and not (cfg.robust_iters and i >= cfg.robust_iters):
-            return cfg.robust, cfg.robust_scale
-        if self.full_masks is not None or self.face_w is not None or cfg.saturation > 0 or float(cfg.weight_outside) != 1.0:
-            return 'l2', None
-        return None
+        """(kind, scale) of the weighted robust pixel term at iteration i (default: the current one), or None when it does not run it."""
+        return self._term_args('robust', i)
 
     def loss_and_backward(self, frame_ids, view_ids=None, validate=True):
         """Forward + backward of fit.py:556-611 for a batch of frames x cameras (view_ids: see mvp).  Returns the loss (tensor).
@@ -1293,14 +1294,9 @@ class Fitter:
         # (the mip branch of the reference's render(), fit.py:153-155, runs inside the same kernels)
         one_shot = (cfg.fused_objective and cfg.fused_render and cfg.fused_loss and C in (1, 3, 4) and cfg.shading == 'texture'
                     and (not mip or cfg.sparse_objective))
-        # the windowed pixel term of this iteration, (kind, taps), or None (FitConfig lets at most one sigma be > 0)
-        window = ('blur', self.blur_taps(i)) if cfg.blur_sigma > 0 else ('norm', self.norm_taps(i)) if cfg.norm_sigma > 0 else None
-        if window is not None and window[1] is None:
-            window = None
-        robust = self.robust_term(i)   # (kind, scale) of the weighted robust pixel term, or None (never together with a window: __init__)
-        self._wsum = None
-        if window is not None or robust is not None:
-            one_shot = False           # a windowed or a weighted loss needs the image in memory: the operator path
+        term = pixel_term(cfg, i, self._weighted)      # a windowed or a weighted loss needs the image in memory: the operator path
+        one_shot = one_shot and term is None
+        robust = term is not None and term[0] == 'robust'
         # one flat buffer for the small accumulators of this step's backward kernels, zero-filled by the objective's first kernel; the
         # pool around it goes to the functions whose backward takes views of it
         zero_buf, pool = None, None
@@ -1327,16 +1323,12 @@ class Fitter:
             colour, rast_out = render_from_clip(self.glctx, pos_clip, self.pos_idx, self.uv, self.uv_idx, self.tex_opt,
                                                 self.resolution, mip, cfg.max_mip_level, cfg.fused_render)
         # regularisers (fit.py:578-595): evaluated on this rank's meshes, averaged over all ranks
-        chain_terms = bool(cfg.weight_meshedge or cfg.weight_normalconsistency or (cfg.weight_laplacian and not cfg.fused_loss)
-                           or (cfg.regularize_correctives and cfg.mode == 'combined' and i > cfg.max_iter / 2)
-                           or (cfg.regularize_prior and cfg.mode == 'prior'))
         reg = self._zero
-        lap_rest = self.rest if cfg.laplacian_relative else None
         if cfg.weight_meshedge:
             reg = reg + cfg.weight_meshedge * mesh_edge_loss(vtx_pos_split, self.topo, 0.1)
         if cfg.weight_laplacian and not cfg.fused_loss:
             # the reference squares the value of ONE mesh per step (fit.py:581): a batch is the mean of the squares
-            reg = reg + cfg.weight_laplacian * (mesh_laplacian_smoothing(vtx_pos_split, self.topo, per_mesh=True, rest=lap_rest) ** 2).mean()
+            reg = reg + cfg.weight_laplacian * (mesh_laplacian_smoothing(vtx_pos_split, self.topo, per_mesh=True, rest=self._lap_rest) ** 2).mean()
         if cfg.weight_normalconsistency:
             reg = reg + cfg.weight_normalconsistency * mesh_normal_consistency(vtx_pos_split, self.topo)
         if cfg.regularize_correctives and cfg.mode == 'combined' and i > cfg.max_iter / 2:
@@ -1345,12 +1337,13 @@ class Fitter:
         if cfg.regularize_prior and cfg.mode == 'prior':
             mi = torch.matmul(self.maps_intermediate['local'], self._take(self.maps['local'], 1, frame_ids))
             reg = reg + torch.mean(mi ** 2)
-        if self.world > 1 and chain_terms:
+        chained = reg is not self._zero      # (some term above was added)
+        if self.world > 1 and chained:
             reg = reg / self.world
         # the eager terms (Laplacian, stretch, bend, motion: __init__), their gradients made here with their values; a slice of frames is
         # consecutive (no frame numbers to hand over), an index tensor names them
         step_ids = frame_ids if torch.is_tensor(frame_ids) else None
-        terms = [term(vtx_pos_split, step_ids) for term in self._reg_terms]
+        terms = [reg_term(vtx_pos_split, step_ids) for reg_term in self._reg_terms]
         self.optimizer.zero_grad(set_to_none=True)
         if one_shot:
             bg_sum = None
@@ -1371,27 +1364,15 @@ class Fitter:
                                      one_pass=cfg.one_pass, unit_upstream=True, zero_extra=zero_buf,      # (the seeds below are 1)
                                      skip_out=self._skip_cur)
             self._backward(pix, self._one, reg, *terms)
-            loss = pix.detach()
-            if chain_terms:      # (an add is a launch: none for a reg that is the constant 0)
-                loss = loss + reg.detach()
-            for term in terms:
-                loss = loss + term.detach()
+            value = pix.detach()
         elif cfg.fused_loss:
-            if robust is not None:
+            weights = {}
+            if robust:
                 mask = self._take(self.masks.reshape(-1, *self.resolution), 0, rows) if self.masks is not None else None
-                sum_sq, g_colour = pixel_loss_robust(colour, rast_out, ref, robust[0], robust[1], n_total, mask=mask, face_weights=self.face_w,
-                                                     weight_outside=cfg.weight_outside, saturation=cfg.saturation)
-                self._wsum = sum_sq[1]
-            elif window is None:
-                sum_sq, g_colour = pixel_loss_fused(colour, rast_out, ref, n_total)
-            elif window[0] == 'blur':
-                sum_sq, g_colour = pixel_loss_blurred(colour, rast_out, ref, window[1], n_total)
-            else:
-                sum_sq, g_colour = pixel_loss_normalised(colour, rast_out, ref, window[1], cfg.norm_eps, n_total)
+                weights = dict(mask=mask, face_weights=self.face_w, weight_outside=cfg.weight_outside, saturation=cfg.saturation)
+            sums, g_colour = pixel_term_loss(term, colour, rast_out, ref, n_total, **weights)
             self._backward(colour, g_colour, reg, *terms)
-            loss = sum_sq[0].to(torch.float32) / n_total + reg.detach()
-            for term in terms:
-                loss = loss + term.detach()
+            value = sums[0].to(torch.float32) / n_total
         else:
             col = torch.where(rast_out[..., 3:] > 0, colour, self._background)
             # the reference holds its target image as float32 on the GPU (fit.py:531-532); the 8-bit batch is converted once
@@ -1399,9 +1380,15 @@ class Fitter:
                 self._targets_f32 = self.targets.to(torch.float32)
             ref_f = self._take(self._targets_f32.reshape(-1, *self.resolution), 0, rows).reshape(Fb * Nc, *self.resolution, 1)
             loss = torch.mean((ref_f - col * 255) ** 2) / self.world + reg
-            for term in terms:
-                loss = loss + term
+            for t in terms:
+                loss = loss + t
             loss.backward()
+        if cfg.fused_loss:      # the value, summed after the backward pass has been enqueued.  An add is a launch: the one-pass step
+            # has none for a reg that is the constant 0; the operator path has always had it, and keeps its launches
+            loss = value + reg.detach() if (chained or not one_shot) else value
+            for t in terms:
+                loss = loss + t.detach()
+        self._wsum = sums[1] if robust else None      # (the sum of the weights of an iteration on the robust term, for the step log)
         self._store_result(frame_ids, vtx_pos.detach())
         return loss.detach()
 
@@ -1532,8 +1519,7 @@ class Fitter:
                 v = self.vertices(frame_ids, validate=False).reshape(self._n(frame_ids), -1, 3)
                 rec = rec or {"it": i}
                 rec["MEL"] = float(cfg.weight_meshedge * mesh_edge_loss(v, self.topo, 0.1))
-                lap_rest = self.rest if cfg.laplacian_relative else None
-                rec["LAP"] = float(cfg.weight_laplacian * (mesh_laplacian_smoothing(v, self.topo, per_mesh=True, rest=lap_rest) ** 2).mean())
+                rec["LAP"] = float(cfg.weight_laplacian * (mesh_laplacian_smoothing(v, self.topo, per_mesh=True, rest=self._lap_rest) ** 2).mean())
                 rec["STR"] = float(stretch_penalty(v, self.topo, cfg.weight_stretch, rest=self.rest)) if cfg.weight_stretch else 0.0
                 rec["BND"] = float(bend_penalty(v, self.topo, cfg.weight_bend, rest=self.rest)) if cfg.weight_bend else 0.0
                 rec["MNC"] = float(cfg.weight_normalconsistency * mesh_normal_consistency(v, self.topo))

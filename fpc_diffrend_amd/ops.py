@@ -20,6 +20,7 @@ autograd), supplies the stream, and runs autograd bookkeeping.  All pixel work h
 libfpcdr.so; there is no CPU or eager-torch fallback.
 """
 import ctypes
+import functools
 import weakref
 from collections import OrderedDict
 
@@ -660,12 +661,47 @@ def gaussian_taps(kernel_size, sigma):
     return torch.from_numpy((g / g.sum()).astype(np.float32))
 
 
-def _window_args(colour, rast, ref_u8, taps, nonneg_taps=False):
-    """What both windowed-loss calls do before they allocate: -> (colour, rast, ref_u8 detached and contiguous, the taps as a CPU
-    float32 tensor [k]), or ValueError.  The checks that need no GPU (the taps) run before the tensors are looked at."""
+def _colour_shape(colour):
+    """(B, H, W, C) of the colour a pixel-loss call is handed, or ValueError: what the checks that need no GPU read of it."""
     if not (torch.is_tensor(colour) and colour.dim() == 4):
         raise ValueError("colour must be a [B,H,W,C] tensor")
+    return tuple(colour.shape)
+
+
+def _pixel_tensors(colour, rast, ref_u8):
+    """The tensor checks of every pixel-loss call: colour [B,H,W,C] float32, rast [B,H,W,4] float32, ref_u8 [B,H,W] uint8, all on the
+    GPU -> the three detached and contiguous, or ValueError.  A call runs its checks that need no GPU before this one."""
+    B, H, W, _ = _colour_shape(colour)
+    _check_tensor('colour', colour, torch.float32, 4)
+    _check_tensor('rast', rast, torch.float32, 4)
+    _check_tensor('ref_u8', ref_u8, torch.uint8, 3)
+    if tuple(rast.shape) != (B, H, W, 4) or tuple(ref_u8.shape) != (B, H, W):
+        raise ValueError(f"rast must be [B,H,W,4] and ref_u8 [B,H,W] for colour {tuple(colour.shape)}")
+    return colour.detach().contiguous(), rast.detach().contiguous(), ref_u8.contiguous()
+
+
+def _pixel_head(colour, rast, ref_u8, background, grad_scale):
+    """The ten fields every pixel-loss parameter struct begins with (fpcdr_pixel_loss_params and the three that follow its style)."""
     B, H, W, C = colour.shape
+    return dict(color=_ptr(colour), rast=_ptr(rast), ref=_ptr(ref_u8), B=B, H=H, W=W, C=C, bg=float(background), color_scale=255.0,
+                grad_scale=float(grad_scale))
+
+
+def pixel_loss_call(colour, rast, ref_u8, grad_scale, background=45.0 / 255.0, want_grad=True):
+    """One fpcdr_pixel_loss call, the plain L2: -> (sum (ref - 255 * (rast.w > 0 ? colour : background))^2 [1] f64, grad_scale * d sum /
+    d colour [B,H,W,C] or None)."""
+    colour, rast, ref_u8 = _pixel_tensors(colour, rast, ref_u8)
+    with torch.cuda.device(colour.device):
+        acc = torch.zeros(1, dtype=torch.float64, device=colour.device)
+        grad = torch.empty_like(colour) if want_grad else None
+        p = _lib.PixelLoss(**_pixel_head(colour, rast, ref_u8, background, grad_scale), loss_sum=_ptr(acc), grad_color=_ptr(grad))
+        _lib.call("fpcdr_pixel_loss", ctypes.byref(p), _stream())
+    return acc, grad
+
+
+def _window_args(colour, taps, nonneg_taps=False):
+    """The taps of a windowed-loss call as a CPU float32 tensor [k], checked against the image size, or ValueError.  Needs no GPU."""
+    _, H, W, _ = _colour_shape(colour)
     taps = torch.as_tensor(taps, dtype=torch.float32).detach().cpu().reshape(-1)
     k = taps.numel()
     if k % 2 == 0 or not 3 <= k <= 63:
@@ -674,61 +710,29 @@ def _window_args(colour, rast, ref_u8, taps, nonneg_taps=False):
         raise ValueError("the taps of the normalised loss must be finite and non-negative (m >= mu^2 rests on it)")
     if (k - 1) // 2 >= min(H, W):
         raise ValueError(f"reflected borders need (kernel_size - 1) / 2 < min(H, W) (got kernel size {k} for {H} x {W})")
-    _check_tensor('colour', colour, torch.float32, 4)
-    _check_tensor('rast', rast, torch.float32, 4)
-    _check_tensor('ref_u8', ref_u8, torch.uint8, 3)
-    if tuple(rast.shape) != (B, H, W, 4) or tuple(ref_u8.shape) != (B, H, W):
-        raise ValueError(f"rast must be [B,H,W,4] and ref_u8 [B,H,W] for colour {tuple(colour.shape)}")
-    return colour.detach().contiguous(), rast.detach().contiguous(), ref_u8.contiguous(), taps
+    return taps
 
 
 def _set_taps(p, taps):
-    """taps [k] -> the taps field of a parameter struct (fpcdr_blur_loss_params / fpcdr_norm_loss_params)"""
+    """taps [k] -> the radius and taps fields of a parameter struct (fpcdr_blur_loss_params / fpcdr_norm_loss_params)"""
+    p.radius = (taps.numel() - 1) // 2
     for t in range(taps.numel()):
         p.taps[t] = float(taps[t])
 
 
 def blur_loss_call(colour, rast, ref_u8, taps, grad_scale, background=45.0 / 255.0, want_grad=True):
     """One fpcdr_blur_loss call: -> (sum E^2 [1] f64, grad_scale * d sum / d colour [B,H,W,C] or None, E [B,H,W,C])."""
-    colour, rast, ref_u8, taps = _window_args(colour, rast, ref_u8, taps)
-    B, H, W, C = colour.shape
+    taps = _window_args(colour, taps)
+    colour, rast, ref_u8 = _pixel_tensors(colour, rast, ref_u8)
     with torch.cuda.device(colour.device):
         acc = torch.zeros(1, dtype=torch.float64, device=colour.device)
         tmp, blurred = torch.empty_like(colour), torch.empty_like(colour)
         grad = torch.empty_like(colour) if want_grad else None
-        p = _lib.BlurLoss(color=_ptr(colour), rast=_ptr(rast), ref=_ptr(ref_u8), B=B, H=H, W=W, C=C, bg=float(background),
-                          color_scale=255.0, grad_scale=float(grad_scale), radius=(taps.numel() - 1) // 2, tmp=_ptr(tmp),
-                          blurred=_ptr(blurred), loss_sum=_ptr(acc), grad_color=_ptr(grad))
+        p = _lib.BlurLoss(**_pixel_head(colour, rast, ref_u8, background, grad_scale), tmp=_ptr(tmp), blurred=_ptr(blurred),
+                          loss_sum=_ptr(acc), grad_color=_ptr(grad))
         _set_taps(p, taps)
         _lib.call("fpcdr_blur_loss", ctypes.byref(p), _stream())
     return acc, grad, blurred
-
-
-class _windowed_pixel_loss_func(torch.autograd.Function):
-    """call = blur_loss_call or norm_loss_call, rest = its arguments behind grad_scale: the mean over n_total, and the gradient the same
-    call computed, times the upstream scalar, as the backward."""
-    @staticmethod
-    def forward(ctx, call, n_total, colour, rast, ref_u8, taps, *rest):
-        acc, grad, _ = call(colour, rast, ref_u8, taps, 1.0 / n_total, *rest)
-        ctx.save_for_backward(grad)
-        ctx.n_rest = len(rest)
-        return (acc[0] / n_total).to(torch.float32)
-
-    @staticmethod
-    def backward(ctx, upstream):
-        grad, = ctx.saved_tensors
-        return (None, None, grad * upstream, None, None, None) + (None,) * ctx.n_rest
-
-
-def blurred_pixel_loss(colour, rast, ref_u8, sigma=None, kernel_size=31, n_total=None, background=45.0 / 255.0, taps=None):
-    """mean over n_total elements (default: all of colour) of E^2, E = the Gaussian-blurred residual ref - 255 * (rast.w > 0 ? colour :
-    background) with reflected borders (DESIGN.md 3, "Blurred loss rule"; fpcdr_blur_loss) -- a float32 scalar whose backward is the
-    closed-form gradient the same call computed, times the upstream scalar.  taps= (odd, 3 .. 63 entries) overrides sigma and kernel_size."""
-    if taps is None:
-        if sigma is None:
-            raise ValueError("blurred_pixel_loss needs sigma (or taps)")
-        taps = gaussian_taps(kernel_size, sigma)
-    return _windowed_pixel_loss_func.apply(blur_loss_call, float(n_total or colour.numel()), colour, rast, ref_u8, taps, background)
 
 
 def norm_loss_call(colour, rast, ref_u8, taps, grad_scale, eps=2.0, want_grad=True, background=45.0 / 255.0):
@@ -738,7 +742,8 @@ def norm_loss_call(colour, rast, ref_u8, taps, grad_scale, eps=2.0, want_grad=Tr
     eps = float(eps)
     if not (eps > 0.0 and eps < float('inf')):
         raise ValueError(f"eps must be finite and positive, in grey levels (got {eps})")
-    colour, rast, ref_u8, taps = _window_args(colour, rast, ref_u8, taps, nonneg_taps=True)
+    taps = _window_args(colour, taps, nonneg_taps=True)
+    colour, rast, ref_u8 = _pixel_tensors(colour, rast, ref_u8)
     B, H, W, C = colour.shape
     with torch.cuda.device(colour.device):
         f32 = dict(dtype=torch.float32, device=colour.device)
@@ -749,28 +754,11 @@ def norm_loss_call(colour, rast, ref_u8, taps, grad_scale, eps=2.0, want_grad=Tr
         if want_grad:
             grad = torch.empty_like(colour)
             planes['pq'], planes['p'] = torch.empty(B, H, W, C, 2, **f32), torch.empty_like(colour)
-        p = _lib.NormLoss(color=_ptr(colour), rast=_ptr(rast), ref=_ptr(ref_u8), B=B, H=H, W=W, C=C, bg=float(background),
-                          color_scale=255.0, grad_scale=float(grad_scale), eps=eps, radius=(taps.numel() - 1) // 2, tmp=_ptr(tmp),
-                          stats=_ptr(stats), d=_ptr(planes['d']), pq=_ptr(planes.get('pq')), p=_ptr(planes.get('p')),
-                          loss_sum=_ptr(acc), grad_color=_ptr(grad))
+        p = _lib.NormLoss(**_pixel_head(colour, rast, ref_u8, background, grad_scale), eps=eps, tmp=_ptr(tmp), stats=_ptr(stats),
+                          d=_ptr(planes['d']), pq=_ptr(planes.get('pq')), p=_ptr(planes.get('p')), loss_sum=_ptr(acc), grad_color=_ptr(grad))
         _set_taps(p, taps)
         _lib.call("fpcdr_norm_loss", ctypes.byref(p), _stream())
     return acc, grad, planes
-
-
-def normalised_pixel_loss(colour, rast, ref_u8, sigma=None, kernel_size=31, eps=2.0, n_total=None, background=45.0 / 255.0, taps=None):
-    """mean over n_total elements (default: all of colour) of (n_a - n_t)^2, the render a = 255 * (rast.w > 0 ? colour : background) and
-    the capture t = ref each normalised by the mean and the deviation of its own Gaussian window, n = (x - G x) / sqrt(G x^2 - (G x)^2 +
-    eps^2) (DESIGN.md 3, "Normalised loss rule"; fpcdr_norm_loss): a camera's gain and offset drop out.  A dimensionless float32 scalar
-    whose backward is the closed-form gradient the same call computed, times the upstream scalar.  eps is in grey levels; taps= (odd,
-    3 .. 63 non-negative entries) overrides sigma and kernel_size.  Within a window the loss sees neither the level nor the contrast of the
-    texture: start from a baked or supplied texture, not from noise."""
-    if taps is None:
-        if sigma is None:
-            raise ValueError("normalised_pixel_loss needs sigma (or taps)")
-        taps = gaussian_taps(kernel_size, sigma)
-    return _windowed_pixel_loss_func.apply(norm_loss_call, float(n_total or colour.numel()), colour, rast, ref_u8, taps, float(eps), True,
-                                           background)
 
 
 def robust_args(kind, scale, weight_outside=1.0, saturation=0):
@@ -802,18 +790,11 @@ def robust_loss_call(colour, rast, ref_u8, kind, scale, grad_scale, mask=None, f
     of its values is a read-back; check_weights=False for a caller that has checked them once, as the Fitter has); weight_outside for
     uncovered pixels; saturation 1..255: capture pixels at or above it count nothing.  The weights are constants: they get no gradient."""
     kind_no, inv_c, weight_outside, saturation = robust_args(kind, scale, weight_outside, saturation)
-    if not (torch.is_tensor(colour) and colour.dim() == 4):
-        raise ValueError("colour must be a [B,H,W,C] tensor")
-    B, H, W, C = colour.shape
-    _check_tensor('colour', colour, torch.float32, 4)
-    _check_tensor('rast', rast, torch.float32, 4)
-    _check_tensor('ref_u8', ref_u8, torch.uint8, 3)
-    if tuple(rast.shape) != (B, H, W, 4) or tuple(ref_u8.shape) != (B, H, W):
-        raise ValueError(f"rast must be [B,H,W,4] and ref_u8 [B,H,W] for colour {tuple(colour.shape)}")
+    colour, rast, ref_u8 = _pixel_tensors(colour, rast, ref_u8)
     if mask is not None:
         _check_tensor('mask', mask, torch.uint8, 3)
-        if tuple(mask.shape) != (B, H, W):
-            raise ValueError(f"mask must be [B,H,W] = {(B, H, W)} (got {tuple(mask.shape)})")
+        if tuple(mask.shape) != tuple(ref_u8.shape):
+            raise ValueError(f"mask must be [B,H,W] = {tuple(ref_u8.shape)} (got {tuple(mask.shape)})")
         mask = mask.contiguous()
     T = 0
     if face_weights is not None:
@@ -824,29 +805,62 @@ def robust_loss_call(colour, rast, ref_u8, kind, scale, grad_scale, mask=None, f
         face_weights = face_weights.detach().contiguous()
         if check_weights and not bool((torch.isfinite(face_weights) & (face_weights >= 0)).all()):
             raise ValueError("face_weights must be finite and not negative")
-    colour, rast, ref_u8 = colour.detach().contiguous(), rast.detach().contiguous(), ref_u8.contiguous()
     with torch.cuda.device(colour.device):
         sums = torch.zeros(2, dtype=torch.float64, device=colour.device)
         grad = torch.empty_like(colour) if want_grad else None
-        p = _lib.RobustLoss(color=_ptr(colour), rast=_ptr(rast), ref=_ptr(ref_u8), B=B, H=H, W=W, C=C, bg=float(background),
-                            color_scale=255.0, grad_scale=float(grad_scale), kind=kind_no, inv_c=inv_c, w_outside=weight_outside,
+        p = _lib.RobustLoss(**_pixel_head(colour, rast, ref_u8, background, grad_scale), kind=kind_no, inv_c=inv_c, w_outside=weight_outside,
                             sat=saturation, mask=_ptr(mask), face_w=_ptr(face_weights), T=T, sums=_ptr(sums), grad_color=_ptr(grad))
         _lib.call("fpcdr_robust_loss", ctypes.byref(p), _stream())
     return sums, grad
 
 
-class _robust_pixel_loss_func(torch.autograd.Function):
-    """The mean over n_total of one robust_loss_call, and the gradient the same call computed, times the upstream scalar, as the backward."""
+class _pixel_loss_func(torch.autograd.Function):
+    """call = a *_loss_call with its keyword arguments bound, args = its positional arguments between colour and grad_scale: the mean over
+    n_total of the call's first sum, and the gradient the same call computed, times the upstream scalar, as the backward."""
     @staticmethod
-    def forward(ctx, colour, rast, ref_u8, n_total, kind, scale, kwargs):
-        sums, grad = robust_loss_call(colour, rast, ref_u8, kind, scale, 1.0 / n_total, **kwargs)
+    def forward(ctx, call, n_total, colour, *args):
+        sums, grad = call(colour, *args, 1.0 / n_total)[:2]
         ctx.save_for_backward(grad)
+        ctx.n_args = len(args)
         return (sums[0] / n_total).to(torch.float32)
 
     @staticmethod
     def backward(ctx, upstream):
         grad, = ctx.saved_tensors
-        return (grad * upstream, None, None, None, None, None, None)
+        return (None, None, grad * upstream) + (None,) * ctx.n_args
+
+
+def _mean_pixel_loss(call, colour, n_total, *args):
+    _colour_shape(colour)
+    return _pixel_loss_func.apply(call, float(n_total or colour.numel()), colour, *args)
+
+
+def _taps_of(what, sigma, kernel_size, taps):
+    """The "sigma or taps" of the windowed losses: taps= as given, else the Gaussian of (kernel_size, sigma)."""
+    if taps is not None:
+        return taps
+    if sigma is None:
+        raise ValueError(f"{what} needs sigma (or taps)")
+    return gaussian_taps(kernel_size, sigma)
+
+
+def blurred_pixel_loss(colour, rast, ref_u8, sigma=None, kernel_size=31, n_total=None, background=45.0 / 255.0, taps=None):
+    """mean over n_total elements (default: all of colour) of E^2, E = the Gaussian-blurred residual ref - 255 * (rast.w > 0 ? colour :
+    background) with reflected borders (DESIGN.md 3, "Blurred loss rule"; fpcdr_blur_loss) -- a float32 scalar whose backward is the
+    closed-form gradient the same call computed, times the upstream scalar.  taps= (odd, 3 .. 63 entries) overrides sigma and kernel_size."""
+    taps = _taps_of("blurred_pixel_loss", sigma, kernel_size, taps)
+    return _mean_pixel_loss(functools.partial(blur_loss_call, background=background), colour, n_total, rast, ref_u8, taps)
+
+
+def normalised_pixel_loss(colour, rast, ref_u8, sigma=None, kernel_size=31, eps=2.0, n_total=None, background=45.0 / 255.0, taps=None):
+    """mean over n_total elements (default: all of colour) of (n_a - n_t)^2, the render a = 255 * (rast.w > 0 ? colour : background) and
+    the capture t = ref each normalised by the mean and the deviation of its own Gaussian window, n = (x - G x) / sqrt(G x^2 - (G x)^2 +
+    eps^2) (DESIGN.md 3, "Normalised loss rule"; fpcdr_norm_loss): a camera's gain and offset drop out.  A dimensionless float32 scalar
+    whose backward is the closed-form gradient the same call computed, times the upstream scalar.  eps is in grey levels; taps= (odd,
+    3 .. 63 non-negative entries) overrides sigma and kernel_size.  Within a window the loss sees neither the level nor the contrast of the
+    texture: start from a baked or supplied texture, not from noise."""
+    taps = _taps_of("normalised_pixel_loss", sigma, kernel_size, taps)
+    return _mean_pixel_loss(functools.partial(norm_loss_call, eps=float(eps), background=background), colour, n_total, rast, ref_u8, taps)
 
 
 def robust_pixel_loss(colour, rast, ref_u8, kind='charbonnier', scale=None, n_total=None, mask=None, face_weights=None, weight_outside=1.0,
@@ -856,10 +870,9 @@ def robust_pixel_loss(colour, rast, ref_u8, kind='charbonnier', scale=None, n_to
     |d| >> c -- and w the product of the weights given ("Robust loss rule"; fpcdr_robust_loss).  The division is by
     n_total, not by the sum of the weights.  A float32 scalar whose backward is the closed-form gradient the same call computed, times
     the upstream scalar.  There is no default scale: nobody has measured one."""
-    kwargs = dict(mask=mask, face_weights=face_weights, weight_outside=weight_outside, saturation=saturation, background=background)
-    if not (torch.is_tensor(colour) and colour.dim() == 4):
-        raise ValueError("colour must be a [B,H,W,C] tensor")
-    return _robust_pixel_loss_func.apply(colour, rast, ref_u8, float(n_total or colour.numel()), kind, scale, kwargs)
+    call = functools.partial(robust_loss_call, mask=mask, face_weights=face_weights, weight_outside=weight_outside, saturation=saturation,
+                             background=background)
+    return _mean_pixel_loss(call, colour, n_total, rast, ref_u8, kind, scale)
 
 
 def undistort_images(images, intr, dist, clip_max=255, flip_rows=False):

@@ -1,34 +1,81 @@
-"""The fit step's host path with all three shape terms on, run to run and tree to tree.
+"""The fit step's host path, run to run and tree to tree: a script that is copied into two checkouts and imports the package of the tree
+it lies in, one fresh process per run.
 
-    python scripts/fit_terms_traj.py OUT.pt [--graph] [--steps N]       one fresh process per run; imports the package of the tree it lies in
+    python scripts/fit_terms_traj.py OUT.pt [--config NAME] [--graph] [--steps N]
     python scripts/fit_terms_traj.py --compare A.pt B.pt [--spread A2.pt A3.pt ...]
+    python scripts/fit_terms_traj.py --planes OUT.pt
+    python scripts/fit_terms_traj.py --compare-planes A.pt B.pt
+    python scripts/fit_terms_traj.py --time
 
-The first form runs a smoke-sized Fitter (cfg1, 4 frames, cameras 0 and 3, seed 0) with laplacian_relative, weight_stretch and weight_bend
-on for N (20) steps, eager or under the captured HIP graph, and saves the per-step losses and the final parameters.  The second form
-prints the largest relative difference of the losses and of the parameters (L2) between A and B, beside the largest among A and further
-runs of A's tree (--spread), and fails if B is further from A than those runs are from each other (the objective's float atomics make
-two runs of one tree differ)."""
+The first form runs a smoke-sized Fitter for N (20) steps and saves the per-step losses and the final parameters.  --config shape (the
+default): cfg1, 4 frames, cameras 0 and 3, seed 0, with laplacian_relative, weight_stretch and weight_bend on, eager or under the captured
+HIP graph.  --config default | unfused | blur | norm | robust: the pixel terms, on two frames of 64 x 64 and cameras 0 and 4 (robust: with
+masks and face weights); these also save the C-ABI calls of three steps by name and count (_lib.KernelTimer) and the device launches of
+one step (the torch profiler).  The second form prints the largest relative difference of the losses and of the parameters (L2) between A
+and B, beside the largest among A and further runs of A's tree (--spread), and fails if B is further from A than those runs are from each
+other (the objective's float atomics make two runs of one tree differ) or if the recorded calls or launches differ.
+
+--planes saves the sums and the gradient planes of fit.pixel_loss_fused / _blurred / _normalised / _robust at one small shape each, with
+and without n_total; --compare-planes holds the planes of B to torch.equal with A's and the float64 sums, which pass through atomics, to
+1e-12 relative.  --time prints the median step time of the unfused, blur, norm and robust configurations at cfg3's shape."""
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PIXEL_CONFIGS = {'default': {}, 'unfused': dict(fused_objective=False), 'blur': dict(blur_sigma=3.0, blur_kernel_size=15),
+                 'norm': dict(norm_sigma=3.0, norm_kernel_size=15), 'robust': dict(robust='charbonnier', robust_scale=10.0, weight_outside=0.25)}
 
 
-def run(out, graph, steps):
+def _pixel_fitter(name, sc, **kw):
+    """A Fitter of PIXEL_CONFIGS[name] on the scene; 'robust' gets seeded masks and face weights."""
+    import dataclasses
+    import numpy as np
+    from fpc_diffrend_amd import fit
+    kw = dict(PIXEL_CONFIGS[name], **kw)
+    if name == 'robust':
+        rng = np.random.default_rng(3)
+        sc = dataclasses.replace(sc, masks=rng.integers(0, 256, size=(sc.n_frames, len(sc.cams)) + tuple(sc.resolution), dtype=np.uint8))
+        kw['face_weights'] = rng.uniform(0.0, 1.5, size=sc.pos_idx.shape[0]).astype(np.float32)
+    ft = fit.Fitter(sc, fit.FitConfig(**kw), device='cuda')
+    ft.init_near_truth(0.8)
+    return ft
+
+
+def run(out, config, graph, steps):
     sys.path.insert(0, ROOT)
     import torch
-    from fpc_diffrend_amd import fit, scene
+    from fpc_diffrend_amd import _lib, fit, scene
     assert torch.cuda.is_available(), "needs the GPU"
-    sc = scene.cfg('cfg1', n_frames=4)
-    sc.q_gt[:] = (0.0, 0.0, 0.0, 1.0)
-    cfg = fit.FitConfig(max_iter=steps, cam_idxs=(0, 3), lr_base=5e-3, lr_t=5e-3, lr_q=1e-5, hip_graph=graph, seed=0,
-                        weight_laplacian=20.0, laplacian_relative=True, weight_stretch=2.0e3, weight_bend=2.0e4)
-    ft = fit.Fitter(sc, cfg, device='cuda')
-    ft.init_near_truth(0.8)
+    rec = {}
+    if config == 'shape':
+        sc = scene.cfg('cfg1', n_frames=4)
+        sc.q_gt[:] = (0.0, 0.0, 0.0, 1.0)
+        cfg = fit.FitConfig(max_iter=steps, cam_idxs=(0, 3), lr_base=5e-3, lr_t=5e-3, lr_q=1e-5, hip_graph=graph, seed=0,
+                            weight_laplacian=20.0, laplacian_relative=True, weight_stretch=2.0e3, weight_bend=2.0e4)
+        ft = fit.Fitter(sc, cfg, device='cuda')
+        ft.init_near_truth(0.8)
+    else:
+        sc = scene.make_scene(resolution=(64, 64), n_frames=2)
+        kw = dict(max_iter=steps, cam_idxs=(0, 4), seed=0)
+        ft = _pixel_fitter(config, sc, **kw)
+        _lib.TIMER = _lib.KernelTimer()
+        try:
+            for _ in range(3):
+                ft.step()
+            rec['calls'] = {k: n for k, (n, _) in _lib.TIMER.summary().items()}
+        finally:
+            _lib.TIMER = None
+        with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+            ft.step()
+            torch.cuda.synchronize()
+        rec['launches'] = sum(e.count for e in prof.key_averages() if e.device_type == torch.autograd.DeviceType.CUDA)
+        ft = _pixel_fitter(config, sc, **kw)
     losses = [float(ft.step()) for _ in range(steps)]
     torch.cuda.synchronize()
-    torch.save({'losses': losses, 'params': [p.detach().cpu() for p in ft.params]}, out)
-    print(f"{os.path.dirname(fit.__file__)}: graph={graph}, {steps} steps, loss {losses[0]:.6e} -> {losses[-1]:.6e} -> {out}")
+    torch.save(dict(rec, losses=losses, params=[p.detach().cpu() for p in ft.params]), out)
+    print(f"{os.path.dirname(fit.__file__)}: config={config} graph={graph}, {steps} steps, loss {losses[0]:.6e} -> {losses[-1]:.6e}, "
+          f"calls {rec.get('calls')}, launches of a step {rec.get('launches')} -> {out}")
 
 
 def compare(a_path, b_path, spread_paths):
@@ -50,12 +97,90 @@ def compare(a_path, b_path, spread_paths):
         sl, sp = max(p[0] for p in pairs), max(p[1] for p in pairs)
         line += f"; among {len(runs)} runs of A's tree: losses {sl:.3e}, parameters {sp:.3e}"
         ok = dl <= sl and dp <= sp
+    if 'calls' in a:
+        same = a['calls'] == b.get('calls') and a['launches'] == b.get('launches')
+        line += f"; C-ABI calls of three steps {sum(a['calls'].values())} in {len(a['calls'])} names, launches of a step {a['launches']}: " + \
+            ("the same" if same else f"DIFFERENT ({b.get('calls')}, {b.get('launches')})")
+        ok = ok and same
     print(line + ("" if ok else "   OUTSIDE"))
     return 0 if ok else 1
+
+
+def planes(out):
+    """The four pixel-loss wrappers of fit.py on seeded tensors, one small shape each with a ragged tail, with and without n_total."""
+    sys.path.insert(0, ROOT)
+    import torch
+    from fpc_diffrend_amd import fit, ops
+    g = torch.Generator().manual_seed(0)
+    T = 40
+    taps = ops.gaussian_taps(7, 1.5)
+    calls = {'fused': ((1, 5, 67, 3), lambda t, n: fit.pixel_loss_fused(*t[:3], n)),
+             'blurred': ((2, 37, 70, 1), lambda t, n: fit.pixel_loss_blurred(*t[:3], taps, n)),
+             'normalised': ((1, 33, 65, 3), lambda t, n: fit.pixel_loss_normalised(*t[:3], taps, 1.5, n)),
+             'robust': ((2, 19, 131, 1), lambda t, n: fit.pixel_loss_robust(*t[:3], 'geman_mcclure', 12.0, n, mask=t[3], face_weights=t[4],
+                                                                           weight_outside=0.5, saturation=130))}
+    rec = {}
+    for name, ((B, H, W, C), call) in calls.items():
+        colour = torch.rand(B, H, W, C, generator=g).cuda()
+        rast = torch.zeros(B, H, W, 4)
+        rast[..., 3] = torch.randint(1, T + 1, (B, H, W), generator=g).float() * (torch.rand(B, H, W, generator=g) > 0.4)
+        ref = torch.randint(0, 141, (B, H, W), generator=g, dtype=torch.uint8).cuda()
+        mask = torch.randint(0, 256, (B, H, W), generator=g, dtype=torch.uint8).cuda()
+        t = (colour, rast.cuda(), ref, mask, (torch.rand(T, generator=g) * 1.5).cuda())
+        for n in (None, 3 * colour.numel() + 1):
+            sums, grad = call(t, n)
+            rec[f"{name} n_total={n}"] = (sums.cpu(), grad.cpu())
+    torch.save(rec, out)
+    print(f"{os.path.dirname(fit.__file__)}: {len(rec)} (sums, gradient plane) pairs -> {out}")
+
+
+def compare_planes(a_path, b_path):
+    import torch
+    a, b = torch.load(a_path), torch.load(b_path)
+    assert list(a) == list(b)
+    bad = 0
+    for key in a:
+        (sa, ga), (sb, gb) = a[key], b[key]
+        ds = float(((sa - sb).abs() / sa.abs()).max())
+        ok = torch.equal(ga, gb) and float(ga.abs().max()) > 0 and ds <= 1e-12
+        bad += not ok
+        print(f"{key:34s} gradient plane {tuple(ga.shape)} torch.equal: {torch.equal(ga, gb)}; sums differ by {ds:.1e} relative{'' if ok else '   FAIL'}")
+    return 1 if bad else 0
+
+
+def step_times(steps=8):
+    """Milliseconds of a whole Fitter step at cfg3's shape per pixel-term configuration: host clock around step() + synchronise, the
+    median of `steps` after 3 warm-up steps."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    from fpc_diffrend_amd import fit, scene
+    sc = scene.cfg('cfg3')
+    for name in ('unfused', 'blur', 'norm', 'robust'):
+        ft = _pixel_fitter(name, sc)
+        for _ in range(3):
+            ft.step()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(steps):
+            t0 = time.perf_counter()
+            ft.step()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        print(f"STEP_MS {name} {float(np.median(ts)):.3f}   ({os.path.dirname(fit.__file__)})", flush=True)
+        del ft
+        torch.cuda.empty_cache()
 
 
 if __name__ == "__main__":
     arg = lambda name, default: sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
     if sys.argv[1] == "--compare":
         sys.exit(compare(sys.argv[2], sys.argv[3], sys.argv[sys.argv.index("--spread") + 1:] if "--spread" in sys.argv else []))
-    run(sys.argv[1], "--graph" in sys.argv, int(arg("--steps", "20")))
+    if sys.argv[1] == "--compare-planes":
+        sys.exit(compare_planes(sys.argv[2], sys.argv[3]))
+    if sys.argv[1] == "--planes":
+        planes(sys.argv[2])
+    elif sys.argv[1] == "--time":
+        step_times()
+    else:
+        run(sys.argv[1], arg("--config", "shape"), "--graph" in sys.argv, int(arg("--steps", "20")))

@@ -1,8 +1,18 @@
 """Shared builders for the parity tests (seeded synthetic inputs; nothing reads /root/reference)."""
+import os
+
 import numpy as np
 import torch
 
 from fpc_diffrend_amd import camera, scene
+
+
+def lib_loaded():
+    """(the _lib module, the loaded product library), both libraries built first when one is missing."""
+    from fpc_diffrend_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH) or not os.path.exists(_lib.TWOCALL_LIB_PATH):
+        _lib.build()
+    return _lib, _lib.load()
 
 
 def rel_l2(a, b):

@@ -2,11 +2,9 @@
 feature (ops.gaussian_taps, FitConfig, the C ABI's new entry) -- no GPU.  The fold formula of the reflecting blur's adjoint is the
 statement tests/test_gpu_blur.py judges the kernel's gradient by; here it is compared with torch.autograd through F.pad(reflect) +
 conv2d at every shape the GPU file uses."""
-import ctypes
 import dataclasses
 import os
 import re
-import subprocess
 import sys
 
 import pytest
@@ -20,6 +18,7 @@ for p in (HERE, ROOT):
 
 import blur_ref as B  # noqa: E402
 import fitstep_ref as R  # noqa: E402
+from helpers import lib_loaded  # noqa: E402
 
 
 @pytest.mark.parametrize("shape", B.SHAPES, ids=lambda s: "x".join(str(v) for v in s[:5]))
@@ -90,32 +89,14 @@ def test_fitconfig_has_the_blur_fields_off_by_default():
 
 
 def test_library_exports_the_blur_entry_with_abi_16_and_the_binding_mirrors_the_header():
-    from fpc_diffrend_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    lib = _lib.load()
+    """(size and field offsets of the struct against the C compiler's: test_host_logic.py, for every parameter struct of the header)"""
+    _lib, lib = lib_loaded()
     assert _lib.ABI_VERSION == 16 and lib.fpcdr_abi_version() == 16
     assert hasattr(lib, "fpcdr_blur_loss") and hasattr(lib, "fpcdr_blur_loss_scratch_bytes")
     assert lib.fpcdr_blur_loss_scratch_bytes(2, 37, 70, 3) == 2 * 37 * 70 * 3 * 4
     assert lib.fpcdr_blur_loss_scratch_bytes(0, 37, 70, 3) == 0
     header = open(os.path.join(ROOT, "include", "fpcdr.h")).read()
     assert re.search(r"#define FPCDR_ABI_VERSION 16\b", header)
-    # size and field offsets of the parameter struct: ask the C compiler
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "sz.c")
-        with open(src, "w") as f:
-            f.write('#include <stdio.h>\n#include <stddef.h>\n#include "fpcdr.h"\nint main(void) {\n')
-            f.write('    printf("size %zu\\n", sizeof(fpcdr_blur_loss_params));\n')
-            for field, _ in _lib.BlurLoss._fields_:
-                f.write(f'    printf("{field} %zu\\n", offsetof(fpcdr_blur_loss_params, {field}));\n')
-            f.write("    return 0;\n}\n")
-        exe = os.path.join(td, "sz")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        sizes = dict(l.split() for l in subprocess.check_output([exe]).decode().splitlines())
-    assert ctypes.sizeof(_lib.BlurLoss) == int(sizes["size"])
-    for field, _ in _lib.BlurLoss._fields_:
-        assert getattr(_lib.BlurLoss, field).offset == int(sizes[field]), field
 
 
 def test_blur_kernels_have_no_private_segment():

@@ -134,6 +134,34 @@ def test_pixel_loss_fused_equals_reference_chain():
     assert e_gpu <= 8 * e32 + 4, (e_gpu, e32)
 
 
+def test_pixel_loss_fused_and_pixel_loss_call_check_their_tensors_and_agree():
+    """fit.pixel_loss_fused is ops.pixel_loss_call with grad_scale = 1 / n_total: both refuse what the kernel must not be handed, and
+    return the same gradient plane (and the same float64 sum, up to the order of its atomics) for a contiguous input.  (1, 5, 67, 3):
+    the smallest shape with a ragged tail."""
+    import fpc_diffrend_amd.ops as dr
+    from fpc_diffrend_amd import fit
+    g = torch.Generator().manual_seed(3)
+    B, H, W, C = 1, 5, 67, 3
+    colour = torch.rand(B, H, W, C, generator=g).cuda()
+    rast = torch.zeros(B, H, W, 4)
+    rast[..., 3] = (torch.rand(B, H, W, generator=g) > 0.4).float() * 7
+    rast = rast.cuda()
+    ref = torch.randint(0, 141, (B, H, W), generator=g, dtype=torch.uint8).cuda()
+    n = colour.numel()
+    for bad in (dict(rast=rast.cpu()), dict(ref=ref.float()), dict(rast=rast[:, :, :-1].contiguous()), dict(ref=ref[:, :-1].contiguous())):
+        args = (colour, bad.get('rast', rast), bad.get('ref', ref))
+        with pytest.raises(ValueError):
+            fit.pixel_loss_fused(*args)
+        with pytest.raises(ValueError):
+            dr.pixel_loss_call(*args, 1.0 / n)
+    s0, g0 = fit.pixel_loss_fused(colour, rast, ref)
+    s1, g1 = dr.pixel_loss_call(colour, rast, ref, 1.0 / n, fit.BACKGROUND)
+    assert float(g0.abs().max()) > 0 and torch.equal(g0, g1)
+    assert abs(float(s0[0]) - float(s1[0])) <= 1e-12 * abs(float(s1[0]))
+    s2, none = dr.pixel_loss_call(colour, rast, ref, 1.0 / n, want_grad=False)
+    assert none is None and abs(float(s2[0]) - float(s1[0])) <= 1e-12 * abs(float(s1[0]))
+
+
 def test_smoke_step_matches_oracle(oracle_ops):
     from fpc_diffrend_amd import fit, scene
     from oracle import fit as ofit

@@ -151,8 +151,10 @@ def test_abi_library_exports_every_declared_symbol():
              "fpcdr_texture_fwd_params": _lib.TextureFwd, "fpcdr_texture_bwd_params": _lib.TextureBwd,
              "fpcdr_antialias_fwd_params": _lib.AntialiasFwd, "fpcdr_antialias_bwd_params": _lib.AntialiasBwd,
              "fpcdr_pixel_loss_params": _lib.PixelLoss, "fpcdr_adam_params": _lib.AdamParams,
-             "fpcdr_objective_params": _lib.Objective}
-    structs = set(re.findall(r"\}\s*(fpcdr_[a-z0-9_]+_params)\s*;", header))
+             "fpcdr_objective_params": _lib.Objective, "fpcdr_blur_loss_params": _lib.BlurLoss,
+             "fpcdr_norm_loss_params": _lib.NormLoss, "fpcdr_robust_loss_params": _lib.RobustLoss}
+    # (both typedef styles of the header: `typedef struct { ... } name;` and `typedef struct name name; struct name { ... };`)
+    structs = {a or b for a, b in re.findall(r"\}\s*(fpcdr_[a-z0-9_]+_params)\s*;|^struct (fpcdr_[a-z0-9_]+_params) \{", header, flags=re.M)}
     assert structs == set(pairs), structs ^ set(pairs)
     with tempfile.TemporaryDirectory() as td:
         src = os.path.join(td, "sz.c")
@@ -367,3 +369,59 @@ def test_bench_launcher_decides_from_the_command_line_and_fails_with_its_ranks()
     err = r.stderr.decode(errors="replace")
     assert r.returncode != 0 and "bench.py launcher (--gpus 2)" in err and "needs a GPU" in err, err[-2000:]
     assert not r.stdout.decode().strip().startswith("{")
+
+
+def test_pixel_term_schedule_is_the_table_of_the_design():
+    """fit.pixel_term by DESIGN.md 3 ("Which pixel term an iteration runs"): a term lasts for iterations i < its *_iters, for every
+    iteration with *_iters = 0; afterwards the path the other flags select (None), or kind 'l2' when weights are on."""
+    import blur_ref
+    from fpc_diffrend_amd import fit
+    BIG = 10 ** 6
+    blur, norm = lambda s: ('blur', blur_ref.taps(15, s)), ('norm', blur_ref.taps(9, 2.0), 1.5)
+    l2 = ('robust', 'l2', None)
+    nk = dict(norm_sigma=2.0, norm_kernel_size=9, norm_eps=1.5)
+    table = [(dict(), False, {0: None, BIG: None}),
+             (dict(blur_sigma=3.0, blur_kernel_size=15, blur_iters=5), False, {0: blur(3.0), 4: blur(3.0), 5: None, BIG: None}),
+             (dict(blur_sigma=3.0, blur_kernel_size=15), False, {0: blur(3.0), BIG: blur(3.0)}),
+             # sigma goes geometrically from blur_sigma to blur_sigma_end over the blurred iterations (max_iter of them with blur_iters = 0)
+             (dict(blur_sigma=4, blur_sigma_end=1, blur_kernel_size=15, blur_iters=3), False, {0: blur(4.0), 1: blur(2.0), 2: blur(1.0), 3: None}),
+             (dict(blur_sigma=4, blur_sigma_end=1, blur_kernel_size=15, max_iter=3), False, {0: blur(4.0), 1: blur(2.0), 2: blur(1.0), BIG: blur(1.0)}),
+             (dict(blur_sigma=4, blur_sigma_end=1, blur_kernel_size=15, blur_iters=1), False, {0: blur(4.0), 1: None}),
+             (dict(norm_iters=3, **nk), False, {0: norm, 2: norm, 3: None, BIG: None}),
+             (dict(**nk), False, {0: norm, BIG: norm}),
+             (dict(robust='l2', robust_iters=2), False, {0: l2, 1: l2, 2: None, BIG: None}),
+             (dict(weight_outside=0.5), True, {0: l2, BIG: l2}), (dict(), True, {0: l2, BIG: l2})]      # weights only; a Scene's masks alone
+    for kind in ('charbonnier', 'geman_mcclure'):
+        on = ('robust', kind, 10.0)
+        table += [(dict(robust=kind, robust_scale=10.0, robust_iters=2), False, {0: on, 1: on, 2: None, BIG: None}),
+                  (dict(robust=kind, robust_scale=10.0, robust_iters=2, saturation=140), True, {0: on, 1: on, 2: l2, BIG: l2}),
+                  (dict(robust=kind, robust_scale=10.0), False, {0: on, BIG: on})]
+    for kw, weighted, expected in table:
+        cfg = fit.FitConfig(**kw)
+        for i, want in expected.items():
+            got = fit.pixel_term(cfg, i, weighted)
+            assert (got is None) == (want is None) and (got is None or len(got) == len(want)), (kw, i, got)
+            for g, w in zip(got or (), want or ()):
+                assert torch.equal(g, w) if torch.is_tensor(w) else g == w, (kw, i, got)
+
+
+def test_pixel_term_rules_need_no_fitter():
+    """fit.check_pixel_terms: every combination the GPU files see a Fitter refuse, by the options its message names, and what it accepts."""
+    from fpc_diffrend_amd import fit
+    bk, nk = dict(blur_sigma=3.0, blur_kernel_size=15), dict(norm_sigma=3.0, norm_kernel_size=15)
+    refused = [(dict(robust='l2', fused_loss=False), False, ("robust", "fused_loss")), (dict(saturation=140, hip_graph=True), False, ("saturation", "hip_graph")),
+               (dict(hip_graph=True), True, ("masks", "hip_graph")), (dict(fused_loss=False), True, ("masks", "fused_loss")),
+               (bk, True, ("masks", "blur_sigma")), (nk, True, ("masks", "norm_sigma")),
+               (dict(fused_loss=False, **bk), False, ("blur_sigma", "fused_loss")), (dict(hip_graph=True, **bk), False, ("blur_sigma", "hip_graph")),
+               (dict(hip_graph='auto', **bk), False, ("blur_sigma", "hip_graph")),      # 'auto' counts as on
+               (dict(fused_loss=False, **nk), False, ("norm_sigma", "fused_loss")), (dict(hip_graph=True, **nk), False, ("norm_sigma", "hip_graph")),
+               (dict(norm_eps=0.0, **nk), False, ("norm_eps",)), (dict(blur_sigma=3.0, blur_kernel_size=14), False, ("kernel_size",)),
+               (dict(blur_sigma_end=0.0, **bk), False, ("sigma",))]
+    for kw, has_masks, words in refused:
+        with pytest.raises(ValueError) as ei:
+            fit.check_pixel_terms(fit.FitConfig(**kw), has_masks)
+        assert all(w in str(ei.value) for w in words), (kw, str(ei.value))
+    for kw, has_masks in [(dict(), False), (dict(), True), (dict(use_masks=False, **bk), True), (dict(use_masks=False, hip_graph=True), True),
+                          (dict(blur_sigma_end=1.0, **bk), False), (nk, False), (dict(fused_loss=False, hip_graph=True), False),
+                          (dict(robust='charbonnier', robust_scale=10.0, face_weights=[1.0], saturation=140, weight_outside=0.0), True)]:
+        fit.check_pixel_terms(fit.FitConfig(**kw), has_masks)

@@ -10,7 +10,6 @@ import ctypes
 import dataclasses
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -25,6 +24,7 @@ for p in (HERE, ROOT):
 
 import blur_ref as B  # noqa: E402
 import norm_ref as N  # noqa: E402
+from helpers import lib_loaded  # noqa: E402
 
 _ids = lambda s: "x".join(str(v) for v in s[:5])
 
@@ -130,36 +130,15 @@ def test_fitconfig_has_the_norm_fields_off_by_default_and_excludes_the_blur():
     fit.FitConfig(norm_sigma=3.0, norm_kernel_size=15, norm_iters=5)
 
 
-def _lib_loaded():
-    from fpc_diffrend_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return _lib, _lib.load()
-
-
 def test_library_exports_the_norm_entry_with_abi_16_and_the_binding_mirrors_the_header():
-    _lib, lib = _lib_loaded()
+    """(size and field offsets of the struct against the C compiler's: test_host_logic.py, for every parameter struct of the header)"""
+    _lib, lib = lib_loaded()
     assert _lib.ABI_VERSION == 16 and lib.fpcdr_abi_version() == 16
     assert hasattr(lib, "fpcdr_norm_loss") and hasattr(lib, "fpcdr_norm_loss_scratch_bytes")
     assert lib.fpcdr_norm_loss_scratch_bytes(2, 37, 70, 3) == 2 * 37 * 70 * 3 * 4
     assert lib.fpcdr_norm_loss_scratch_bytes(2, 0, 70, 3) == 0
     header = open(os.path.join(ROOT, "include", "fpcdr.h")).read()
     assert re.search(r"#define FPCDR_ABI_VERSION 16\b", header)
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "sz.c")
-        with open(src, "w") as f:
-            f.write('#include <stdio.h>\n#include <stddef.h>\n#include "fpcdr.h"\nint main(void) {\n')
-            f.write('    printf("size %zu\\n", sizeof(fpcdr_norm_loss_params));\n')
-            for field, _ in _lib.NormLoss._fields_:
-                f.write(f'    printf("{field} %zu\\n", offsetof(fpcdr_norm_loss_params, {field}));\n')
-            f.write("    return 0;\n}\n")
-        exe = os.path.join(td, "sz")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        sizes = dict(l.split() for l in subprocess.check_output([exe]).decode().splitlines())
-    assert ctypes.sizeof(_lib.NormLoss) == int(sizes["size"])
-    for field, _ in _lib.NormLoss._fields_:
-        assert getattr(_lib.NormLoss, field).offset == int(sizes[field]), field
     assert [f for f, _ in _lib.NormLoss._fields_][:10] == [f for f, _ in _lib.BlurLoss._fields_][:10]      # (the style of the blur's struct)
 
 
@@ -168,7 +147,7 @@ def test_bad_arguments_give_an_error_code_before_any_launch():
     its error code from the argument checks, which come before the first HIP call -- so this runs on a machine without a GPU, on host
     memory the entry never touches.  An even kernel cannot be written into the C struct (it takes a radius); ops rejects it, with eps
     and the radius, before it looks at the tensors."""
-    _lib, lib = _lib_loaded()
+    _lib, lib = lib_loaded()
     Bn, H, W, C = 1, 12, 9, 1
     n = Bn * H * W * C
     bufs = {name: (ctypes.c_float * (k * n + 4))() for name, k in (('color', 1), ('rast', 4), ('tmp', 4), ('stats', 4), ('d', 1), ('pq', 2),

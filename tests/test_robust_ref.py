@@ -10,7 +10,6 @@ import dataclasses
 import decimal
 import os
 import re
-import subprocess
 import sys
 import tempfile
 
@@ -25,6 +24,7 @@ for p in (HERE, ROOT):
         sys.path.insert(0, p)
 
 import robust_ref as RR  # noqa: E402
+from helpers import lib_loaded  # noqa: E402
 
 _ids = lambda s: "x".join(str(v) for v in s)
 
@@ -183,15 +183,9 @@ def test_fitconfig_has_the_robust_fields_off_by_default_and_validates_them():
             fit.load_face_weights(bad, 3)
 
 
-def _lib_loaded():
-    from fpc_diffrend_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH) or not os.path.exists(_lib.TWOCALL_LIB_PATH):
-        _lib.build()
-    return _lib, _lib.load()
-
-
 def test_both_libraries_export_the_robust_entry_with_abi_16_and_the_binding_mirrors_the_header():
-    _lib, lib = _lib_loaded()
+    """(size and field offsets of the struct against the C compiler's: test_host_logic.py, for every parameter struct of the header)"""
+    _lib, lib = lib_loaded()
     assert _lib.ABI_VERSION == 16 and lib.fpcdr_abi_version() == 16
     assert "fpcdr_robust_loss" in _lib.SYMBOLS
     for path in (_lib.LIB_PATH, _lib.TWOCALL_LIB_PATH):
@@ -201,27 +195,13 @@ def test_both_libraries_export_the_robust_entry_with_abi_16_and_the_binding_mirr
     assert re.search(r"int fpcdr_robust_loss\(const fpcdr_robust_loss_params \*p?, void \*stream\);", header)
     for name, number in _lib.ROBUST_KIND.items():
         assert re.search(rf"#define FPCDR_ROBUST_{name.upper()} {number}\b", header), name
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "sz.c")
-        with open(src, "w") as f:
-            f.write('#include <stdio.h>\n#include <stddef.h>\n#include "fpcdr.h"\nint main(void) {\n')
-            f.write('    printf("size %zu\\n", sizeof(fpcdr_robust_loss_params));\n')
-            for field, _ in _lib.RobustLoss._fields_:
-                f.write(f'    printf("{field} %zu\\n", offsetof(fpcdr_robust_loss_params, {field}));\n')
-            f.write("    return 0;\n}\n")
-        exe = os.path.join(td, "sz")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        sizes = dict(l.split() for l in subprocess.check_output([exe]).decode().splitlines())
-    assert ctypes.sizeof(_lib.RobustLoss) == int(sizes["size"])
-    for field, _ in _lib.RobustLoss._fields_:
-        assert getattr(_lib.RobustLoss, field).offset == int(sizes[field]), field
     assert [f for f, _ in _lib.RobustLoss._fields_][:10] == [f for f, _ in _lib.PixelLoss._fields_][:10]      # (the style of the pixel loss's struct)
 
 
 def test_bad_arguments_give_an_error_code_before_any_launch():
     """Every error of the ABI entry comes from its argument checks, ahead of the first HIP call: this runs without a GPU, on host memory
     the entry never touches.  ops rejects the same on the host, before it looks at the tensors."""
-    _lib, lib = _lib_loaded()
+    _lib, lib = lib_loaded()
     Bn, H, W, C, T = 1, 5, 7, 1, 4
     n = Bn * H * W
     col, rast, grad, fw = ((ctypes.c_float * k)() for k in (n * C, 4 * n, n * C, T))
