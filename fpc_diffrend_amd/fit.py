@@ -38,6 +38,7 @@ from .mesh_reg import (MeshTopology, RestShape, _uniform_laplacian, bend_penalty
                        laplacian_penalty, mesh_edge_loss, mesh_laplacian_smoothing, mesh_normal_consistency, motion_inv_scale,
                        motion_penalty, rest_edge_lengths, stretch_penalty)
 from .ops import _ptr, _stream
+from .tex_prior import chart_map, check_tex_prior_options, load_texel_weights, tex_prior_inv_scale, texture_prior
 
 BACKGROUND = 45.0 / 255.0  # reference fit.py:161
 
@@ -626,6 +627,21 @@ class FitConfig:
                                     # nobody has measured one
     motion_vertex_weights: object = None     # one weight per vertex, finite and >= 0 (0: lips and eyelids left free; large: skull and neck
                                     # held stiff): an array-like [V] or the path of a text file with one number per vertex
+    weight_tex_smooth: float = 0.0  # > 0: neighbouring texels are held together ("Texture prior rule"): the texels no camera
+                                    # sees, or a mask takes out, get a gradient from their neighbours instead of none, and high-frequency
+                                    # texture that explains a misplaced mesh is charged for.  Value and gradient from one call in front of
+                                    # the objective, on the texture itself, whatever the pyramid level or mip.  0 = off: nothing changes
+    tex_smooth_scale: Optional[float] = None     # the Charbonnier scale c in texture units (0..1), finite and > 0: quadratic below c, linear
+                                    # above it, so that an edge of the texture is not smeared.  None: plain squares.  No default value --
+                                    # nobody has measured one
+    tex_smooth_weights: object = None            # one weight per texel, finite and >= 0; a pair takes the smaller of its two: an array-like
+                                    # [Ht,Wt], the path of an 8-bit image (byte / 255, oriented as the texture.png a fit writes), or
+                                    # 'chart': 1 on the texels the render can read (fit.chart_map), 0 elsewhere.  None: 1
+    weight_tex_anchor: float = 0.0  # > 0: the texture is held to the texture the Fitter started with (after init_texture; re-snapshot with
+                                    # Fitter.set_texture_anchor): under norm_sigma it is what keeps the level and contrast of a baked or
+                                    # supplied texture.  0 = off: nothing changes
+    tex_anchor_weights: object = None            # as tex_smooth_weights, per texel.  None: 1 -- or, with init_texture='bake', the bake's
+                                    # `filled` map: only the texels a capture reached are held
     cam_idxs: Sequence[int] = (0, 1, 2, 3, 4, 5, 6, 7, 8)
     mode: str = "prior"
     regularize_correctives: bool = False
@@ -731,6 +747,7 @@ class FitConfig:
         if self.weight_motion and 0 < self.frames_per_step < self.motion_order + 1:
             raise ValueError(f"FitConfig.weight_motion > 0 with motion_order={self.motion_order} needs frames_per_step = 0 or >= "
                              f"{self.motion_order + 1} (got {self.frames_per_step}): fewer frames hold no stencil")
+        check_tex_prior_options(self)
 
     def weights_configured(self):
         """Whether the options alone (without a Scene's masks) put iterations on the weighted robust pixel term."""
@@ -955,10 +972,73 @@ class Fitter:
                 lres = (self.resolution[0] // s, self.resolution[1] // s)
                 lm = dr.downsample_images(self.full_masks, s) if self.full_masks is not None else None
                 self._levels[s] = (lt, lres, dr.reference_background_sumsq(lt.reshape(-1, *lres), BACKGROUND).reshape(lt.shape[:2]), lm)
+        baked = None
         if cfg.init_texture == 'bake':
-            self.bake_texture()
+            _, baked = self.bake_texture()
+        # ---- the texture's prior ("Texture prior rule"): its maps, and the anchor = the texture as it stands now.  Both
+        # weights 0: nothing is built, nothing is launched ----
+        self._tex_anchor, self._tex_anchor_w, self._tex_smooth_w, self._tex_chart = None, None, None, None
+        self._tex_prior_on = bool(cfg.weight_tex_smooth or cfg.weight_tex_anchor)
+        if self._tex_prior_on:
+            self._tex_smooth_w = self._texel_weights(cfg.tex_smooth_weights, 'tex_smooth_weights') if cfg.weight_tex_smooth else None
+            if cfg.weight_tex_anchor:
+                w = cfg.tex_anchor_weights
+                if w is None and baked is not None:      # only the texels a capture reached are worth holding
+                    w = baked.to(torch.float32)
+                self.set_texture_anchor(weights=w)
         if self._levels is not None:
             self._set_level(self.pyramid_factor())
+
+    # ------------------------------------------------------------------------------------------
+    def texture_chart(self):
+        """fit.chart_map of this Fitter's UV mesh at its texture's resolution, float32 [Ht,Wt], built on the first call and kept."""
+        if self._tex_chart is None:
+            self._tex_chart = chart_map(self.uv, self.uv_idx, self.tex_opt.shape[0], self.tex_opt.shape[1])
+        return self._tex_chart
+
+    def _texel_weights(self, weights, option):
+        """A per-texel map of FitConfig (see tex_smooth_weights) or of set_texture_anchor as a float32 device tensor [Ht,Wt], or None."""
+        if weights is None:
+            return None
+        Ht, Wt = int(self.tex_opt.shape[0]), int(self.tex_opt.shape[1])
+        if isinstance(weights, str) and weights == 'chart':
+            return self.texture_chart()
+        if torch.is_tensor(weights):
+            weights = weights.detach().cpu().numpy()
+        return torch.from_numpy(load_texel_weights(weights, Ht, Wt, option)).to(self.device)
+
+    @torch.no_grad()
+    def set_texture_anchor(self, tex=None, weights=None):
+        """Re-snapshot the anchor of FitConfig.weight_tex_anchor: tex [Ht,Wt,C] (None: the texture as it stands now), weights as
+        FitConfig.tex_anchor_weights (None: the weights stay as they are).  The buffers a captured step reads are written in place, so
+        it replays with the new anchor; the first set of weights of a Fitter that had none is a new capture."""
+        if not self.cfg.weight_tex_anchor:
+            raise ValueError("Fitter.set_texture_anchor needs FitConfig.weight_tex_anchor > 0: without it no step reads an anchor")
+        src = self.tex_opt if tex is None else torch.as_tensor(tex, dtype=torch.float32)
+        if tuple(src.shape) != tuple(self.tex_opt.shape):
+            raise ValueError(f"Fitter.set_texture_anchor: tex must be {tuple(self.tex_opt.shape)} (got {tuple(src.shape)})")
+        src = src.detach().to(self.device, torch.float32)
+        if not bool(torch.isfinite(src).all()):
+            raise ValueError("Fitter.set_texture_anchor: the anchor must be finite")
+        if self._tex_anchor is None:
+            self._tex_anchor = src.clone().contiguous()
+        else:
+            self._tex_anchor.copy_(src)
+        if weights is not None:
+            w = self._texel_weights(weights, 'tex_anchor_weights')
+            if self._tex_anchor_w is None:
+                self._tex_anchor_w = w.clone()
+                self._graphs, self._graph_key = None, None
+            else:
+                self._tex_anchor_w.copy_(w)
+
+    def _tex_prior_term(self, **modes):
+        """The step's texture prior at the current texture.  The weights carry the 1 / world: the gradients are summed over the ranks and
+        the texture is replicated, so every rank adds the same share."""
+        cfg, world = self.cfg, self.world
+        return texture_prior(self.tex_opt, cfg.weight_tex_smooth / world, cfg.weight_tex_anchor / world, anchor=self._tex_anchor,
+                             smooth_weights=self._tex_smooth_w, anchor_weights=self._tex_anchor_w, scale=cfg.tex_smooth_scale,
+                             validate=False, **modes)
 
     # ------------------------------------------------------------------------------------------
     @staticmethod
@@ -1344,6 +1424,8 @@ class Fitter:
         # consecutive (no frame numbers to hand over), an index tensor names them
         step_ids = frame_ids if torch.is_tensor(frame_ids) else None
         terms = [reg_term(vtx_pos_split, step_ids) for reg_term in self._reg_terms]
+        if self._tex_prior_on:      # the texture's prior: once per step on the texture itself, whatever the level or mip
+            terms.append(self._tex_prior_term(eager_grad=True, unit_upstream=True, acc=self._reg_acc))
         self.optimizer.zero_grad(set_to_none=True)
         if one_shot:
             bg_sum = None
@@ -1527,6 +1609,11 @@ class Fitter:
                     rec["MOT"] = float(motion_penalty(v, cfg.weight_motion, frame_ids=frame_ids if torch.is_tensor(frame_ids) else None,
                                                       order=cfg.motion_order, scale=cfg.motion_scale, vertex_weights=self._motion_w,
                                                       validate=False))
+                if self._tex_prior_on:     # (likewise)
+                    _, part, _ = dr.tex_prior_call(self.tex_opt.detach(), cfg.weight_tex_smooth, cfg.weight_tex_anchor, self._tex_anchor,
+                                                   self._tex_smooth_w, self._tex_anchor_w, tex_prior_inv_scale(cfg.tex_smooth_scale),
+                                                   want_grad=False)
+                    rec["TEXS"], rec["TEXA"] = float(cfg.weight_tex_smooth * part[0]), float(cfg.weight_tex_anchor * part[1])
         if rec is None:
             return
         line = json.dumps(rec)
@@ -1616,7 +1703,10 @@ class Fitter:
                 "skipped_per_tensor": self.skipped_steps_per_tensor(),      # each tensor its own; the schedule the total)
                 "result": self.result.clone(),      # this rank's rows (others zero): checkpoints are per rank
                 "frame_range": (self.frame_lo, self.frame_hi),
-                "config": dict(self.cfg.__dict__)}
+                "config": dict(self.cfg.__dict__),
+                # (the texture prior's anchor and its weights: None without the term; a checkpoint without the keys loads as before)
+                "tex_anchor": None if self._tex_anchor is None else self._tex_anchor.clone(),
+                "tex_anchor_weights": None if self._tex_anchor_w is None else self._tex_anchor_w.clone()}
 
     def load_state_dict(self, state):
         with torch.no_grad():
@@ -1641,6 +1731,8 @@ class Fitter:
             self._forget_skips(total, per)
         self.rng.bit_generator.state = state["rng"]
         self.result.copy_(state["result"].to(self.result.device))
+        if self._tex_anchor is not None and state.get("tex_anchor") is not None:      # (without the key the anchor stays as constructed)
+            self.set_texture_anchor(state["tex_anchor"], state.get("tex_anchor_weights"))
         self._graphs, self._graph_key = None, None
         if self._levels is not None:
             self._set_level(self.pyramid_factor())

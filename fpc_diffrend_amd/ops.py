@@ -814,6 +814,24 @@ def robust_loss_call(colour, rast, ref_u8, kind, scale, grad_scale, mask=None, f
     return sums, grad
 
 
+def tex_prior_call(tex, w_smooth, w_anchor, anchor=None, smooth_weights=None, anchor_weights=None, inv_c=0.0, want_grad=True, acc=None):
+    """One fpcdr_tex_prior call ("Texture prior rule") on tensors the caller has checked (fit.texture_prior does): tex, anchor
+    [Ht,Wt,C] and the maps [Ht,Wt] float32, contiguous, on one GPU; inv_c the float32 inverse of the Charbonnier scale, 0.0 for L2.
+    -> (value [] = w_smooth * part[0] + w_anchor * part[1], part [2] = (smoothness, anchor) / (Ht Wt), d value / d tex [Ht,Wt,C] for a
+    unit upstream or None).  acc: two float64 zeros on the device (None: a fresh buffer); the call leaves them zero again."""
+    Ht, Wt, C = tex.shape
+    with torch.cuda.device(tex.device):
+        if acc is None:
+            acc = torch.zeros(2, dtype=torch.float64, device=tex.device)
+        assert acc.dtype == torch.float64 and acc.numel() >= 2 and acc.is_contiguous() and acc.device == tex.device
+        part = torch.empty(2, dtype=torch.float32, device=tex.device)
+        out = torch.empty((), dtype=torch.float32, device=tex.device)
+        grad = torch.empty_like(tex) if want_grad else None
+        _lib.call("fpcdr_tex_prior", _ptr(tex), _ptr(anchor), _ptr(smooth_weights), _ptr(anchor_weights), float(inv_c), float(w_smooth),
+                  float(w_anchor), _ptr(grad), _ptr(acc), _ptr(part), _ptr(out), int(Ht), int(Wt), int(C), _stream())
+    return out, part, grad
+
+
 class _pixel_loss_func(torch.autograd.Function):
     """call = a *_loss_call with its keyword arguments bound, args = its positional arguments between colour and grad_scale: the mean over
     n_total of the call's first sum, and the gradient the same call computed, times the upstream scalar, as the backward."""

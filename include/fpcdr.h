@@ -450,6 +450,22 @@ int fpcdr_motion_penalty(const float *x, const int64_t *frame_t /* [F] or NULL *
                          void *acc /* F+1 doubles, zero in, zero out */, float *per, float *out, float weight, int32_t F, int32_t V,
                          void *stream);
 
+/* The texture's prior ("Texture prior rule"), value and gradient in one call (two launches): smoothness over the pairs of
+ * horizontally and vertically neighbouring texels -- none across the border -- and a hold to an anchor texture.
+ *   s_pq = || t_p - t_q ||^2 over the C channels,   rho(s) = s  (inv_c = 0: L2)   or   2 s / (1 + sqrt(1 + s / c^2)),  c = 1 / inv_c
+ *   part[0] = 1 / (Ht Wt) * sum_pairs min(smooth_w[p], smooth_w[q]) rho(s_pq),   part[1] = 1 / (Ht Wt) * sum_p anchor_w[p] || t_p - a_p ||^2
+ *   out[0] = w_smooth * part[0] + w_anchor * part[1]
+ *   grad_tex [Ht,Wt,C] = d out / d tex for a unit upstream (overwritten: every texel gathers its four neighbours, no float atomics,
+ *   bit-identical from run to run), or NULL: value only.
+ * tex, anchor [Ht,Wt,C] float32, C in 1..4; anchor NULL: no anchor term (part[1] = 0; anchor_w must then be NULL too).  smooth_w, anchor_w
+ * [Ht,Wt] float32, finite and >= 0, or NULL: 1.  A pair whose weight is 0 and a texel whose anchor weight is 0 contribute exactly 0 to
+ * value and gradient, whatever the texel holds.  A negative or non-finite inv_c or weight is an error.  acc: 2 * 8 bytes, 8-byte
+ * aligned, ZERO on entry; the call leaves it zero again.                                                                        */
+int fpcdr_tex_prior(const float *tex, const float *anchor /* or NULL */, const float *smooth_w /* [Ht,Wt] or NULL */,
+                    const float *anchor_w /* [Ht,Wt] or NULL */, float inv_c /* 0: L2 */, float w_smooth, float w_anchor,
+                    float *grad_tex /* [Ht,Wt,C] or NULL: value only */, void *acc /* 2 doubles, zero in, zero out */, float *part /* [2] */,
+                    float *out, int32_t Ht, int32_t Wt, int32_t C, void *stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* blend -- V = v_base + Bmat . w     reference fit.py:115-122 (prior), :58-62 (free)            */
 /* ------------------------------------------------------------------------------------------ */
