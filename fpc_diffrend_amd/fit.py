@@ -34,9 +34,9 @@ import torch
 
 from . import _lib, camera
 from . import ops as dr
-from .mesh_reg import (MeshTopology, RestShape, _uniform_laplacian, bend_penalty, hinge_incidence, hinge_rest_cs, hinge_vertices,
-                       laplacian_penalty, mesh_edge_loss, mesh_laplacian_smoothing, mesh_normal_consistency, motion_inv_scale,
-                       motion_penalty, rest_edge_lengths, stretch_penalty)
+from .mesh_reg import (MeshTopology, RestShape, _check_item_weights, _uniform_laplacian, bend_penalty, check_motion_options,
+                       hinge_incidence, hinge_rest_cs, hinge_vertices, laplacian_penalty, mesh_edge_loss, mesh_laplacian_smoothing,
+                       mesh_normal_consistency, motion_inv_scale, motion_penalty, rest_edge_lengths, stretch_penalty)
 from .ops import _ptr, _stream
 from .tex_prior import chart_map, check_tex_prior_options, load_texel_weights, tex_prior_inv_scale, texture_prior
 
@@ -291,7 +291,7 @@ def pixel_loss_robust(colour, rast_out, ref_u8, kind, scale, n_total=None, mask=
 
 def _load_weights(weights, n, option, item):
     """FitConfig.<option> -- an array-like [n] or the path of a text file with one number per <item> -- as a float32 array [n], or
-    ValueError: another length, an entry that is not finite or is negative."""
+    ValueError: another length, an entry that is not finite or is negative (mesh_reg._check_item_weights)."""
     if isinstance(weights, (str, os.PathLike)):
         try:
             w = np.loadtxt(weights, dtype=np.float64, ndmin=1)
@@ -299,11 +299,7 @@ def _load_weights(weights, n, option, item):
             raise ValueError(f"FitConfig.{option}: cannot read {weights}: {e}")
     else:
         w = np.asarray(weights, dtype=np.float64)
-    if w.ndim != 1 or w.shape[0] != n:
-        raise ValueError(f"FitConfig.{option} holds one number per {item}: expected [{n}], got shape {tuple(w.shape)}")
-    if not (np.isfinite(w).all() and (w >= 0).all()):
-        raise ValueError(f"FitConfig.{option} must be finite and not negative")
-    return w.astype(np.float32)
+    return _check_item_weights(w, (n,), option, item)
 
 
 def load_face_weights(face_weights, n_faces):
@@ -327,6 +323,29 @@ def motion_options(cfg, n_vertices, n_local):
                          f"(this one has {n_local}): the stencils end at the shard's borders")
     w = None if cfg.motion_vertex_weights is None else load_motion_vertex_weights(cfg.motion_vertex_weights, n_vertices)
     return motion_inv_scale(cfg.motion_scale), w
+
+
+class PriorTerm:
+    """One term a fit step evaluates in front of the pixel objective, stated once (the table of Fitter._build_prior_terms): the public
+    penalty fn(*args, *weights, **kw) with (args, kw) = inputs(vtx, ids) -- vtx [Fb,V,3] the step's meshes, ids their frame numbers (None:
+    consecutive, else the sorted int64 device tensor) -- and one log key per weight.  The Fitter evaluates it in two forms:
+      term(vtx, ids) -> scalar     the step's: weights / world (the gradients are summed over the ranks) and the keywords `step` of the
+                                   eager hand-over: the gradient is made with the value, d loss / d term = 1 exactly;
+      term.log(vtx, ids) -> dict   the log's: per key the value with that weight alone, at its full size (0.0 and no launch for a
+                                   weight of 0): a fresh accumulator, and no gradient under the caller's torch.no_grad()."""
+
+    def __init__(self, fn, inputs, weights, keys, world, **step):
+        self.fn, self.inputs, self.weights, self.keys, self.step = fn, inputs, tuple(weights), tuple(keys), step
+        self.shares = tuple(w / world for w in self.weights)
+
+    def __call__(self, vtx, ids):
+        args, kw = self.inputs(vtx, ids)
+        return self.fn(*args, *self.shares, **kw, **self.step)
+
+    def log(self, vtx, ids):
+        args, kw = self.inputs(vtx, ids)
+        alone = lambda j: (w if k == j else 0.0 for k, w in enumerate(self.weights))
+        return {key: float(self.fn(*args, *alone(j), **kw)) if self.weights[j] else 0.0 for j, key in enumerate(self.keys)}
 
 
 def pixel_term(cfg, i, weighted=False):
@@ -738,15 +757,7 @@ class FitConfig:
         if self.weights_configured() and (self.blur_sigma > 0 or self.norm_sigma > 0):
             raise ValueError("FitConfig: robust, face_weights, saturation > 0 and weight_outside != 1 cannot be combined with blur_sigma > 0 "
                              "or norm_sigma > 0: weighting the windowed losses is a different rule")
-        if isinstance(self.motion_order, bool) or self.motion_order not in (1, 2):
-            raise ValueError(f"FitConfig.motion_order must be 1 (velocity) or 2 (acceleration) (got {self.motion_order!r})")
-        try:
-            motion_inv_scale(self.motion_scale)
-        except ValueError as e:
-            raise ValueError(f"FitConfig.motion_scale: {e}")
-        if self.weight_motion and 0 < self.frames_per_step < self.motion_order + 1:
-            raise ValueError(f"FitConfig.weight_motion > 0 with motion_order={self.motion_order} needs frames_per_step = 0 or >= "
-                             f"{self.motion_order + 1} (got {self.frames_per_step}): fewer frames hold no stencil")
+        check_motion_options(self)
         check_tex_prior_options(self)
 
     def weights_configured(self):
@@ -899,39 +910,6 @@ class Fitter:
         self.rng = np.random.default_rng(cfg.seed + 1000 * rank)
         # final shapes (fit.py:457); every rank fills the rows of its own frames, gather_result() joins the shards
         self._result_full = torch.zeros(F, self.v_base.shape[0], dtype=torch.float32, device=dev)
-        # the base mesh as the rest shape of the regularisers that measure against it
-        self.rest = RestShape(self.topo, self.v_base) if (cfg.laplacian_relative or cfg.weight_stretch or cfg.weight_bend) else None
-        self._lap_rest = self.rest if cfg.laplacian_relative else None      # (the Laplacian term's: the plain one has no rest shape)
-        # the bending term's tables and the scratch of its corner gradients for the most frames a step takes: made here, before any capture
-        self._bnd_scratch = None
-        if cfg.weight_bend:
-            n_hinges = self.topo.hinges()[2]
-            assert self.rest.bend_cs.shape == (2, n_hinges)      # (built here, not in the first step)
-            self._bnd_scratch = torch.empty(max((self.frame_hi - self.frame_lo) * n_hinges * 12, 1), dtype=torch.float32, device=dev)
-        # The step's eager terms, (vtx [Fb,V,3], the step's frame numbers: None for the whole contiguous shard, else the sorted int64 device
-        # tensor) -> scalar, in the fixed order Laplacian, stretch, bend, motion.  Each makes its gradient with its value (it depends on the
-        # vertices only) and hands the buffer over in backward(); its weight carries the 1 / world, so that d loss / d term = 1 exactly.
-        # ONE accumulator buffer serves them all: the calls are ordered on the step's one stream, and each leaves the buffer zero (the
-        # finish kernel of csrc/mesh_reg.hip).
-        self._reg_acc = torch.zeros(self.frame_hi - self.frame_lo + 1, dtype=torch.float64, device=dev)
-        eager = dict(eager_grad=True, unit_upstream=True, acc=self._reg_acc)
-        self._reg_terms = []
-        if cfg.weight_laplacian and cfg.fused_loss:      # (two launches, ~25 us in front of the objective)
-            self._reg_terms.append(lambda vtx, ids: laplacian_penalty(vtx, self.topo, cfg.weight_laplacian / world, rest=self._lap_rest, **eager))
-        if cfg.weight_stretch:
-            self._reg_terms.append(lambda vtx, ids: stretch_penalty(vtx, self.topo, cfg.weight_stretch / world, rest=self.rest, **eager))
-        if cfg.weight_bend:
-            self._reg_terms.append(lambda vtx, ids: bend_penalty(vtx, self.topo, cfg.weight_bend / world, rest=self.rest,
-                                                                 scratch=self._bnd_scratch, **eager))
-        # the motion term couples the step's own meshes: this rank's frames only (its stencils end at the shard's borders), and of a random
-        # subset the frames adjacent in the take (the kernel reads the frame numbers on the device: pick_frames' are sorted and distinct)
-        self._motion_w = None
-        if cfg.weight_motion:
-            _, w = motion
-            self._motion_w = None if w is None else torch.from_numpy(w).to(dev)
-            self._reg_terms.append(lambda vtx, ids: motion_penalty(vtx, cfg.weight_motion / world, frame_ids=ids, order=cfg.motion_order,
-                                                                   scale=cfg.motion_scale, vertex_weights=self._motion_w, validate=False,
-                                                                   **eager))
         self._result_pending = None
         self.iteration = 0
         self._log_file, self._log_t, self._log_it = None, None, 0
@@ -975,21 +953,54 @@ class Fitter:
         baked = None
         if cfg.init_texture == 'bake':
             _, baked = self.bake_texture()
-        # ---- the texture's prior ("Texture prior rule"): its maps, and the anchor = the texture as it stands now.  Both
-        # weights 0: nothing is built, nothing is launched ----
-        self._tex_anchor, self._tex_anchor_w, self._tex_smooth_w, self._tex_chart = None, None, None, None
-        self._tex_prior_on = bool(cfg.weight_tex_smooth or cfg.weight_tex_anchor)
-        if self._tex_prior_on:
-            self._tex_smooth_w = self._texel_weights(cfg.tex_smooth_weights, 'tex_smooth_weights') if cfg.weight_tex_smooth else None
-            if cfg.weight_tex_anchor:
-                w = cfg.tex_anchor_weights
-                if w is None and baked is not None:      # only the texels a capture reached are worth holding
-                    w = baked.to(torch.float32)
-                self.set_texture_anchor(weights=w)
+        self._build_prior_terms(motion, baked)
         if self._levels is not None:
             self._set_level(self.pyramid_factor())
 
     # ------------------------------------------------------------------------------------------
+    def _build_prior_terms(self, motion, baked):
+        """self._reg_terms: the step's eager terms as one PriorTerm each, in the fixed order Laplacian, stretch, bend, motion, texture, and
+        what they need on the device (a weight of 0: nothing is built, allocated or launched).  motion, baked: __init__'s, or None."""
+        cfg, dev, n_local = self.cfg, self.device, self.frame_hi - self.frame_lo
+        # within a mesh: the base mesh is the rest shape of the terms that measure against it (the plain Laplacian has none)
+        self.rest = RestShape(self.topo, self.v_base) if (cfg.laplacian_relative or cfg.weight_stretch or cfg.weight_bend) else None
+        self._lap_rest = self.rest if cfg.laplacian_relative else None
+        self._bnd_scratch = None
+        if cfg.weight_bend:      # the hinge tables, and the scratch of the corner gradients for the most frames a step takes
+            n_hinges = self.topo.hinges()[2]
+            assert self.rest.bend_cs.shape == (2, n_hinges)      # (built here, not in the first step)
+            self._bnd_scratch = torch.empty(max(n_local * n_hinges * 12, 1), dtype=torch.float32, device=dev)
+        self._motion_w = torch.from_numpy(motion[1]).to(dev) if (cfg.weight_motion and motion[1] is not None) else None
+        # the texture's prior (DESIGN.md 3, "Texture prior rule"): its maps, and the anchor = the texture as it stands now
+        self._tex_anchor, self._tex_anchor_w, self._tex_smooth_w, self._tex_chart = None, None, None, None
+        self._tex_prior_on = bool(cfg.weight_tex_smooth or cfg.weight_tex_anchor)
+        if cfg.weight_tex_smooth:
+            self._tex_smooth_w = self._texel_weights(cfg.tex_smooth_weights, 'tex_smooth_weights')
+        if cfg.weight_tex_anchor:
+            w = cfg.tex_anchor_weights
+            if w is None and baked is not None:      # only the texels a capture reached are worth holding
+                w = baked.to(torch.float32)
+            self.set_texture_anchor(weights=w)
+        # ONE accumulator buffer serves every term: the calls are ordered on the step's one stream, and each leaves the buffer zero (the
+        # finish kernels of csrc/mesh_reg.hip and csrc/tex_prior.hip)
+        self._reg_acc = torch.zeros(n_local + 1, dtype=torch.float64, device=dev)
+        on_mesh = lambda rest: lambda vtx, ids: ((vtx, self.topo), dict(rest=rest))
+        # this rank's frames only (the stencils end at the shard's borders), and of a random subset the frames adjacent in the take (the
+        # kernel reads the frame numbers on the device: pick_frames' are sorted and distinct)
+        on_frames = lambda vtx, ids: ((vtx,), dict(frame_ids=ids, order=cfg.motion_order, scale=cfg.motion_scale,
+                                                   vertex_weights=self._motion_w, validate=False))
+        # once per step on the texture itself, whatever the level or mip (read at the call: set_texture_anchor may add the weights later)
+        on_texture = lambda vtx, ids: ((self.tex_opt,), dict(anchor=self._tex_anchor, smooth_weights=self._tex_smooth_w,
+                                                             anchor_weights=self._tex_anchor_w, scale=cfg.tex_smooth_scale, validate=False))
+        # (on, fn, inputs, weights, log keys, the step form's own keywords); LAP is logged by the torch form, fused_loss or not
+        table = [(cfg.weight_laplacian and cfg.fused_loss, laplacian_penalty, on_mesh(self._lap_rest), [cfg.weight_laplacian], [], {}),
+                 (cfg.weight_stretch, stretch_penalty, on_mesh(self.rest), [cfg.weight_stretch], ["STR"], {}),
+                 (cfg.weight_bend, bend_penalty, on_mesh(self.rest), [cfg.weight_bend], ["BND"], dict(scratch=self._bnd_scratch)),
+                 (cfg.weight_motion, motion_penalty, on_frames, [cfg.weight_motion], ["MOT"], {}),
+                 (self._tex_prior_on, texture_prior, on_texture, [cfg.weight_tex_smooth, cfg.weight_tex_anchor], ["TEXS", "TEXA"], {})]
+        self._reg_terms = [PriorTerm(fn, inputs, weights, keys, self.world, eager_grad=True, unit_upstream=True, acc=self._reg_acc, **step)
+                           for on, fn, inputs, weights, keys, step in table if on]
+
     def texture_chart(self):
         """fit.chart_map of this Fitter's UV mesh at its texture's resolution, float32 [Ht,Wt], built on the first call and kept."""
         if self._tex_chart is None:
@@ -1031,14 +1042,6 @@ class Fitter:
                 self._graphs, self._graph_key = None, None
             else:
                 self._tex_anchor_w.copy_(w)
-
-    def _tex_prior_term(self, **modes):
-        """The step's texture prior at the current texture.  The weights carry the 1 / world: the gradients are summed over the ranks and
-        the texture is replicated, so every rank adds the same share."""
-        cfg, world = self.cfg, self.world
-        return texture_prior(self.tex_opt, cfg.weight_tex_smooth / world, cfg.weight_tex_anchor / world, anchor=self._tex_anchor,
-                             smooth_weights=self._tex_smooth_w, anchor_weights=self._tex_anchor_w, scale=cfg.tex_smooth_scale,
-                             validate=False, **modes)
 
     # ------------------------------------------------------------------------------------------
     @staticmethod
@@ -1420,12 +1423,10 @@ class Fitter:
         chained = reg is not self._zero      # (some term above was added)
         if self.world > 1 and chained:
             reg = reg / self.world
-        # the eager terms (Laplacian, stretch, bend, motion: __init__), their gradients made here with their values; a slice of frames is
-        # consecutive (no frame numbers to hand over), an index tensor names them
+        # the eager terms (_build_prior_terms), their gradients made here with their values; a slice of frames is consecutive (no frame
+        # numbers to hand over), an index tensor names them
         step_ids = frame_ids if torch.is_tensor(frame_ids) else None
         terms = [reg_term(vtx_pos_split, step_ids) for reg_term in self._reg_terms]
-        if self._tex_prior_on:      # the texture's prior: once per step on the texture itself, whatever the level or mip
-            terms.append(self._tex_prior_term(eager_grad=True, unit_upstream=True, acc=self._reg_acc))
         self.optimizer.zero_grad(set_to_none=True)
         if one_shot:
             bg_sum = None
@@ -1602,18 +1603,10 @@ class Fitter:
                 rec = rec or {"it": i}
                 rec["MEL"] = float(cfg.weight_meshedge * mesh_edge_loss(v, self.topo, 0.1))
                 rec["LAP"] = float(cfg.weight_laplacian * (mesh_laplacian_smoothing(v, self.topo, per_mesh=True, rest=self._lap_rest) ** 2).mean())
-                rec["STR"] = float(stretch_penalty(v, self.topo, cfg.weight_stretch, rest=self.rest)) if cfg.weight_stretch else 0.0
-                rec["BND"] = float(bend_penalty(v, self.topo, cfg.weight_bend, rest=self.rest)) if cfg.weight_bend else 0.0
+                rec["STR"], rec["BND"] = 0.0, 0.0      # (always there; the later terms' keys only with the term on)
                 rec["MNC"] = float(cfg.weight_normalconsistency * mesh_normal_consistency(v, self.topo))
-                if cfg.weight_motion:      # (only with the term on: without it a record is what it was)
-                    rec["MOT"] = float(motion_penalty(v, cfg.weight_motion, frame_ids=frame_ids if torch.is_tensor(frame_ids) else None,
-                                                      order=cfg.motion_order, scale=cfg.motion_scale, vertex_weights=self._motion_w,
-                                                      validate=False))
-                if self._tex_prior_on:     # (likewise)
-                    _, part, _ = dr.tex_prior_call(self.tex_opt.detach(), cfg.weight_tex_smooth, cfg.weight_tex_anchor, self._tex_anchor,
-                                                   self._tex_smooth_w, self._tex_anchor_w, tex_prior_inv_scale(cfg.tex_smooth_scale),
-                                                   want_grad=False)
-                    rec["TEXS"], rec["TEXA"] = float(cfg.weight_tex_smooth * part[0]), float(cfg.weight_tex_anchor * part[1])
+                for reg_term in self._reg_terms:
+                    rec.update(reg_term.log(v, frame_ids if torch.is_tensor(frame_ids) else None))
         if rec is None:
             return
         line = json.dumps(rec)

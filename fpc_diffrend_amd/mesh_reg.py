@@ -154,8 +154,6 @@ def mesh_laplacian_smoothing(verts, topo, per_mesh=False, rest=None):
     return per if per_mesh else per.mean()
 
 
-
-
 class _penalty(torch.autograd.Function):
     """The host path the penalties share.  Each is one C-ABI call that ends in the finish kernel (csrc/mesh_reg.hip), and each can
     make its gradient for a unit upstream in forward() already (the terms depend on the vertices only)."""
@@ -290,8 +288,6 @@ class RestShape:
         return self._bend_cs
 
 
-
-
 class _stretch_penalty(_penalty):
     """weight * mean_f mean_edges (|e| - l)^2 with its gradient from ONE call (fpcdr_stretch_penalty): the kernel that walks a vertex's
     ring for the value has everything the gradient at that vertex needs, so the gradient for a unit upstream is always made in
@@ -322,8 +318,6 @@ def stretch_penalty(verts, topo, weight, rest=None, target=0.0, eager_grad=False
     else:
         rest_len, n_edges = rest.len, rest.n_edges
     return _stretch_penalty.apply(verts, topo.nbr32, rest_len, n_edges, target, weight, bool(eager_grad and unit_upstream), acc)
-
-
 
 
 class _bend_penalty(_penalty):
@@ -362,22 +356,50 @@ def bend_penalty(verts, topo, weight, rest=None, eager_grad=False, unit_upstream
                                bool(eager_grad and unit_upstream), acc, scratch)
 
 
-def motion_inv_scale(scale):
-    """1 / scale as the float32 the kernel is handed (fpcdr_motion_penalty's inv_c), 0.0 for None (L2); ValueError for a scale that is
-    not finite and positive, or whose inverse is not a finite positive float32."""
+def _inv_scale(scale, whose, refuse_bool=False):
+    """1 / scale as the float32 a kernel is handed as its Charbonnier inv_c, 0.0 for None (L2); ValueError ("<whose> scale ...") for a
+    scale that is not finite and positive (refuse_bool: or is a bool), or whose inverse is not a finite positive float32."""
     if scale is None:
         return 0.0
     try:
         c = float(scale)
     except (TypeError, ValueError):
-        raise ValueError(f"the motion term's scale must be a number (got {scale!r})")
-    if not (np.isfinite(c) and c > 0.0):
-        raise ValueError(f"the motion term's scale must be finite and positive (got {scale!r})")
+        raise ValueError(f"{whose} scale must be a number (got {scale!r})")
+    if (refuse_bool and isinstance(scale, bool)) or not (np.isfinite(c) and c > 0.0):
+        raise ValueError(f"{whose} scale must be finite and positive (got {scale!r})")
     with np.errstate(over='ignore'):
         inv = float(np.float32(1.0 / c))
     if not (np.isfinite(inv) and inv > 0.0):
-        raise ValueError(f"the motion term's scale {scale!r} has no finite positive inverse in float32")
+        raise ValueError(f"{whose} scale {scale!r} has no finite positive inverse in float32")
     return inv
+
+
+def _check_item_weights(w, shape, option, item):
+    """How every loader of a per-<item> weight option of FitConfig ends: w (float64) as a contiguous float32 array of `shape`, or ValueError."""
+    if w.shape != tuple(shape):
+        raise ValueError(f"FitConfig.{option} holds one number per {item}: expected [{','.join(map(str, shape))}], got shape {tuple(w.shape)}")
+    if not (np.isfinite(w).all() and (w >= 0).all()):
+        raise ValueError(f"FitConfig.{option} must be finite and not negative")
+    return np.ascontiguousarray(w.astype(np.float32))
+
+
+def motion_inv_scale(scale):
+    """fpcdr_motion_penalty's inv_c for a scale in the length units of the vertices (_inv_scale: 0.0 for None, or ValueError)."""
+    return _inv_scale(scale, "the motion term's")
+
+
+def check_motion_options(cfg):
+    """What FitConfig's motion fields ask of each other (FitConfig.__post_init__), or ValueError.  Needs no GPU; what needs the mesh and
+    the shard is fit.motion_options."""
+    if isinstance(cfg.motion_order, bool) or cfg.motion_order not in (1, 2):
+        raise ValueError(f"FitConfig.motion_order must be 1 (velocity) or 2 (acceleration) (got {cfg.motion_order!r})")
+    try:
+        motion_inv_scale(cfg.motion_scale)
+    except ValueError as e:
+        raise ValueError(f"FitConfig.motion_scale: {e}")
+    if cfg.weight_motion and 0 < cfg.frames_per_step < cfg.motion_order + 1:
+        raise ValueError(f"FitConfig.weight_motion > 0 with motion_order={cfg.motion_order} needs frames_per_step = 0 or >= "
+                         f"{cfg.motion_order + 1} (got {cfg.frames_per_step}): fewer frames hold no stencil")
 
 
 def _check_motion_order(order):

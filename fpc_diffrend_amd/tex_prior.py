@@ -9,25 +9,12 @@ import numpy as np
 import torch
 
 from . import ops as dr
-from .mesh_reg import _penalty
+from .mesh_reg import _check_item_weights, _inv_scale, _penalty
 
 
 def tex_prior_inv_scale(scale):
-    """1 / scale as the float32 the kernel is handed (fpcdr_tex_prior's inv_c), 0.0 for None (L2); ValueError for a scale that is not
-    finite and positive, or whose inverse is not a finite positive float32.  The scale is in texture units (0..1)."""
-    if scale is None:
-        return 0.0
-    try:
-        c = float(scale)
-    except (TypeError, ValueError):
-        raise ValueError(f"the texture prior's scale must be a number (got {scale!r})")
-    if isinstance(scale, bool) or not (np.isfinite(c) and c > 0.0):
-        raise ValueError(f"the texture prior's scale must be finite and positive (got {scale!r})")
-    with np.errstate(over='ignore'):
-        inv = float(np.float32(1.0 / c))
-    if not (np.isfinite(inv) and inv > 0.0):
-        raise ValueError(f"the texture prior's scale {scale!r} has no finite positive inverse in float32")
-    return inv
+    """fpcdr_tex_prior's inv_c for a scale in texture units, 0..1 (mesh_reg._inv_scale: 0.0 for None, or ValueError; a bool is refused)."""
+    return _inv_scale(scale, "the texture prior's", refuse_bool=True)
 
 
 def _check_weight(name, w):
@@ -112,11 +99,7 @@ def load_texel_weights(weights, Ht, Wt, option):
             w = np.asarray(weights, dtype=np.float64)
         except (TypeError, ValueError):
             raise ValueError(f"FitConfig.{option} must be an array-like [{Ht},{Wt}], the path of an 8-bit image, or 'chart'")
-    if w.shape != (Ht, Wt):
-        raise ValueError(f"FitConfig.{option} holds one number per texel: expected [{Ht},{Wt}], got shape {tuple(w.shape)}")
-    if not (np.isfinite(w).all() and (w >= 0).all()):
-        raise ValueError(f"FitConfig.{option} must be finite and not negative")
-    return np.ascontiguousarray(w.astype(np.float32))
+    return _check_item_weights(w, (Ht, Wt), option, 'texel')
 
 
 def dilate3(cover):

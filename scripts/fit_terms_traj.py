@@ -6,18 +6,25 @@ it lies in, one fresh process per run.
     python scripts/fit_terms_traj.py --planes OUT.pt
     python scripts/fit_terms_traj.py --compare-planes A.pt B.pt
     python scripts/fit_terms_traj.py --time
+    python scripts/fit_terms_traj.py --enqueue
 
 The first form runs a smoke-sized Fitter for N (20) steps and saves the per-step losses and the final parameters.  --config shape (the
 default): cfg1, 4 frames, cameras 0 and 3, seed 0, with laplacian_relative, weight_stretch and weight_bend on, eager or under the captured
 HIP graph.  --config default | unfused | blur | norm | robust: the pixel terms, on two frames of 64 x 64 and cameras 0 and 4 (robust: with
 masks and face weights); these also save the C-ABI calls of three steps by name and count (_lib.KernelTimer) and the device launches of
-one step (the torch profiler).  The second form prints the largest relative difference of the losses and of the parameters (L2) between A
+one step (the torch profiler).  --config priors: the step's five prior terms together (rest Laplacian, stretch, bend, motion of order 2,
+texture smoothness on the chart with a scale and a hold to an anchor, at the weights of tests/test_gpu_prior_terms.py) on four frames of
+cfg1 at 128 x 128, cameras 0 and 3, eager or with --graph; it saves the calls and launches as well, and the log records of the
+iterations 0 and 10.  The second form prints the largest relative difference of the losses and of the parameters (L2) between A
 and B, beside the largest among A and further runs of A's tree (--spread), and fails if B is further from A than those runs are from each
-other (the objective's float atomics make two runs of one tree differ) or if the recorded calls or launches differ.
+other (the objective's float atomics make two runs of one tree differ), if the recorded calls or launches differ, or if the log
+records differ in their keys or, by more than A's runs among themselves and 1e-6, in a value.
 
 --planes saves the sums and the gradient planes of fit.pixel_loss_fused / _blurred / _normalised / _robust at one small shape each, with
 and without n_total; --compare-planes holds the planes of B to torch.equal with A's and the float64 sums, which pass through atomics, to
-1e-12 relative.  --time prints the median step time of the unfused, blur, norm and robust configurations at cfg3's shape."""
+1e-12 relative.  --time prints the median step time of the unfused, blur, norm and robust configurations at cfg3's shape.  --enqueue
+prints the median host time to enqueue a step of the priors configuration at one image a step (frames_per_step 3, views_per_step 1), the
+launch-bound shape: 200 steps after 3, no synchronisation inside the loop."""
 import os
 import sys
 import time
@@ -25,6 +32,21 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PIXEL_CONFIGS = {'default': {}, 'unfused': dict(fused_objective=False), 'blur': dict(blur_sigma=3.0, blur_kernel_size=15),
                  'norm': dict(norm_sigma=3.0, norm_kernel_size=15), 'robust': dict(robust='charbonnier', robust_scale=10.0, weight_outside=0.25)}
+
+PRIORS = dict(laplacian_relative=True, weight_laplacian=1.0e8, weight_stretch=2.5e7, weight_bend=1.0e9, weight_motion=6.0e6, motion_order=2,
+              weight_tex_smooth=3.0e4, tex_smooth_scale=0.1, tex_smooth_weights='chart', weight_tex_anchor=1.0e5)
+
+
+def _priors_fitter(**kw):
+    """A Fitter with the five prior terms on (PRIORS) on four frames of cfg1, and an anchor that differs from the start texture."""
+    from fpc_diffrend_amd import fit, scene
+    sc = scene.cfg('cfg1', n_frames=4)
+    sc.q_gt[:] = (0.0, 0.0, 0.0, 1.0)
+    cfg = fit.FitConfig(cam_idxs=(0, 3), resolution=(128, 128), lr_base=5e-3, lr_t=5e-3, lr_q=1e-5, seed=0, **PRIORS, **kw)
+    ft = fit.Fitter(sc, cfg, device='cuda')
+    ft.init_near_truth(0.8)
+    ft.set_texture_anchor((ft.tex_opt.detach() * 0.9 + 0.03).contiguous())
+    return ft
 
 
 def _pixel_fitter(name, sc, **kw):
@@ -56,9 +78,13 @@ def run(out, config, graph, steps):
         ft = fit.Fitter(sc, cfg, device='cuda')
         ft.init_near_truth(0.8)
     else:
-        sc = scene.make_scene(resolution=(64, 64), n_frames=2)
-        kw = dict(max_iter=steps, cam_idxs=(0, 4), seed=0)
-        ft = _pixel_fitter(config, sc, **kw)
+        if config == 'priors':
+            make = lambda **kw: _priors_fitter(max_iter=steps, hip_graph=graph, **kw)
+        else:
+            sc = scene.make_scene(resolution=(64, 64), n_frames=2)
+            make = lambda **kw: _pixel_fitter(config, sc, max_iter=steps, cam_idxs=(0, 4), seed=0, **kw)
+        ft = make()
+        assert fit.Fitter.GRAPH_WARMUP == 3      # (--graph: the three timed steps are the eager ones in front of the capture)
         _lib.TIMER = _lib.KernelTimer()
         try:
             for _ in range(3):
@@ -66,13 +92,19 @@ def run(out, config, graph, steps):
             rec['calls'] = {k: n for k, (n, _) in _lib.TIMER.summary().items()}
         finally:
             _lib.TIMER = None
+        if graph:
+            ft.step()      # (the capture: the step profiled below is a replay)
         with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
             ft.step()
             torch.cuda.synchronize()
         rec['launches'] = sum(e.count for e in prof.key_averages() if e.device_type == torch.autograd.DeviceType.CUDA)
-        ft = _pixel_fitter(config, sc, **kw)
+        ft = make(**(dict(log_interval=10, reg_log_interval=10, log_path=out + ".log") if config == 'priors' else {}))
     losses = [float(ft.step()) for _ in range(steps)]
     torch.cuda.synchronize()
+    if config == 'priors':
+        import json
+        rec['log'] = [json.loads(line) for line in open(out + ".log")]
+        os.remove(out + ".log")
     torch.save(dict(rec, losses=losses, params=[p.detach().cpu() for p in ft.params]), out)
     print(f"{os.path.dirname(fit.__file__)}: config={config} graph={graph}, {steps} steps, loss {losses[0]:.6e} -> {losses[-1]:.6e}, "
           f"calls {rec.get('calls')}, launches of a step {rec.get('launches')} -> {out}")
@@ -102,6 +134,15 @@ def compare(a_path, b_path, spread_paths):
         line += f"; C-ABI calls of three steps {sum(a['calls'].values())} in {len(a['calls'])} names, launches of a step {a['launches']}: " + \
             ("the same" if same else f"DIFFERENT ({b.get('calls')}, {b.get('launches')})")
         ok = ok and same
+    if 'log' in a:
+        timing = ("frames_per_s",)
+        gap = lambda x, y: max((abs(r[k] - s[k]) / max(abs(r[k]), 1e-30) for r, s in zip(x['log'], y['log']) for k in r
+                                if k not in timing and not isinstance(r[k], list)), default=0.0)
+        keys = [list(r) for r in a['log']] == [list(r) for r in b['log']]
+        dv, sv = gap(a, b), max([gap(a, x) for x in runs[1:]] if spread_paths else [0.0])
+        line += f"; {len(a['log'])} log records, keys {'the same' if keys else 'DIFFERENT'} ({' '.join(a['log'][0])}), values differ by " \
+                f"{dv:.3e} (A's runs: {sv:.3e})"
+        ok = ok and keys and dv <= max(sv, 1e-6)
     print(line + ("" if ok else "   OUTSIDE"))
     return 0 if ok else 1
 
@@ -172,6 +213,25 @@ def step_times(steps=8):
         torch.cuda.empty_cache()
 
 
+def enqueue_time(steps=200):
+    """Milliseconds of host time to enqueue one step of the priors configuration at one image a step: the median over `steps` steps."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    from fpc_diffrend_amd import fit
+    ft = _priors_fitter(max_iter=80000, frames_per_step=3, views_per_step=1)
+    for _ in range(3):
+        ft.step()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(steps):
+        t0 = time.perf_counter()
+        ft.step()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    torch.cuda.synchronize()
+    print(f"ENQUEUE_MS priors {float(np.median(ts)):.4f}   (min {min(ts):.4f}, {steps} steps; {os.path.dirname(fit.__file__)})", flush=True)
+
+
 if __name__ == "__main__":
     arg = lambda name, default: sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
     if sys.argv[1] == "--compare":
@@ -182,5 +242,7 @@ if __name__ == "__main__":
         planes(sys.argv[2])
     elif sys.argv[1] == "--time":
         step_times()
+    elif sys.argv[1] == "--enqueue":
+        enqueue_time()
     else:
         run(sys.argv[1], arg("--config", "shape"), "--graph" in sys.argv, int(arg("--steps", "20")))

@@ -124,3 +124,57 @@ def comparison_pair(i, height=1600, width=1200):
     ref = ((y // 8) * 3 + (x // 16) * 5 + 7 * i) % 200
     img = (ref + ((y // 64 + x // 32 + i) % 9) * ((y // 32 + i) % 3) - ((x // 128 + 2 * i) % 5)).clip(0, 255)
     return img.astype(np.uint8), ref.astype(np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# a Fitter near the truth and the additive check of the terms in front of the pixel objective (tests/test_gpu_rest.py, _bend.py,
+# _motion.py, _tex_prior.py, _prior_terms.py)
+# ---------------------------------------------------------------------------------------------------------------------
+
+def fitter_near_truth(n_frames, rank=0, world=1, **kw):
+    """A Fitter on n_frames of cfg1 with the poses at identity, cameras (0, 3), the plain Laplacian off, at init_near_truth(0.8); kw
+    overrides any FitConfig field."""
+    from fpc_diffrend_amd import fit
+    sc = scene.cfg('cfg1', n_frames=n_frames)
+    sc.q_gt[:] = (0.0, 0.0, 0.0, 1.0)
+    base = dict(max_iter=100, cam_idxs=(0, 3), lr_base=5e-3, lr_t=5e-3, lr_q=1e-5, weight_laplacian=0.0)
+    base.update(kw)
+    ft = fit.Fitter(sc, fit.FitConfig(**base), device='cuda', rank=rank, world=world)
+    ft.init_near_truth(0.8)
+    return ft
+
+
+def fitter_grads(ft):
+    """The gradient of every parameter tensor of a Fitter as a flat float64 vector (zeros where there is none)."""
+    return [(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).double() for p in ft.params]
+
+
+def flat_grads(ft):
+    return torch.cat(fitter_grads(ft))
+
+
+def additive(log, tag, ft_on, ft_off, frames, term_of, sized=True):
+    """g_on - g_off = g_term per parameter tensor, and the same for the loss values; -> (l_term, |g_term|).  term_of(v): the terms that
+    ft_on runs and ft_off does not, from direct calls on ft_on's vertices v [Fb,V,3] (and on its other parameters, where a term reads
+    them).  log: the tag of the printed line."""
+    l_on, l_off = float(ft_on.loss_and_backward(frames)), float(ft_off.loss_and_backward(frames))
+    assert bool((ft_on._reg_acc == 0).all())
+    g_on, g_off = fitter_grads(ft_on), fitter_grads(ft_off)
+    ft_on.optimizer.zero_grad(set_to_none=True)
+    Fb = ft_on._n(frames)
+    term = term_of(ft_on.vertices(frames).reshape(Fb, -1, 3))
+    term.backward()
+    g_term, l_term = fitter_grads(ft_on), float(term.detach())
+    cat = lambda g: torch.cat(g)
+    n_on, n_off, n_term = float(cat(g_on).norm()), float(cat(g_off).norm()), float(cat(g_term).norm())
+    worst = 0.0
+    for k, (a, b, t) in enumerate(zip(g_on, g_off, g_term)):
+        err, bar = float(((a - b) - t).norm()), 1e-4 * (float(a.norm()) + float(b.norm()))
+        worst = max(worst, err / bar if bar > 0 else (0.0 if err == 0 else float('inf')))
+        assert err <= bar, (tag, k, err, bar)
+    print(f"{log} fitter/{tag} |g_on|={n_on:.4e} |g_off|={n_off:.4e} |g_term|={n_term:.4e} worst err/bar={worst:.3e} "
+          f"l_on={l_on:.6e} l_off={l_off:.6e} l_term={l_term:.6e}")
+    if sized:
+        assert 0.1 * n_off <= n_term <= 10.0 * n_off, (tag, n_term, n_off)
+    assert abs((l_on - l_off) - l_term) <= 1e-4 * (abs(l_on) + abs(l_off))
+    return l_term, n_term

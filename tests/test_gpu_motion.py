@@ -56,6 +56,7 @@ import torch
 
 import fitstep_ref as R
 import motion_ref as M
+from helpers import additive, fitter_near_truth
 
 pytestmark = pytest.mark.gpu
 
@@ -262,43 +263,10 @@ W_FREE, NOISE = 1.0e4, 0.02      # the behaviour test: the weight, and the size 
 
 
 def _fitter(n_frames=5, rank=0, world=1, **kw):
-    from fpc_diffrend_amd import fit, scene
-    sc = scene.cfg('cfg1', n_frames=n_frames)
-    sc.q_gt[:] = (0.0, 0.0, 0.0, 1.0)
-    base = dict(max_iter=100, cam_idxs=(0, 3), lr_base=5e-3, lr_t=5e-3, lr_q=1e-5, weight_laplacian=0.0, optimize_texture=False)
-    base.update(kw)
-    ft = fit.Fitter(sc, fit.FitConfig(**base), device='cuda', rank=rank, world=world)
-    ft.init_near_truth(0.8)
-    return ft
+    return fitter_near_truth(n_frames, rank, world, **{'optimize_texture': False, **kw})
 
 
-def _grads(ft):
-    return [(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).double() for p in ft.params]
-
-
-def _additive(tag, ft_on, ft_off, frames, term_of, sized=True):
-    """g_on - g_off = g_term per parameter tensor, and the same for the loss values; -> (l_term, |g_term|)."""
-    l_on, l_off = float(ft_on.loss_and_backward(frames)), float(ft_off.loss_and_backward(frames))
-    assert bool((ft_on._reg_acc == 0).all())
-    g_on, g_off = _grads(ft_on), _grads(ft_off)
-    ft_on.optimizer.zero_grad(set_to_none=True)
-    Fb = ft_on._n(frames)
-    term = term_of(ft_on.vertices(frames).reshape(Fb, -1, 3))
-    term.backward()
-    g_term, l_term = _grads(ft_on), float(term.detach())
-    cat = lambda g: torch.cat(g)
-    n_on, n_off, n_term = float(cat(g_on).norm()), float(cat(g_off).norm()), float(cat(g_term).norm())
-    worst = 0.0
-    for k, (a, b, t) in enumerate(zip(g_on, g_off, g_term)):
-        err, bar = float(((a - b) - t).norm()), 1e-4 * (float(a.norm()) + float(b.norm()))
-        worst = max(worst, err / bar if bar > 0 else (0.0 if err == 0 else float('inf')))
-        assert err <= bar, (tag, k, err, bar)
-    print(f"MOTION fitter/{tag} |g_on|={n_on:.4e} |g_off|={n_off:.4e} |g_term|={n_term:.4e} worst err/bar={worst:.3e} "
-          f"l_on={l_on:.6e} l_off={l_off:.6e} l_term={l_term:.6e}")
-    if sized:
-        assert 0.1 * n_off <= n_term <= 10.0 * n_off, (tag, n_term, n_off)
-    assert abs((l_on - l_off) - l_term) <= 1e-4 * (abs(l_on) + abs(l_off))
-    return l_term, n_term
+_additive = functools.partial(additive, "MOTION")
 
 
 @pytest.mark.parametrize("path", ['one_pass', 'torch'])

@@ -56,6 +56,7 @@ import torch
 
 import fitstep_ref as R
 import rest_ref as S
+from helpers import fitter_near_truth, flat_grads as _flat_grads
 
 pytestmark = pytest.mark.gpu
 
@@ -280,18 +281,7 @@ W_LAP, W_STR = 1.0e8, 2.5e7
 
 
 def _fitter(**kw):
-    from fpc_diffrend_amd import fit, scene
-    sc = scene.cfg('cfg1', n_frames=4)
-    sc.q_gt[:] = (0.0, 0.0, 0.0, 1.0)
-    base = dict(max_iter=100, cam_idxs=(0, 3), lr_base=5e-3, lr_t=5e-3, lr_q=1e-5, weight_laplacian=0.0, optimize_texture=False)
-    base.update(kw)
-    ft = fit.Fitter(sc, fit.FitConfig(**base), device='cuda')
-    ft.init_near_truth(0.8)
-    return ft
-
-
-def _flat_grads(ft):
-    return torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).double() for p in ft.params])
+    return fitter_near_truth(4, **{'optimize_texture': False, **kw})
 
 
 @pytest.mark.parametrize("terms", ['lap', 'stretch', 'both'])

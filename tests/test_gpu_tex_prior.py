@@ -54,6 +54,7 @@ import torch
 
 import fitstep_ref as R
 import tex_prior_ref as T
+from helpers import additive, fitter_grads, fitter_near_truth
 
 pytestmark = pytest.mark.gpu
 
@@ -305,14 +306,7 @@ W_GRAPH_S, W_GRAPH_A = 1.0e3, 1.0e3      # the captured steps: the term is of th
 
 
 def _fitter(n_frames=3, rank=0, world=1, **kw):
-    from fpc_diffrend_amd import fit, scene
-    sc = scene.cfg('cfg1', n_frames=n_frames)
-    sc.q_gt[:] = (0.0, 0.0, 0.0, 1.0)
-    base = dict(max_iter=100, cam_idxs=(0, 3), resolution=(128, 128), lr_base=5e-3, lr_t=5e-3, lr_q=1e-5, weight_laplacian=0.0)
-    base.update(kw)
-    ft = fit.Fitter(sc, fit.FitConfig(**base), device='cuda', rank=rank, world=world)
-    ft.init_near_truth(0.8)
-    return ft
+    return fitter_near_truth(n_frames, rank, world, **{'resolution': (128, 128), **kw})
 
 
 def _anchor_of(ft):
@@ -321,35 +315,17 @@ def _anchor_of(ft):
     return (ft.tex_opt.detach() * 0.9 + 0.03).contiguous(), _map(Ht, Wt, 77)
 
 
-def _grads(ft):
-    return [(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).double() for p in ft.params]
-
-
 def _additive(tag, ft_on, ft_off, frames, world=1):
     """tex_opt.grad = g_off + g_term within 1e-4 (|g_on| + |g_off|), every other parameter's gradient the control's, the loss likewise."""
     from fpc_diffrend_amd import fit
     cfg = ft_on.cfg
-    l_on, l_off = float(ft_on.loss_and_backward(frames)), float(ft_off.loss_and_backward(frames))
-    assert bool((ft_on._reg_acc == 0).all())
-    g_on, g_off = _grads(ft_on), _grads(ft_off)
-    leaf = ft_on.tex_opt.detach().clone().requires_grad_(True)
-    term = fit.texture_prior(leaf, cfg.weight_tex_smooth / world, cfg.weight_tex_anchor / world, anchor=ft_on._tex_anchor,
-                             smooth_weights=ft_on._tex_smooth_w, anchor_weights=ft_on._tex_anchor_w, scale=cfg.tex_smooth_scale)
-    term.backward()
-    g_term, l_term = leaf.grad.reshape(-1).double(), float(term.detach())
     tex = len(ft_on.params) - 1
     assert ft_on.params[tex] is ft_on.tex_opt
-    worst = 0.0
-    for k, (a, b) in enumerate(zip(g_on, g_off)):
-        t = g_term if k == tex else torch.zeros_like(a)
-        err, bar = float(((a - b) - t).norm()), 1e-4 * (float(a.norm()) + float(b.norm()))
-        worst = max(worst, err / bar if bar > 0 else (0.0 if err == 0 else float('inf')))
-        assert err <= bar, (tag, k, err, bar)
-    n_on, n_off, n_term = float(g_on[tex].norm()), float(g_off[tex].norm()), float(g_term.norm())
-    print(f"TEXPRIOR fitter/{tag} tex |g_on|={n_on:.4e} |g_off|={n_off:.4e} |g_term|={n_term:.4e} worst err/bar={worst:.3e} "
-          f"l_on={l_on:.6e} l_off={l_off:.6e} l_term={l_term:.6e}")
+    l_term, n_term = additive("TEXPRIOR", tag, ft_on, ft_off, frames, lambda v: fit.texture_prior(
+        ft_on.tex_opt, cfg.weight_tex_smooth / world, cfg.weight_tex_anchor / world, anchor=ft_on._tex_anchor,
+        smooth_weights=ft_on._tex_smooth_w, anchor_weights=ft_on._tex_anchor_w, scale=cfg.tex_smooth_scale), sized=False)
+    n_off = float(fitter_grads(ft_off)[tex].norm())      # (the term reaches the texture alone: n_term is its texture gradient's)
     assert n_term >= 1e-2 * n_off > 0.0, (tag, n_term, n_off)
-    assert abs((l_on - l_off) - l_term) <= 1e-4 * (abs(l_on) + abs(l_off))
     return l_term
 
 
