@@ -467,7 +467,8 @@ extern "C" int fpcdr_antialias_bwd(const fpcdr_antialias_bwd_params *p, void *st
         const size_t n4 = nfl / 4;
         const size_t g = (n4 + (size_t)COPY_U * 256 - 1) / ((size_t)COPY_U * 256);
         FPCDR_REQUIRE(g <= 0x7fffffffull, "tensor too large for one launch");
-        hipLaunchKernelGGL(k_copy_f4_chunk, dim3((unsigned)g), dim3(256), 0, st, (const v4f *)p->dy, (v4f *)p->grad_color, n4);
+        if (g)      // (fewer than four floats: no float4 piece, and a grid of 0 workgroups is an invalid launch)
+            hipLaunchKernelGGL(k_copy_f4_chunk, dim3((unsigned)g), dim3(256), 0, st, (const v4f *)p->dy, (v4f *)p->grad_color, n4);
         if (nfl & 3)
             (void)hipMemcpyAsync(p->grad_color + n4 * 4, p->dy + n4 * 4, (nfl & 3) * sizeof(float), hipMemcpyDeviceToDevice, st);
     } else if (hipMemcpyAsync(p->grad_color, p->dy, nfl * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
