@@ -1,0 +1,934 @@
+"""float64 restatement on the CPU of the one-pass pixel objective (csrc/objective.hip: k_shade_list, k_fix<0>, k_fix<1>,
+k_objective_finish; the non-mip call, C in 1, 3, 4, the three boundary modes), value and both gradients, without autograd: the
+yardstick of tests/test_gpu_objective_ref.py, itself checked on the CPU by tests/test_objective_ref.py.  Nothing here imports
+fpc_diffrend_amd; the triangle ids come from the function handed to case_inputs (oracle.ops), as in rasterize_ref.case_inputs.
+
+The call fuses rasterize -> interpolate -> texture 'linear' -> antialias -> where(covered, ., background) -> mean squared error against
+an 8-bit reference.  It is restated the way the kernels decompose it, with every value a rasterize_ref.Q (value and first-order
+rounding scale S, carried from the float32 inputs down by the rules of rasterize_ref.py's docstring), so that one text gives the
+float64 reference, "the same formula in float32 by torch" (dtype=float32: e32) and the per-entry scale:
+    k_shade, every covered pixel   (u, v, z/w) = shade_uvz (rasterize_ref._Pixels); w = 1 - u - v, tu = u q0 + v q1 + w q2;
+                                   x = prep(tu) Wt - 0.5, x0 = floor x, fx = x - x0 (_Lookup: make_taps / make_taps_fast);
+                                   col = top + (bot - top) fy, top = t00 + (t10 - t00) fx; dd = rf - col cs, d0 = rf - bg cs;
+                                   value += dd^2 - d0^2; gq = (-2 cs gs) dd; g_tex[tap k] += gq w_k, w_00 = (1 - fx)(1 - fy), ...;
+                                   gtu = (sum_c gq dcol/dfx) Wt mu, (gu, gv) through q0 - q2, q1 - q2, then shade_uv_bwd (_uv_bwd)
+    k_fix<0>, a blended pixel r    acc = col_r + sum over its active (pair, edge) entries of amt (col_o - col_r), col of an empty
+                                   pixel = the texture at uv = (0, 0); dn = rf - acc cs; value += (dn^2 - d0^2) - (dd^2 - d0^2);
+                                   g_aa[r] = (-2 cs gs) dn replaces gq
+    k_fix<1>, pixel X of a blend   go = g_aa[X] - sum_{r = X} amt g_aa[r] + sum_{o = X, r covered} amt g_aa[r];
+                                   the DIFFERENCE dl = go - gq chained like gq above (shade_pixel_bwd<false> is _uv_bwd again);
+                                   d alpha / d pos once per entry with a covered receiver (antialias_ref._pos_terms, boost 1);
+                                   esum = sum_{r covered, o empty} amt g_aa[r], scattered by k_objective_finish with the four
+                                   weights of uv = (0, 0)
+    value                          (the float sums above + C * sum over ALL pixels of (rf - b)^2) / n_total
+An entry of g_pos or g_tex is the sum of its terms as the kernels form them and its S the sum of their scales: the plain term and
+the difference term of a blended pixel each keep their own (S(dl) = S(go) + S(gq)), so their cancellation never shrinks S.  The
+texture coordinate's scale enters through fx and fy, which carry it (texture_ref.py: coordinate-aware).  The colours and g_aa that
+antialias_ref._pos_terms is handed count as inputs there (S = |value|): the d alpha / d pos terms have the scale antialias_ref gives
+them, which is smaller than one carried through the lookup -- a stricter yardstick, the same for e32 and the GPU.
+The value's scale is  [ sum over its terms of (S carried to the term + |dd^2| + |d0^2|) + C * bg_sumsq's ] / n_total: the first part
+bounds what the per-pixel operations lose, the second what the float accumulations lose; N_VALUE below counts both.
+
+Every discrete choice is made in float32, one rounded operation each, in the kernels' order (choices()): the clamp and renormalise
+gates of the barycentrics, floor(tu) under 'wrap', tu < 0 and tu > 1 under 'clamp' (the clamp itself and the masks mu, mv), the tap
+cells floor(prep(t) n - 0.5) and with them zero-mode validity, and through antialias_ref.decisions on the float32 z/w that k_shade
+stores the silhouette bits, pair_select, the active edges and t >= 1/2.  Which pixels are deferred (pair_maybe on ids and silhouette
+bits) and which are hit follow in integers.  reference() evaluates ON those choices and asserts that the gates rasterize_ref makes
+in its own dtype agree.  margins() gives, per covered pixel and per candidate pair, how far every one of them is from flipping, in
+units of u of its own scale; the constructions move a triangle and its uv until none is within SETTLE_MARGIN (no pixel left out).
+
+float32_in_kernel_order() is reference(dtype=float32) per pixel -- the text above is written in the kernels' operation order -- and
+names the texels that hold exactly ONE term, from a pixel outside every blend: there g_tex must equal gq * w_k bit for bit (one
+addend through the window's double, the float cast and an atomic onto 0 is exact).  plan() restates in integers how k_shade places
+its texel windows and which tables overflow; predicted_zeros() names the entries without a term."""
+import functools
+import math
+
+import numpy as np
+import torch
+
+import antialias_ref as AR
+import rasterize_ref as RR
+import texture_ref as TR
+from fitstep_ref import BACKGROUND, U, bg_sumsq, measure, rel_l2      # noqa: F401  (re-exported)
+from rasterize_ref import GATE_MARGIN, SETTLE_MARGIN, Q, _clip, _inp, _where
+
+MUTANT = None          # set by test_objective_ref.py only: a deliberately wrong restatement (see there)
+
+BIN = 32               # OB
+OWIN_CELLS = {1: 1216, 3: 1600, 4: 1600}      # owin_cells<CS>()
+VT_SLOTS, FVS, FTS, ESLOTS = 256, 64, 128, 32
+CS_SCALE = 255.0       # color_scale
+PASS0_ROWS = (0, 1, 4, 5, 10, 11, 14, 15)     # rows of a half that its first pass shades: row pairs 0, 2, 5, 7 (0x7520)
+OUTPUTS = ('g_tex', 'g_pos')
+
+# Rounded operations on the longest path into the value, in units of the scale above (S carried like the error: a path of n operations
+# loses at most (n + 1) u of S to first order).  p = x - fx w 2, a0 4, at 6, iw 7, b0 8, the renormalising sum and quotient 10, u 11;
+# w = 1 - u - v 13, its product 14, the two adds of tu 16; prep 17, * Wt 18, - 0.5 19, fx 20; (t10 - t00) fx + t00: 22; bot - top 23,
+# * fy 24, + top 25; * cs 26, rf - . 27; dd^2 28, - d0^2 29.  A blended pixel adds: col_o - col_r 26, * amt 27, the quad's two DPP adds
+# 29, + col_r 30, dn 32, dn^2 33, - d0^2 34, and the subtraction of the plain term 35.
+# Then the float accumulations of a lane -- k_shade: four pixels of C channels, 4 C; k_fix<0>: two per channel and trip, a trip per 16
+# deferred pixels of the bin --, the six DPP steps of wave_sum_dpp, and the float cast of the quotient.  The four wave sums of a bin,
+# the slots, the background share and the division are double.
+N_VALUE_PIXEL, N_VALUE_BLEND = 29, 35
+
+
+# The bar is (n_value + 2) u of S, as in fitstep_ref.py: n_value + 1 is the first-order bound of a path of n_value operations, and one more u
+# stands for the second-order terms (n^2 u^2, far below u at these counts).  It is a worst-case count against a scale summed over thousands
+# of pixels, so measured errors are a hundredth of a u: this bar sees a wrong term, a wrong factor or a lost pixel, not a lost bit.
+def n_value(C, max_deferred_in_a_bin):
+    trips = -(-4 * max_deferred_in_a_bin // 64)
+    return max(N_VALUE_PIXEL + 4 * C, N_VALUE_BLEND + 2 * C * trips) + 6 + 1
+
+
+def _coef(x):
+    return Q(x, torch.zeros_like(x))
+
+
+def _at(q, idx):
+    return Q(q.v[idx], q.S[idx])
+
+
+def _zeros(n, dtype):
+    return Q(torch.zeros(n, dtype=dtype), torch.zeros(n, dtype=dtype))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the texture lookup (behind one class: the mip branch can be stated on the same skeleton)
+# ---------------------------------------------------------------------------------------------------------------------
+
+class _Lookup:
+    """make_taps / make_taps_fast + load_taps + mask_taps for n pixels at (tu, tv) (Q) in tex [Ht,Wt,C].  ch: the float32 choices
+    (a dict this fills when it is empty, and follows otherwise).  Taps k = 0..3 are (00, 10, 01, 11)."""
+
+    def __init__(self, tex, tu, tv, boundary, dtype, ch):
+        Ht, Wt, C = tex.shape
+        make = len(ch) == 0
+        self.gates = []      # Q whose value must stay positive for the choice to hold
+
+        def coord(t, n, key):
+            one = torch.ones_like(t.v)
+            if boundary == 'wrap':
+                if make:
+                    ch[key + 'fl'] = torch.floor(t.v)
+                fl = ch[key + 'fl'].to(dtype)
+                p = Q(t.v - fl, t.S + fl.abs())
+                self.gates += [p, Q(fl + 1.0 - t.v, p.S)]
+            elif boundary == 'clamp':
+                if make:
+                    ch[key + 'lo'], ch[key + 'hi'] = t.v < 0, t.v > 1
+                lo, hi = ch[key + 'lo'], ch[key + 'hi']
+                p = _where(lo, _coef(torch.zeros_like(one)), _where(hi, Q(one, one), t))
+                self.gates += [Q(torch.where(lo, -t.v, t.v), t.S), Q(torch.where(hi, t.v - 1.0, 1.0 - t.v), t.S + 1.0)]
+            else:
+                p = t
+            x = Q(p.v * float(n) - 0.5, p.S * float(n) + 0.5)
+            if make:
+                ch[key + 'x0'] = torch.floor(x.v)
+            x0f = ch[key + 'x0'].to(dtype)
+            f = Q(x.v - x0f, x.S)
+            self.gates += [f, Q(x0f + 1.0 - x.v, x.S)]
+            inside = ~(ch[key + 'lo'] | ch[key + 'hi']) if boundary == 'clamp' else torch.ones_like(t.v, dtype=torch.bool)
+            return f, ch[key + 'x0'].long(), inside
+
+        self.fx, self.x0, in_u = coord(tu, Wt, 'u')
+        self.fy, self.y0, in_v = coord(tv, Ht, 'v')
+        self.mu, self.mv = in_u.to(dtype), in_v.to(dtype)
+        ix = (TR._idx(self.x0, Wt, boundary), TR._idx(self.x0 + 1, Wt, boundary))
+        iy = (TR._idx(self.y0, Ht, boundary), TR._idx(self.y0 + 1, Ht, boundary))
+        vx = (TR._inside(self.x0, Wt, boundary), TR._inside(self.x0 + 1, Wt, boundary))
+        vy = (TR._inside(self.y0, Ht, boundary), TR._inside(self.y0 + 1, Ht, boundary))
+        t = tex.detach().to('cpu', dtype)
+        self.flat, self.valid, self.t = [], [], []
+        for k in range(4):
+            jx, jy = k & 1, k >> 1
+            ok = vx[jx] & vy[jy]
+            self.flat.append(iy[jy] * Wt + ix[jx])
+            self.valid.append(ok)
+            m = ok.to(dtype)
+            self.t.append([Q(t[iy[jy], ix[jx], c] * m, t[iy[jy], ix[jx], c].abs() * m) for c in range(C)])
+        fx, fy = self.fx, self.fy
+        self.col = []
+        for c in range(C):
+            t00, t10, t01, t11 = (self.t[k][c] for k in range(4))
+            top = t00 + (t10 - t00) * fx
+            bot = t01 + (t11 - t01) * fx
+            self.col.append(top + (bot - top) * fy)
+        self.wk = [(1.0 - fx) * (1.0 - fy), fx * (1.0 - fy), (1.0 - fx) * fy, fx * fy]
+        self.Ht, self.Wt, self.C = Ht, Wt, C
+
+    def backward(self, g):
+        """g: C Q [n] = d loss / d colour -> (gtu, gtv): d loss / d (tu, tv), masked by mu, mv."""
+        fx, fy = self.fx, self.fy
+        gfx = gfy = _zeros(fx.v.numel(), fx.v.dtype)
+        for c in range(self.C):
+            t00, t10, t01, t11 = (self.t[k][c] for k in range(4))
+            gfx = gfx + g[c] * ((t10 - t00) * (1.0 - fy) + (t11 - t01) * fy)
+            gfy = gfy + g[c] * ((t01 + (t11 - t01) * fx) - (t00 + (t10 - t00) * fx))
+        return gfx * float(self.Wt) * self.mu, gfy * float(self.Ht) * self.mv
+
+    def scatter(self, G, GS, g, rows):
+        """g_tex[tap k] += g_c * w_k for the pixels `rows`, at the taps that exist."""
+        for k in range(4):
+            ok = self.valid[k][rows]
+            if MUTANT == 'zero_padding_gets_gradient':
+                ok = torch.ones_like(ok)
+            for c in range(self.C):
+                term = _at(g[c], rows) * _at(self.wk[k], rows)
+                idx = self.flat[k][rows][ok] * self.C + c
+                G.index_add_(0, idx, term.v[ok])
+                GS.index_add_(0, idx, term.S[ok])
+
+
+def _uv_bwd(px, gu, gv):
+    """shade_uv_bwd on the kept values of px (= shade_pixel_bwd<false>, which recomputes the same operations): (gu, gv) Q [n] -> the
+    nine components (vertex 0: x, y, w; vertex 1; vertex 2)."""
+    p0x, p0y, p1x, p1y, p2x, p2y = px.p
+    fx, fy, a0, a1, iw, b0, b1, uc, vc = px.fx, px.fy, px.a0, px.a1, px.iw, px.b0, px.b1, px.uc, px.vc
+    s = 1.0 / px.sum
+    dot = (uc * gu + vc * gv) * s * s
+    guc, gvc = _where(px.ren, gu * s - dot, gu), _where(px.ren, gv * s - dot, gv)
+    open0, open1 = (b0.v >= 0.0) & (b0.v <= 1.0), (b1.v >= 0.0) & (b1.v <= 1.0)
+    gb0, gb1 = _where(open0, guc, 0.0), _where(open1, gvc, 0.0)
+    zero = _zeros(px.n, px.dtype)
+    ga0, ga1 = gb0 * iw, gb1 * iw
+    giw = gb0 * a0 + gb1 * a1
+    gat = -giw * iw * iw
+    ga0, ga1, ga2 = ga0 + gat, ga1 + gat, gat
+    gp1x = ga0 * p2y; gp2y = ga0 * p1x; gp1y = zero - ga0 * p2x; gp2x = zero - ga0 * p1y
+    gp2x = gp2x + ga1 * p0y; gp0y = ga1 * p2x; gp2y = gp2y - ga1 * p0x; gp0x = zero - ga1 * p2y
+    gp0x = gp0x + ga2 * p1y; gp1y = gp1y + ga2 * p0x; gp0y = gp0y - ga2 * p1x; gp1x = gp1x - ga2 * p0y
+    return [gp0x, gp0y, zero - fx * gp0x - fy * gp0y, gp1x, gp1y, zero - fx * gp1x - fy * gp1y, gp2x, gp2y, zero - fx * gp2x - fy * gp2y]
+
+
+def _edge_pos_terms(D, E, colP, gaa, dtype):
+    """aa_edge_pos_grad for every active (pair, edge) entry, G = sum_c g_aa[receiver]_c (col[P]_c - col[Q]_c) on the colours and gradients
+    of THIS call (Q per channel over all pixels; g_aa of an empty pixel is 0: such an entry has no term) -> (rows of va, rows of vb,
+    [x, y, w] of a, of b, keep: the entries not left at G == 0).  antialias_ref._pos_terms is this with colour and dy as inputs."""
+    pr, i, e = D.pairs, D.ei, D.ee
+    hw, hh = 0.5 * D.W, 0.5 * D.H
+    G = _zeros(i.numel(), dtype)
+    for c in range(len(colP)):
+        G = G + _at(gaa[c], D.er) * (_at(colP[c], pr.pP[i]) - _at(colP[c], pr.pQ[i]))
+    pick = lambda k: Q(E[k].v[i, e], E[k].S[i, e])
+    t, Ld = pick('t'), pick('Ld')
+    s = Q(E['s'].v[i], E['s'].S[i])
+    qax, qay, wa, qbx, qby, wb = (pick(k) for k in ('qax', 'qay', 'wa', 'qbx', 'qby', 'wb'))
+    gLz = (-G) / (s * Ld)
+    gLd = ((-G) * t) / Ld
+    is_x = pr.d[i] == 0
+    zero = _zeros(i.numel(), dtype)
+    gLx, gLy = _where(is_x, gLd, zero), _where(is_x, zero, gLd)
+    g_qay = zero + gLx * wb; g_wb = zero + gLx * qay; g_wa = zero - gLx * qby; g_qby = zero - gLx * wa
+    g_wa = g_wa + gLy * qbx; g_qbx = zero + gLy * wa; g_qax = zero - gLy * wb; g_wb = g_wb - gLy * qax
+    g_qax = g_qax + gLz * qby; g_qby = g_qby + gLz * qax; g_qay = g_qay - gLz * qbx; g_qbx = g_qbx - gLz * qay
+    fxp, fyp = _coef(pr.Px[i].to(dtype) + 0.5 - hw), _coef(pr.Py[i].to(dtype) + 0.5 - hh)
+    if MUTANT == 'w_column_with_fxp_fyp_swapped':
+        fxp, fyp = fyp, fxp
+    ta = [g_qax * hw, g_qay * hh, g_wa - fxp * g_qax - fyp * g_qay]
+    tb = [g_qbx * hw, g_qby * hh, g_wb - fxp * g_qbx - fyp * g_qby]
+    base = pr.b[i] * D.V
+    return base + D.E['va'][i, e], base + D.E['vb'][i, e], ta, tb, G.v != 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# choices and evaluation
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _consts(inp, dtype):
+    """The float32 numbers the kernels are handed, as `dtype` tensors: gs = 1 / n_total, K = (-2 cs gs) formed first, bg cs."""
+    B, (H, W), C = inp['pos'].shape[0], inp['res'], inp['tex'].shape[2]
+    n_total = inp.get('n_total') or B * H * W * C
+    gs = np.float32(1.0 / n_total)
+    K = (torch.tensor(-2.0 * CS_SCALE, dtype=dtype) * torch.tensor(float(gs), dtype=dtype))
+    if MUTANT == 'gq_without_2':
+        K = K * 0.5
+    bgs = np.float32(np.float32(inp.get('background', BACKGROUND)) * np.float32(CS_SCALE))
+    return n_total, K, torch.tensor(float(bgs), dtype=dtype)
+
+
+class _State:
+    pass
+
+
+def _tex_coord(px, inp, dtype):
+    uvt = inp['uv'].detach().to('cpu', dtype)[inp['uv_tri'].detach().cpu().long()[px.t]]      # [n,3,2]
+    q = [[_inp(uvt[:, k, c]) for c in range(2)] for k in range(3)]
+    u, v = px.uvz[0], px.uvz[1]
+    w = 1.0 - u - v
+    if MUTANT == 'tu_summed_in_another_order':
+        tu, tv = (u * q[0][0] + w * q[2][0]) + v * q[1][0], (u * q[0][1] + w * q[2][1]) + v * q[1][1]
+    else:
+        tu, tv = u * q[0][0] + v * q[1][0] + w * q[2][0], u * q[0][1] + v * q[1][1] + w * q[2][1]
+    return q, tu, tv
+
+
+def _forward(inp, dtype, ch):
+    """k_shade's per-pixel forward in dtype; ch: dict of the float32 choices (filled when empty)."""
+    st = _State()
+    H, W = inp['res']
+    st.px = px = RR._Pixels(inp['pos'], inp['tri'], inp['ids'], (H, W), dtype)
+    st.q, st.tu, st.tv = _tex_coord(px, inp, dtype)
+    st.lk = _Lookup(inp['tex'], st.tu, st.tv, inp['boundary'], dtype, ch.setdefault('taps', {}))
+    zero = _zeros(1, dtype)
+    if MUTANT == 'esum_with_wrap_taps_under_clamp' and inp['boundary'] == 'clamp':
+        st.lk0 = _Lookup(inp['tex'], zero, zero, 'wrap', dtype, {})
+    else:
+        st.lk0 = _Lookup(inp['tex'], zero, zero, inp['boundary'], dtype, ch.setdefault('taps0', {}))
+    if 'ren' not in ch:
+        ch['ren'], ch['open0'], ch['open1'] = px.ren, (px.b0.v >= 0) & (px.b0.v <= 1), (px.b1.v >= 0) & (px.b1.v <= 1)
+        ch['lo0'], ch['lo1'] = px.b0.v < 0, px.b1.v < 0
+        rast = torch.zeros(px.B, H, W, 4)
+        rast[px.bi, px.yy, px.xx, 2] = px.uvz[2].v
+        rast[..., 3] = inp['ids'].float()
+        ch['rast'] = rast
+        ch['adj'] = AR.topology(inp['tri'])
+        ch['D'] = AR.decisions(None, rast, inp['pos'], inp['tri'], ch['adj'])
+    else:
+        same = torch.equal(px.ren, ch['ren']) and torch.equal((px.b0.v >= 0) & (px.b0.v <= 1), ch['open0']) and \
+            torch.equal((px.b1.v >= 0) & (px.b1.v <= 1), ch['open1']) and torch.equal(px.b0.v < 0, ch['lo0']) and torch.equal(px.b1.v < 0, ch['lo1'])
+        assert same, "a barycentric gate decides differently in float32: the case is not settled"
+    return st
+
+
+@functools.lru_cache(maxsize=None)
+def _choices_cached(name):
+    ch = {}
+    _forward(_case_cache[name], torch.float32, ch)
+    return ch
+
+
+def choices(inp):
+    """Every discrete choice of a call, made in float32 (module docstring) -> dict: ren, open0, open1 (barycentric gates), taps (floor(tu),
+    clamp states and tap cells per axis), taps0 (the lookup at uv = (0, 0)), rast (z/w as k_shade stores it, ids), adj, D
+    (antialias_ref.decisions).  Cached for a case's inputs: treat as read-only."""
+    if _case_cache.get(inp.get('name')) is inp:
+        return _choices_cached(inp['name'])
+    ch = {}
+    _forward(inp, torch.float32, ch)
+    return ch
+
+
+def evaluate(inp, dtype=torch.float64):
+    """The statement on the choices of choices(inp) -> dict: 'value' (value, S) scalars, 'g_pos' (value, S) [B,V,4], 'g_tex' (value, S)
+    [Ht,Wt,C], and what the tests look at: 'st' (the forward), 'D', 'E', 'hit' / 'hit2' (flat pixel indices of the blended covered pixels /
+    of the pixels k_fix<1> visits), 'gq' [n,C] values, 'dd' [n,C] values, 'esum' (C values), 'n_esum' entries, 'terms' per texel."""
+    ch = choices(inp)
+    st = _forward(inp, dtype, ch)
+    px, lk, lk0, D = st.px, st.lk, st.lk0, ch['D']
+    B, (H, W) = px.B, inp['res']
+    Ht, Wt, C = inp['tex'].shape
+    P, n = B * H * W, px.n
+    n_total, K, bgs = _consts(inp, dtype)
+    Kq = Q(K, K.abs())
+    pix = (px.bi * H + px.yy) * W + px.xx                        # flat pixel index of every covered pixel
+    rowof = torch.full((P,), -1, dtype=torch.int64)
+    rowof[pix] = torch.arange(n)
+    cov = rowof >= 0
+    rf_all = inp['ref_u8'].detach().cpu().to(dtype).reshape(-1)
+    rf = _inp(rf_all[pix])
+    d0 = rf - Q(bgs.expand(n), bgs.abs().expand(n))
+    dd = [rf - lk.col[c] * CS_SCALE for c in range(C)]
+    gq = [Kq * dd[c] for c in range(C)]
+    G_tex, S_tex = torch.zeros(Ht * Wt * C, dtype=dtype), torch.zeros(Ht * Wt * C, dtype=dtype)
+    G_pos, S_pos = torch.zeros(B * px.V, 4, dtype=dtype), torch.zeros(B * px.V, 4, dtype=dtype)
+    every = torch.arange(n)
+
+    def chain(g, rows):
+        """texture, interpolate and rasterize backward of d loss / d colour g (C Q [n]) for the pixels `rows`."""
+        lk.scatter(G_tex, S_tex, g, rows)
+        gtu, gtv = lk.backward(g)
+        q = st.q
+        gu = gtu * (q[0][0] - q[2][0]) + gtv * (q[0][1] - q[2][1])
+        gv = gtu * (q[1][0] - q[2][0]) + gtv * (q[1][1] - q[2][1])
+        nine = _uv_bwd(px, gu, gv)
+        for k in range(3):
+            for c3, colm in enumerate((0, 1, 3)):
+                G_pos[:, colm].index_add_(0, px.rows[k][rows], nine[3 * k + c3].v[rows])
+                S_pos[:, colm].index_add_(0, px.rows[k][rows], nine[3 * k + c3].S[rows])
+
+    chain(gq, every)                                                            # k_shade: the un-antialiased gradient of every covered pixel
+
+    # ---- k_fix<0>: the blend of every covered receiver ----
+    pr = D.pairs
+    E = AR._edges(pr, D.pos3, inp['tri'], dtype)
+    ei, ee, er, eo = D.ei, D.ee, D.er, D.eo
+    t = Q(E['t'].v[ei, ee], E['t'].S[ei, ee])
+    amt = _where(D.efar, t - 0.5, 0.5 - t)
+    rc = cov[er]                                                                # entries whose receiver is covered: the others change nothing
+    colP = []
+    for c in range(C):
+        v, S = lk0.col[c].v.expand(P).clone(), lk0.col[c].S.expand(P).clone()
+        v[pix], S[pix] = lk.col[c].v, lk.col[c].S
+        colP.append(Q(v, S))
+    hit = torch.unique(er[rc])
+    hrow = rowof[hit]
+    dn, gaa = [], []
+    for c in range(C):
+        delta = _at(amt, rc) * (_at(colP[c], eo[rc]) - _at(colP[c], er[rc]))
+        av, aS = torch.zeros(P, dtype=dtype), torch.zeros(P, dtype=dtype)
+        av.index_add_(0, er[rc], delta.v)
+        aS.index_add_(0, er[rc], delta.S)
+        acc = Q(av[hit], aS[hit]) + _at(lk.col[c], hrow)
+        dn.append(_at(rf, hrow) - acc * CS_SCALE)
+        gv_, gS_ = torch.zeros(P, dtype=dtype), torch.zeros(P, dtype=dtype)
+        gv_[pix], gS_[pix] = gq[c].v, gq[c].S
+        g_hit = Kq * dn[c]
+        gv_[hit], gS_[hit] = g_hit.v, g_hit.S
+        gaa.append(Q(gv_, gS_))
+
+    # ---- k_fix<1>: the difference, d alpha / d pos, the empty pixels' share ----
+    both = rc & cov[eo]
+    hit2 = torch.unique(torch.cat([er[rc], eo[both]]))
+    h2row = rowof[hit2]
+    dl, esum = [], []
+    for c in range(C):
+        term = _at(amt, rc) * _at(gaa[c], er[rc])
+        gov, goS = torch.zeros(P, dtype=dtype), torch.zeros(P, dtype=dtype)
+        gov.index_add_(0, er[rc], -term.v)
+        goS.index_add_(0, er[rc], term.S)
+        if MUTANT != 'partner_gradient_dropped':
+            o_cov = cov[eo[rc]]
+            gov.index_add_(0, eo[rc][o_cov], term.v[o_cov])
+            goS.index_add_(0, eo[rc][o_cov], term.S[o_cov])
+        go = Q(gov[hit2], goS[hit2]) + _at(gaa[c], hit2)
+        d = go - _at(gq[c], h2row)
+        if MUTANT == 'difference_term_sign_flipped':
+            d = -d
+        if MUTANT == 'difference_term_dropped':
+            d = d * 0.0
+        full = _zeros(n, dtype)
+        full.v[h2row], full.S[h2row] = d.v, d.S
+        dl.append(full)
+        empty_o = ~cov[eo[rc]]
+        esum.append(Q(term.v[empty_o].sum(), term.S[empty_o].sum()))
+    n_esum = int((rc & ~cov[eo]).sum())
+    chain(dl, h2row)
+    if n_esum and MUTANT != 'no_esum_share':
+        one = torch.zeros(1, dtype=torch.int64)
+        lk0.scatter(G_tex, S_tex, [Q(e.v.reshape(1), e.S.reshape(1)) for e in esum], one)
+    col_img = torch.stack([q.v for q in colP], 1)
+    rows_a, rows_b, ta, tb, keep = _edge_pos_terms(D, E, colP, gaa, dtype)
+    for rows, three in ((rows_a, ta), (rows_b, tb)):
+        for colm, q in zip((0, 1, 3), three):
+            G_pos[:, colm].index_add_(0, rows[keep], q.v[keep])
+            S_pos[:, colm].index_add_(0, rows[rc], q.S[rc])
+            if MUTANT == 'd_alpha_counted_by_both_pixels':
+                G_pos[:, colm].index_add_(0, rows[keep & both], q.v[keep & both])
+    # ---- the value ----
+    tv_, tS_ = torch.zeros((), dtype=dtype), torch.zeros((), dtype=dtype)
+    d0h = _at(d0, hrow)
+    for c in range(C):
+        plain = dd[c] * dd[c] if MUTANT == 'background_share_for_covered_pixels_too' else dd[c] * dd[c] - d0 * d0
+        tv_ = tv_ + plain.v.sum()
+        tS_ = tS_ + (plain.S + (dd[c].v * dd[c].v).abs() + d0.v * d0.v).sum()
+        ddh = _at(dd[c], hrow)
+        corr = dn[c] * dn[c] - d0h * d0h
+        if MUTANT != 'hit_pixel_added_without_removing_the_plain_term':
+            corr = corr - (ddh * ddh - d0h * d0h)
+        tv_ = tv_ + corr.v.sum()
+        tS_ = tS_ + (corr.S + dn[c].v * dn[c].v + ddh.v * ddh.v + 2.0 * d0h.v * d0h.v).sum()
+    b = float(np.float32(float(inp.get('background', BACKGROUND)) * 255.0))      # what reference_background_sumsq hands fpcdr_ref_bg_sumsq
+    bg_v, bg_S = bg_sumsq(inp['ref_u8'], b, dtype)
+    value = (tv_ + float(C) * bg_v.sum()) / float(n_total)
+    value_S = (tS_ + float(C) * bg_S.sum()) / float(n_total)
+    return {'value': (value, value_S), 'g_pos': (G_pos.reshape(B, px.V, 4), S_pos.reshape(B, px.V, 4)),
+            'g_tex': (G_tex.reshape(Ht, Wt, C), S_tex.reshape(Ht, Wt, C)), 'st': st, 'D': D, 'E': E, 'hit': hit, 'hit2': hit2, 'pix': pix,
+            'cov': cov, 'rowof': rowof, 'gq': torch.stack([q.v for q in gq], 1), 'dd': torch.stack([q.v for q in dd], 1),
+            'dn': torch.stack([q.v for q in dn], 1) if hit.numel() else torch.zeros(0, C, dtype=dtype), 'n_esum': n_esum, 'col': col_img,
+            'bgs': float(bgs), 'b': b, 'n_total': n_total}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# margins, zeros, the kernel-order statement
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _margins_of(st, D, E64):
+    m = torch.full((st.px.n,), float('inf'), dtype=torch.float64)
+    for q in st.px.gates():
+        m = torch.minimum(m, torch.nan_to_num(q.v.abs() / (U * q.S), nan=0.0))
+    for q in st.lk.gates:
+        m = torch.minimum(m, torch.where(q.S > 0, q.v / (U * q.S), torch.where(q.v > 0, torch.full_like(q.v, float('inf')), torch.zeros_like(q.v))))
+    sil = torch.where(D.pairs.analysed, D.sil_margin, torch.full_like(D.sil_margin, float('inf')))
+    return {'pixel': m, 'edge': AR.edge_margins(D, E64) if D.pairs.n else torch.zeros(0, 3, dtype=torch.float64), 'sil': sil, 'z': D.pairs.zm}
+
+
+def margins(inp, r=None):
+    """How far every float32 choice is from flipping, in units of u of its own scale, on the float64 evaluation r -> dict:
+    'pixel' [n] (barycentric gates, floor(tu), the clamp of tu, the tap cells), 'edge' [pairs,3], 'sil' [B,T] (inf where no pair analyses the
+    triangle), 'z' [pairs]."""
+    r = r or evaluate(inp)
+    return _margins_of(r['st'], r['D'], r['E'])
+
+
+def decision_margin(inp, r=None):
+    return min([float('inf')] + [float(v.min()) for v in margins(inp, r).values() if v.numel()])
+
+
+def _structure(inp):
+    """From the choices alone: reach [Ht*Wt] bool (texels some term reaches), rows [B*V] bool (vertices with a term), the per-texel count of
+    plain terms and whether the empty pixels' share exists."""
+    ch = choices(inp)
+    st = _forward(inp, torch.float32, ch)
+    px, lk, lk0, D = st.px, st.lk, st.lk0, ch['D']
+    B, (H, W) = px.B, inp['res']
+    Ht, Wt, C = inp['tex'].shape
+    pix = (px.bi * H + px.yy) * W + px.xx
+    cov = torch.zeros(B * H * W, dtype=torch.bool)
+    cov[pix] = True
+    count = torch.zeros(Ht * Wt, dtype=torch.int64)
+    for k in range(4):
+        count.index_add_(0, lk.flat[k][lk.valid[k]], torch.ones(int(lk.valid[k].sum()), dtype=torch.int64))
+    rc = cov[D.er]
+    n_esum = int((rc & ~cov[D.eo]).sum())
+    reach = count > 0
+    if n_esum:
+        for k in range(4):
+            reach[lk0.flat[k][lk0.valid[k]]] = True
+    anyv = lk.valid[0] | lk.valid[1] | lk.valid[2] | lk.valid[3]
+    term = (ch['open0'] | ch['open1']) & ((lk.mu != 0) | (lk.mv != 0)) & anyv
+    off_centre = (px.fx.v != 0) | (px.fy.v != 0)      # (the w column's term is -fx g_x - fy g_y: none at the image's centre)
+    rows, rows_w = torch.zeros(B * px.V, dtype=torch.bool), torch.zeros(B * px.V, dtype=torch.bool)
+    for k in range(3):
+        rows[px.rows[k][term]] = True
+        rows_w[px.rows[k][term & off_centre]] = True
+    # an edge entry has a term when its receiver is covered and one of its two colours is not the exact 0 of zero-mode padding
+    live = torch.full((B * H * W,), bool((lk0.valid[0] | lk0.valid[1] | lk0.valid[2] | lk0.valid[3]).any()))
+    live[pix] = anyv
+    ent = rc & (live[D.pairs.pP[D.ei]] | live[D.pairs.pQ[D.ei]])
+    base = D.pairs.b[D.ei] * D.V
+    for r_ in (rows, rows_w):
+        r_[(base + D.E['va'][D.ei, D.ee])[ent]] = True
+        r_[(base + D.E['vb'][D.ei, D.ee])[ent]] = True
+    return dict(reach=reach, rows=rows, rows_w=rows_w, count=count, n_esum=n_esum, cov=cov, pix=pix, st=st, D=D)
+
+
+def predicted_zeros(inp):
+    """The entries without any term, from ids and float32 choices alone, never from values -> dict: 'g_tex' [Ht,Wt,C] bool (texels no tap
+    of a covered pixel and no share of the empty pixels reaches), 'g_pos' [B,V,4] bool (the z column; vertices of triangles no pixel shows
+    or whose pixels all have both clamp gates closed or mu = mv = 0, and of no active edge with a covered receiver: an image wholly behind
+    the camera has every row)."""
+    s = _structure(inp)
+    Ht, Wt, C = inp['tex'].shape
+    B, V = inp['pos'].shape[:2]
+    zp = (~s['rows']).reshape(B, V, 1).expand(B, V, 4).clone()
+    zp[..., 2] = True
+    zp[..., 3] = ~s['rows_w'].reshape(B, V)
+    return {'g_tex': (~s['reach']).reshape(Ht, Wt, 1).expand(Ht, Wt, C).clone(), 'g_pos': zp}
+
+
+def float32_in_kernel_order(inp):
+    """The per-pixel float32 statement, one rounding per operation, in the kernels' order -> dict: 'r' (evaluate(inp, float32)), 'texel'
+    [m] flat indices of the texels that hold exactly one plain term, of a pixel outside every blend, and no share of the empty pixels, and
+    'g_tex' [m,C] the float32 product gq * w_k there; 'gq_w' [n,4,C] all the products."""
+    r = evaluate(inp, torch.float32)
+    s = _structure(inp)
+    lk, C = r['st'].lk, inp['tex'].shape[2]
+    n = r['st'].px.n
+    prod = torch.stack([torch.stack([r['gq'][:, c] * lk.wk[k].v for c in range(C)], 1) for k in range(4)], 1)      # [n,4,C]
+    in_blend = torch.zeros(n, dtype=torch.bool)
+    in_blend[r['rowof'][r['hit2']]] = True
+    single = s['count'] == 1
+    if s['n_esum']:
+        for k in range(4):
+            single[r['st'].lk0.flat[k][r['st'].lk0.valid[k]]] = False
+    texel, val = [], []
+    for k in range(4):
+        ok = lk.valid[k] & single[lk.flat[k]] & ~in_blend
+        texel.append(lk.flat[k][ok])
+        val.append(prod[ok, k])
+    return {'r': r, 'texel': torch.cat(texel), 'g_tex': torch.cat(val), 'gq_w': prod}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# plan: where k_shade places its windows, which tables overflow
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _window(x0, y0, Ht, Wt, cells, boundary):
+    """setup_window on the taps (x0, y0) the first pass kept -> dict ox, oy, ows, owr, owrap, centred, fits (None without a tap)."""
+    if x0.numel() == 0:
+        return None
+    xa, xb, ya, yb = int(x0.min()), int(x0.max()), int(y0.min()), int(y0.max())
+    centred = False
+    if boundary == 'wrap' and (xb - xa >= (Wt >> 1) or yb - ya >= (Ht >> 1)):
+        cx, cy = torch.where(x0 >= (Wt >> 1), x0 - Wt, x0), torch.where(y0 >= (Ht >> 1), y0 - Ht, y0)
+        xa2, xb2, ya2, yb2 = int(cx.min()), int(cx.max()), int(cy.min()), int(cy.max())
+        if xb2 - xa2 < xb - xa:
+            xa, xb, centred = xa2, xb2, True
+        if yb2 - ya2 < yb - ya:
+            ya, yb, centred = ya2, yb2, True
+    nw, nh = xb - xa + 2, yb - ya + 2
+    sx0, sy0 = xa, ya
+    fits = nw * nh <= cells
+    if fits:
+        stride = nw
+        rows = cells // stride
+        sy0 -= (rows - nh) >> 1
+    else:
+        f = np.float32
+        aspect = min(max(f(nw) / f(nh), f(1.0) / f(cells)), f(cells))
+        stride = min(max(int(np.sqrt(f(f(cells) * aspect))), 2), cells // 2)
+        rows = cells // stride
+        sx0 += (nw - stride) >> 1
+        sy0 += (nh - rows) >> 1
+    owrap = sx0 < 0 or sy0 < 0 or sx0 + stride > Wt or sy0 + rows > Ht
+    return dict(ox=sx0, oy=sy0, ows=stride, owr=rows, owrap=owrap, centred=centred, fits=fits, box=(nw, nh))
+
+
+def plan(inp):
+    """In integers, per occupied bin (b, by, bx) and half, what k_shade and k_fix do with the call -> dict:
+    'halves': {(b, by, bx, half): window dict + 'inside' / 'outside' (pixels whose four adds go into the window / to memory)},
+    'bins': {(b, by, bx): dict vertices (distinct, of the pixels with a gradient: against VT_SLOTS), deferred, hit, hit_vertices (against FVS),
+    hit_texels (against FTS), sil (a silhouette bit in the plane or its apron: the bin takes a record slot)},
+    'pairs': blended pairs, 'cross': those across a bin border, 'empty_partner': entries with a covered receiver and an empty partner,
+    'image_border': blended pairs with a pixel on the image's border, 'max_deferred': the most deferred pixels of a bin."""
+    s = _structure(inp)
+    st, D = s['st'], s['D']
+    px, lk = st.px, st.lk
+    B, (H, W) = px.B, inp['res']
+    Ht, Wt, C = inp['tex'].shape
+    cells, bd = OWIN_CELLS[C], inp['boundary']
+    ids = inp['ids'].detach().cpu().long()
+    sil = D.sil                                                        # [B,T]
+    silpix = torch.zeros(B, H, W, dtype=torch.int64)
+    silpix[px.bi, px.yy, px.xx] = sil[px.bi, px.t]
+    code = ids | (silpix << 24)
+    # deferred: pair_maybe with an in-image neighbour
+    pad = torch.zeros(B, H + 2, W + 2, dtype=torch.int64)
+    pad[:, 1:-1, 1:-1] = code
+    inimg = torch.zeros(B, H + 2, W + 2, dtype=torch.bool)
+    inimg[:, 1:-1, 1:-1] = True
+    deferred = torch.zeros(B, H, W, dtype=torch.bool)
+    for dy, dx in ((0, 1), (1, 0), (0, -1), (-1, 0)):
+        nb = pad[:, 1 + dy:H + 1 + dy, 1 + dx:W + 1 + dx]
+        ok = inimg[:, 1 + dy:H + 1 + dy, 1 + dx:W + 1 + dx]
+        deferred |= ok & (((code ^ nb) & 0xffffff) != 0) & (((code | nb) >> 24) != 0)
+    deferred &= ids > 0
+    rc = s['cov'][D.er]
+    hit2 = torch.zeros(B * H * W, dtype=torch.bool)
+    hit2[D.er[rc]] = True
+    hit2[D.eo[rc & s['cov'][D.eo]]] = True
+    hit2 = hit2.reshape(B, H, W)
+    key = (px.bi * 1000 + px.yy // BIN) * 1000 + px.xx // BIN
+    halves, bins = {}, {}
+    is_hit = hit2[px.bi, px.yy, px.xx]
+    ent_bin = lambda p: ((p // (H * W)) * 1000 + ((p // W) % H) // BIN) * 1000 + (p % W) // BIN
+    for k in torch.unique(key).tolist():
+        b, by, bx = k // 1000000, (k // 1000) % 1000, k % 1000
+        m = key == k
+        for half in (0, 1):
+            zy = px.yy - by * BIN
+            mh = m & (zy // 16 == half)
+            if not bool(mh.any()):
+                continue
+            first = mh & torch.isin(zy % 16, torch.tensor(PASS0_ROWS))
+            w = _window(lk.x0[first], lk.y0[first], Ht, Wt, cells, bd)
+            if w is None:
+                w = dict(ox=0, oy=0, ows=1, owr=1, owrap=False, centred=False, fits=True, box=(0, 0))
+            lx, ly = lk.x0[mh] - w['ox'], lk.y0[mh] - w['oy']
+            if bd == 'wrap' and w['owrap']:
+                wc = lambda d, n: torch.where(d < 0, d + n, torch.where(d >= n, d - n, d))
+                lx, ly = wc(lx, Wt), wc(ly, Ht)
+            inside = (lx >= 0) & (lx < w['ows'] - 1) & (ly >= 0) & (ly < w['owr'] - 1)
+            halves[(b, by, bx, half)] = dict(w, inside=int(inside.sum()), outside=int((~inside).sum()))
+        y0, x0 = by * BIN, bx * BIN
+        apron = code[b, max(y0 - 1, 0):y0 + BIN + 1, max(x0 - 1, 0):x0 + BIN + 1]
+        apron = apron.clone()
+        # (the four corners of the apron are not loaded)
+        sub = torch.zeros_like(apron, dtype=torch.bool)
+        ys, xs = max(y0 - 1, 0), max(x0 - 1, 0)
+        sub[(y0 - ys):(y0 - ys) + BIN, :] = True
+        sub[:, (x0 - xs):(x0 - xs) + BIN] = True
+        mhit = m & is_hit
+        ent = rc & ((ent_bin(D.pairs.pP[D.ei]) == k) | (ent_bin(D.pairs.pQ[D.ei]) == k))
+        ent_first = rc & (ent_bin(torch.where(s['cov'][D.pairs.p0[D.ei]], D.pairs.p0[D.ei], D.pairs.p1[D.ei])) == k)
+        hv = torch.cat([px.vi[mhit].reshape(-1), D.E['va'][D.ei, D.ee][ent_first], D.E['vb'][D.ei, D.ee][ent_first]])
+        bins[(b, by, bx)] = dict(
+            vertices=int(torch.unique(px.vi[m].reshape(-1)).numel()), deferred=int(deferred[b, y0:y0 + BIN, x0:x0 + BIN].sum()),
+            hit=int(mhit.sum()), hit_vertices=int(torch.unique(hv).numel()),
+            hit_texels=int(torch.unique(torch.cat([lk.flat[t][mhit & lk.valid[t]] for t in range(4)])).numel()),
+            sil=bool((((apron >> 24) != 0) & sub).any()), entries=int(ent.sum()))
+    pr = D.pairs
+    blended = D.active.any(1)
+    p0, p1 = pr.p0[blended], pr.p1[blended]
+    on_border = lambda p: ((p % W) == 0) | ((p % W) == W - 1) | (((p // W) % H) == 0) | (((p // W) % H) == H - 1)
+    return dict(halves=halves, bins=bins, pairs=int(blended.sum()), cross=int((ent_bin(p0) != ent_bin(p1)).sum()),
+                cross_x31=int(((pr.x0[blended] % BIN == BIN - 1) & (pr.d[blended] == 0)).sum()),
+                cross_y31=int(((pr.y0[blended] % BIN == BIN - 1) & (pr.d[blended] == 1)).sum()),
+                empty_partner=s['n_esum'], image_border=int((on_border(p0) | on_border(p1)).sum()),
+                max_deferred=max([v['deferred'] for v in bins.values()] + [0]), deferred=int(deferred.sum()), hit=int(hit2.sum()),
+                code=code)
+
+
+def id_planes(inp):
+    """The id planes the call leaves (include/fpcdr.h): (triangle + 1) | silhouette bits << 24 per pixel -> [B,H,W] int64."""
+    return plan(inp)['code']
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the cases of tests/test_gpu_objective_ref.py
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _unsafe(inp, shared=False):
+    """-> (rows of pos.reshape(-1, 4), rows of uv) of every triangle with a choice closer than SETTLE_MARGIN.  Unshared triangles move
+    whole, with their three texture coordinates.  shared (a mesh): a tap too close to a cell border moves the texture coordinate of ONE
+    corner, the one the pixel weighs most, and leaves the geometry -- a vertex re-draws its whole fan."""
+    ch = {}
+    _forward(inp, torch.float32, ch)
+    try:
+        st = _forward(inp, torch.float64, ch)
+    except AssertionError:      # (a gate that float32 and float64 decide differently: closer than any margin)
+        st = _forward(inp, torch.float64, {})
+    D = ch['D']
+    E64 = AR._edges(D.pairs, D.pos3, inp['tri'], torch.float64)
+    px = st.px
+    geo, tap = torch.zeros(px.n, dtype=torch.bool), torch.zeros(px.n, dtype=torch.bool)
+    for q in px.gates():
+        geo |= ~(q.v.abs() > SETTLE_MARGIN * U * q.S)
+    for q in st.lk.gates:
+        tap |= ~(q.v > SETTLE_MARGIN * U * q.S)
+        geo |= SETTLE_MARGIN * U * q.S > 0.25      # (a triangle seen edge-on: a scale no fraction is safe at; the triangle moves)
+    if not shared:
+        geo |= tap
+    rows = torch.unique(torch.cat([px.rows[k][geo] for k in range(3)] + [AR._unsafe_rows(D, E64)]))
+    tap &= ~geo
+    u, v = px.uvz[0].v[tap], px.uvz[1].v[tap]
+    corner = torch.stack([u, v, 1.0 - u - v], 1).argmax(1)
+    return rows, torch.unique(torch.cat([inp['uv_tri'].long()[px.t[geo]].reshape(-1), inp['uv_tri'].long()[px.t[tap], corner]]))
+
+
+def _settle(g, ids_of, gen, rounds=200):
+    """Move (by up to 0.05 pixel a round) the vertices of every triangle with a choice too close, and its texture coordinates, until none
+    is.  g: dict X [B,V,2], z, w [B,V] float64, uv [Vt,2] float64 (or uv_fn(X, off) with off [T,2], the per-triangle offsets that are
+    drawn again instead) and the rest of the inputs -> the inputs."""
+    H, W = g['res']
+    kept, fewest = None, None
+    for _ in range(rounds):
+        pos = _clip(g['X'], g['z'], g['w'], H, W)
+        uv = g['uv_fn'](g['X'], g['off']) if 'uv_fn' in g else g['uv']
+        inp = dict(pos=pos, tri=g['tri'], ids=ids_of(pos, g['tri']), res=g['res'], uv=uv.float().contiguous(), uv_tri=g['uv_tri'], tex=g['tex'],
+                   ref_u8=g['ref_u8'], boundary=g['boundary'])
+        shared = bool(g.get('shared'))
+        rows, uvr = _unsafe(inp, shared)
+        if rows.numel() == 0 and uvr.numel() == 0:
+            return inp
+        # (shared vertices: a move that leaves more to move than the state it started from is taken back)
+        if shared and fewest is not None and rows.numel() + uvr.numel() > fewest:
+            g['X'], g['uv'], g['off'], rows, uvr = kept[0].clone(), None if kept[1] is None else kept[1].clone(), \
+                None if kept[2] is None else kept[2].clone(), kept[3], kept[4]
+        else:
+            fewest = rows.numel() + uvr.numel()
+            kept = (g['X'].clone(), None if g.get('uv') is None else g['uv'].clone(), None if g.get('off') is None else g['off'].clone(), rows, uvr)
+        if 'shift' in g:      # every image shows the triangles of the first, a whole number of pixels away
+            rows = torch.unique(rows % g['X'].shape[1])
+            g['X'][0][rows] += (torch.rand(rows.numel(), 2, generator=gen, dtype=torch.float64) - 0.5) * 0.1
+            g['X'] = g['X'][:1] + g['shift']
+        else:
+            g['X'].reshape(-1, 2)[rows] += (torch.rand(rows.numel(), 2, generator=gen, dtype=torch.float64) - 0.5) * 0.1
+        if 'uv_fn' in g:
+            tr = torch.unique(uvr // 3)
+            g['off'][tr] = g['draw_off'](tr.numel())
+        else:
+            g['uv'][uvr] += (torch.rand(uvr.numel(), 2, generator=gen, dtype=torch.float64) - 0.5) * (0.05 if shared else 0.004)
+    raise AssertionError("the construction does not settle")
+
+
+def _fat_soup(B, T, gen, H, W, size_px):
+    """rasterize_ref._soup_geometry with triangles near equilateral (circumradius 0.7 to 1 size_px, corners within 25 degrees of a regular
+    triangle's): a sliver's barycentrics -- and with them its texture coordinate -- have a scale of thousands of u, and no fraction is
+    64 of those away from a cell border."""
+    rnd = lambda *shape: torch.rand(*shape, generator=gen, dtype=torch.float64)
+    centre = torch.stack([rnd(B, T, 1) * (W + 10) - 5, rnd(B, T, 1) * (H + 10) - 5], -1)
+    ang = rnd(B, T, 1) * 2 * math.pi + torch.arange(3, dtype=torch.float64) * (2 * math.pi / 3) + (rnd(B, T, 3) - 0.5) * (50 * math.pi / 180)
+    rad = size_px * (0.7 + 0.3 * rnd(B, T, 3))
+    X = centre + torch.stack([rad * torch.cos(ang), rad * torch.sin(ang)], -1)
+    z = rnd(B, T * 3) * 1.8 - 0.9
+    w = rnd(B, T * 3) * 2.5 + 0.5
+    return X.reshape(B, T * 3, 2), z, w, torch.arange(T * 3, dtype=torch.int32).reshape(T, 3)
+
+
+def _subdivided(v, tri):
+    """Every triangle of a mesh on the unit sphere split in four (midpoints pushed back onto the sphere)."""
+    v, mid, out = [tuple(p) for p in v.tolist()], {}, []
+
+    def m(a, b):
+        key = (min(a, b), max(a, b))
+        if key not in mid:
+            p = np.array(v[a]) + np.array(v[b])
+            v.append(tuple(p / np.linalg.norm(p)))
+            mid[key] = len(v) - 1
+        return mid[key]
+
+    for a, b, c in tri.tolist():
+        ab, bc, ca = m(a, b), m(b, c), m(c, a)
+        out += [(a, ab, ca), (ab, b, bc), (ca, bc, c), (ab, bc, ca)]
+    return torch.tensor(v, dtype=torch.float64), torch.tensor(out, dtype=torch.int32)
+
+
+def _screen_uv(X, Ht, Wt, tpp, origin=(0.0, 0.0)):
+    """Texture coordinates affine in the screen position: tpp texels per pixel along both axes."""
+    return torch.stack([(X[..., 0] - origin[0]) * tpp / Wt, (X[..., 1] - origin[1]) * tpp / Ht], -1)
+
+
+ISLANDS = [[(6.3, 5.2), (17.8, 8.1), (9.4, 19.7)], [(40.2, 4.4), (58.9, 12.3), (44.1, 17.6)], [(8.8, 30.3), (21.2, 41.7), (5.1, 40.2)],
+           [(36.4, 27.9), (62.3, 33.2), (49.7, 43.1)], [(26.1, 18.2), (32.7, 21.9), (28.3, 27.4)]]
+TINY = {'1x1': ((1, 1), [(-1.0, -1.0), (3.0, -1.0), (0.0, 3.0)]), '1x2': ((1, 2), [(0.2, -1.0), (1.2, 0.4), (0.1, 2.0)]),
+        '2x1': ((2, 1), [(-1.0, 0.1), (2.0, 0.2), (0.4, 1.2)])}
+
+
+# right edges between the pixel centres of columns 31 | 32 and 63 | 64 (the one-pixel partial bin column), a bottom edge between rows 31 | 32
+BORDER_TRIS = [[(20.0, 9.0), (31.9, 3.2), (31.95, 21.0)], [(52.0, 8.0), (63.9, 2.4), (63.95, 24.0)], [(40.0, 20.0), (58.0, 31.9), (41.0, 31.95)]]
+
+
+def _case(name, why, geom, C, boundary, tex_hw, res=(45, 70), B=2, **kw):
+    return dict(dict(name=name, why=why, geom=geom, C=C, boundary=boundary, tex_hw=tex_hw, res=res, B=B), **kw)
+
+
+def _cases():
+    out = []
+    c = lambda *a, **kw: out.append(_case(*a, **kw))
+    c('magnified/C1/wrap', 'k_shade_list<1, WRAP>; 3 texels a pixel: one term per texel, the aspect window, taps inside and outside it',
+      'soup', 1, 'wrap', (256, 256), n_tri=36, size=14.0, tpp=3.0, affine=True)      # (256: 70 pixels of 3 texels lap a 128-texel row, and
+    #                                        the taps {3 p, 3 p + 1} of column p would meet those of column p + 43 at 3 * 43 = 129 = 128 + 1)
+    c('soup/C1/wrap/seam', 'a 24 x 16 texture at half a texel a pixel over several periods: the centred view, owrap, many terms per texel',
+      'soup', 1, 'wrap', (16, 24), n_tri=60, size=10.0, tpp=0.5)
+    c('soup/C3/clamp', 'k_shade_list<3, -1>, 1600 cells; uv beyond [0, 1]: mu / mv = 0', 'soup', 3, 'clamp', (12, 20), n_tri=60, size=10.0, span=1.6)
+    c('soup/C4/zero', 'k_shade_list<4, -1>; taps with two, three and four corners in the padding', 'soup', 4, 'zero', (10, 14), n_tri=60, size=10.0, span=1.6)
+    c('mesh/B3', 'a closed mesh in three poses, the third behind the camera: shared vertices, folds, bins without a silhouette', 'mesh', 3, 'wrap',
+      (4, 4), res=(96, 96), B=3)
+    c('confetti', 'over 256 vertices in a bin, over 64 vertices and 128 texels among its blended pixels: all three tables go to memory', 'confetti', 1,
+      'wrap', (16, 16), n_tri=700, size=3.2)
+    for bd, C in (('wrap', 1), ('clamp', 3), ('zero', 4)):
+        c(f'islands/{bd}', 'separated triangles on an empty frame: every blend has an empty partner; uv away from the taps of (0, 0)', 'islands', C, bd,
+          (16, 16))
+    c('borders', 'blended pairs across columns and rows 31 | 32 and on the image border at 33 x 65 (one-pixel partial bins)', 'soup', 3, 'wrap', (16, 24),
+      res=(33, 65), n_tri=24, size=11.0, tpp=0.5, extra=BORDER_TRIS)
+    for k in TINY:
+        c(f'tiny/{k}', 'an image of one or two pixels', 'tiny', 3 if k == '1x1' else 1, 'wrap', (8, 8), res=TINY[k][0], B=1, tiny=k)
+    return out
+
+
+CASES = _cases()
+CASE_IDS = [c['name'] for c in CASES]
+_case_cache = {}
+
+
+def _geometry(c, gen):
+    """-> X [B,V,2], z, w [B,V], tri, uv [Vt,2] float64, uv_tri."""
+    (H, W), B, (Ht, Wt) = c['res'], c['B'], c['tex_hw']
+    if c['geom'] in ('soup', 'confetti'):
+        X, z, w, tri = _fat_soup(B, c['n_tri'], gen, H, W, c['size'])
+        if 'extra' in c:      # hand-placed triangles in front of the soup (z/w = -0.95), the same in every image but 0.37 pixel apart
+            E = torch.tensor(c['extra'], dtype=torch.float64).reshape(1, -1, 2) + torch.arange(B, dtype=torch.float64).reshape(B, 1, 1) * 0.37
+            X, z = torch.cat([X, E], 1), torch.cat([z, torch.full((B, E.shape[1]), -0.95, dtype=torch.float64)], 1)
+            w = torch.cat([w, torch.rand(B, E.shape[1], generator=gen, dtype=torch.float64) * 2.5 + 0.5], 1)
+            tri = torch.arange(X.shape[1], dtype=torch.int32).reshape(-1, 3)
+        if c['geom'] == 'confetti':      # every triangle at its own place in the texture, at about a texel a pixel
+            centre = X[0].reshape(-1, 3, 2).mean(1, keepdim=True)
+            uv = (torch.rand(c['n_tri'], 1, 2, generator=gen, dtype=torch.float64) + (X[0].reshape(-1, 3, 2) - centre) / Wt).reshape(-1, 2)
+        elif 'span' in c:
+            uv = torch.stack([X[0, :, 0] / W, X[0, :, 1] / H], -1) * c['span'] - 0.5 * (c['span'] - 1.0)
+        elif c.get('affine'):
+            # w one per triangle: the interpolation is affine in the screen, the step a whole number of texels a pixel, and the fraction
+            # (fx, fy) one per triangle, drawn away from the cell borders -- at 128 texels the coordinate's own scale is thousands of u, and
+            # no triangle of random fractions keeps all its pixels 64 of them away from a border
+            w = w.reshape(B, -1, 3)[..., :1].expand(-1, -1, 3).reshape(B, -1).contiguous()
+            shift = torch.tensor([[3.0, -2.0]], dtype=torch.float64) * torch.arange(B, dtype=torch.float64).reshape(B, 1, 1)
+            X = X[:1] + shift
+            w[1:] = -w[1:]      # the second image lies behind the camera: every texel under a pixel outside a blend has ONE term
+            draw = lambda n: 0.15 + 0.7 * torch.rand(n, 2, generator=gen, dtype=torch.float64)
+            fn = lambda X_, off: (_screen_uv(X_[0], Ht, Wt, c['tpp']).reshape(-1, 3, 2) + ((off - c['tpp'] * 0.5 + 0.5) / torch.tensor([Wt, Ht]))[:, None]).reshape(-1, 2)
+            return X, z, w, tri, None, tri.clone(), dict(uv_fn=fn, off=draw(c['n_tri']), draw_off=draw, shift=shift)
+        else:
+            uv = _screen_uv(X[0], Ht, Wt, c['tpp'], origin=(-7.3, -5.1))
+        return X, z, w, tri, uv, tri.clone(), {}
+    if c['geom'] == 'mesh':
+        v, tri = _subdivided(*AR._octahedron())      # 66 vertices, 128 triangles, closed
+        Xs, zs, ws = [], [], []
+        for b in range(3):
+            Rm, _ = torch.linalg.qr(torch.randn(3, 3, generator=gen, dtype=torch.float64))
+            p = v @ Rm.T * torch.tensor([1.0, 0.9, 1.1], dtype=torch.float64)
+            wv = 3.0 + p[:, 2]
+            Xs.append(torch.stack([W / 2 + 1.3 * (b - 1) + 130.0 * p[:, 0] / wv, H / 2 - 0.7 * b + 130.0 * p[:, 1] / wv], 1))
+            zs.append(p[:, 2] / 4.0)
+            ws.append(wv if b < 2 else -wv)      # the third pose: every w negative, the image shows nothing
+        uv = 0.5 + 0.45 * v[:, :2] + 0.1 * v[:, 2:3]
+        return torch.stack(Xs), torch.stack(zs), torch.stack(ws), tri, uv, tri.clone(), dict(shared=True)
+    tris = ISLANDS if c['geom'] == 'islands' else [TINY[c['tiny']][1]]
+    X = torch.tensor(tris, dtype=torch.float64).reshape(1, -1, 2).repeat(B, 1, 1)
+    X = X + torch.arange(B, dtype=torch.float64).reshape(B, 1, 1) * 0.37
+    n = X.shape[1] // 3
+    w = torch.rand(B, 3 * n, generator=gen, dtype=torch.float64) * 2.5 + 0.5
+    z = torch.rand(B, 3 * n, generator=gen, dtype=torch.float64) * 1.8 - 0.9
+    tri = torch.arange(3 * n, dtype=torch.int32).reshape(n, 3)
+    uv = 0.3 + 0.4 * torch.rand(3 * n, 2, generator=gen, dtype=torch.float64)
+    return X, z, w, tri, uv, tri.clone(), {}
+
+
+def case_inputs(name, oracle_ops):
+    """The float32 inputs of a case, settled: dict with pos [B,V,4], tri, ids (oracle_ops.rasterize_ids), res, uv [Vt,2], uv_tri, tex
+    [Ht,Wt,C], ref_u8 [B,H,W], boundary.  Cached: treat as read-only."""
+    if name in _case_cache:
+        return _case_cache[name]
+    c = CASES[CASE_IDS.index(name)]
+    gen = torch.Generator().manual_seed(4000 + sum(ord(ch) for ch in name.split('/')[0]) + 7 * c['C'])
+    X, z, w, tri, uv, uv_tri, extra = _geometry(c, gen)
+    (H, W), B, (Ht, Wt), C = c['res'], c['B'], c['tex_hw'], c['C']
+    tex = (torch.rand(Ht, Wt, C, generator=gen) * 0.5 + 0.01).contiguous()
+    ref = torch.randint(1, 141, (B, H, W), generator=gen, dtype=torch.uint8)      # (never 0: a pixel that shows only zero-mode padding has colour 0, and dd = 0 must not occur)
+    g = dict(X=X, z=z, w=w, tri=tri, uv=uv, uv_tri=uv_tri, tex=tex, ref_u8=ref, boundary=c['boundary'], res=(H, W), **dict(dict(off=None), **extra))
+    inp = _settle(g, lambda p, t: oracle_ops.rasterize_ids(p, t, (H, W)), gen)
+    inp['name'] = name
+    _case_cache[name] = inp
+    return inp
+
+
+@functools.lru_cache(maxsize=None)
+def _reference_cached(name, dtype):
+    return evaluate(_case_cache[name], dtype)
+
+
+def reference(inp, dtype=torch.float64):
+    """evaluate() on a case's inputs.  Cached: treat as read-only."""
+    if _case_cache.get(inp.get('name')) is inp and MUTANT is None:
+        return _reference_cached(inp['name'], dtype)
+    return evaluate(inp, dtype)
+
+
+def measure_rows(x, ref, name):
+    """measure() of output `name` (g_tex, g_pos) -> list of (row name, e in units of u): g_pos has its w column on a row of its own."""
+    r, S = ref[name]
+    x = x.detach().cpu()
+    if name == 'g_tex':
+        return [('g_tex', measure(x, r, S)[0])]
+    xyz = [0, 1, 2]
+    return [('g_pos', measure(x[..., xyz], r[..., xyz], S[..., xyz])[0]), ('g_pos.w', measure(x[..., 3], r[..., 3], S[..., 3])[0])]
+
+
+def value_error(x, ref):
+    """|x - r| / S of the value in units of u."""
+    r, S = ref['value']
+    return abs(float(x) - float(r)) / float(S) / U
+
+
+def failures(inp, ref, r32, got, k32=None):
+    """What of `got` (value, g_tex, g_pos, optionally the one-term texels) misses a bar of tests/test_gpu_objective_ref.py -> list.  ref, r32: evaluate() in float64 and float32; k32: float32_in_kernel_order."""
+    bad = []
+    zeros = predicted_zeros(inp)
+    for k in OUTPUTS:
+        if not torch.equal(ref[k][1] == 0, zeros[k]):
+            bad.append((k, 'the entries without a scale are not the predicted ones'))
+        try:
+            rows, rows32 = measure_rows(got[k], ref, k), measure_rows(r32[k][0], ref, k)
+        except AssertionError:
+            bad.append((k, 'a term where there is none'))
+            continue
+        for (row, e), (_, e32) in zip(rows, rows32):
+            if not e <= 8 * e32 + 4:
+                bad.append((row, 'bound', round(e, 2), round(8 * e32 + 4, 2)))
+    n = n_value(inp['tex'].shape[2], plan(inp)['max_deferred'])
+    if not value_error(got['value'], ref) <= n + 2:
+        bad.append(('value', value_error(got['value'], ref), n + 2))
+    if k32 is not None and not torch.equal(got['g_tex'].reshape(-1, inp['tex'].shape[2])[k32['texel']].float(), k32['g_tex']):
+        bad.append(('g_tex', 'a one-term texel is not gq * w bit for bit'))
+    return bad
