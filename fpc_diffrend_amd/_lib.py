@@ -141,6 +141,15 @@ class RobustLoss(ctypes.Structure):
                 ("sums", _p), ("grad_color", _p)]
 
 
+WSUM_SLOTS = 32     # FPCDR_WSUM_SLOTS
+
+
+class ObjectiveWeighted(ctypes.Structure):
+    """fpcdr_objective_weighted_params: the plain call's parameters as `base`, then the weights."""
+    _fields_ = [("base", Objective), ("kind", _i), ("inv_c", ctypes.c_float), ("w_outside", ctypes.c_float), ("sat", _i),
+                ("T_weights", _i), ("mask", _p), ("face_w", _p), ("wsum", _p)]
+
+
 ADAM_MAX_TENSORS = 16     # FPCDR_ADAM_MAX_TENSORS
 
 
@@ -211,6 +220,8 @@ SYMBOLS = {
     "fpcdr_norm_loss_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "fpcdr_norm_loss": (_int, [ctypes.POINTER(NormLoss), _p]),
     "fpcdr_robust_loss": (_int, [ctypes.POINTER(RobustLoss), _p]),
+    "fpcdr_objective_weighted_fwd": (_int, [ctypes.POINTER(ObjectiveWeighted), _p]),
+    "fpcdr_ref_bg_wsum": (_int, [_p, _p, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, _i, ctypes.c_float, ctypes.c_float, _i, _p, _p]),
     "fpcdr_adam_step": (_int, [ctypes.POINTER(AdamParams), _p]),
     "fpcdr_undistort_u8": (_int, [_p, _p, _p, ctypes.c_int64, _i, _i, _i, _i, _i, _p]),
     "fpcdr_compare_u8": (_int, [_p, _int, ctypes.c_float, _p, _p, _p, ctypes.c_int64, _i, _i, _i, _i, _i, _i, _p]),

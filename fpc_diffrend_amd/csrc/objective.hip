@@ -18,9 +18,14 @@
 //                                      it), and the antialias op's own d alpha / d pos
 //
 // The antialias pair analysis -- ~1 % of the covered pixels, 56 spilled VGPRs in the old backward -- lives in k_fix alone.
+//
+// fpcdr_objective_weighted_fwd runs WEIGHTED instantiations of k_shade and k_fix (template flag WGT, the weights in a kernel parameter of
+// their own, WgtO): the Robust loss rule's rho, psi and per-pixel weights in the three places the loss enters.  The plain instantiations
+// contain none of it ("Weighted objective rule").
 #include "common.h"
 
 #include <stdlib.h>
+#include <cmath>
 
 namespace {
 
@@ -77,6 +82,54 @@ struct MipO {
     TexLevels lv;      // tex[0] = ObjArgs.tex, grad[0] = ObjArgs.grad_tex; grad[] all null when no texture gradient is wanted
     int n_levels;
 };
+// WEIGHTED instantiations ("Weighted objective rule"; fpcdr_objective_weighted_fwd): the Robust loss rule's rho, psi and
+// weights inside the one-pass kernels.  A kernel parameter of its own, as MipO is: ObjArgs and the plain kernels know nothing of it.
+constexpr int WSLOTS = FPCDR_WSUM_SLOTS;
+struct WgtO {
+    const uint8_t *mask;      // [B,H,W] or null: read where the capture byte is
+    const float *face_w;      // [T] or null: one gather on the triangle
+    int T, kind;
+    float inv_c, w_outside;
+    int sat;
+    double *wsum;             // [WSLOTS]: C * sum over covered pixels of (w - w0), zeroed by the call
+};
+// rho and psi = rho' / 2 of one residual: the expressions of k_robust_loss (robust.hip), the kind a wave-uniform branch
+__device__ __forceinline__ void rho_psi(const WgtO *wa, float d, float &rho, float &psi) {
+    const float dd = d * d;
+    rho = dd;
+    float s = 1.0f;
+    if (wa->kind != FPCDR_ROBUST_L2) {      // (uniform)
+        const float z = d * wa->inv_c;
+        const float t = z * z;
+        if (wa->kind == FPCDR_ROBUST_CHARBONNIER) {
+            const float h = sqrtf(1.0f + t);
+            rho = (2.0f * dd) / (1.0f + h);
+            s = 1.0f / h;
+        } else {
+            const float q = 1.0f + t;
+            rho = dd / q;
+            s = 1.0f / (q * q);
+        }
+    }
+    psi = d * s;
+}
+// wm of a pixel from its mask byte and its capture value (rf: the byte as a float), and the weight of face t
+__device__ __forceinline__ float mask_weight(const WgtO *wa, const uint8_t *maskp, unsigned int poff, float rf) {
+    float wm = wa->mask ? (float)ld32(maskp, poff) * (1.0f / 255.0f) : 1.0f;      // (uniform branch)
+    if (wa->sat > 0 && rf >= (float)wa->sat) wm = 0.0f;
+    return wm;
+}
+__device__ __forceinline__ float face_weight(const WgtO *wa, int t) {
+    if (!wa->face_w) return 1.0f;      // (uniform)
+    return (unsigned int)t < (unsigned int)wa->T ? ld32(wa->face_w, (unsigned int)t) : 0.0f;      // (a wrong table length reads nothing out of bounds)
+}
+// the weighted form of loss_grad: ONE expression for the three kernels; w = 1 and kind L2 give loss_grad's bits
+__device__ __forceinline__ float loss_grad_w(const WgtO *wa, float w, float dd, float color_scale, float grad_scale) {
+    float rho, psi;
+    rho_psi(wa, dd, rho, psi);
+    return (-2.0f * color_scale * grad_scale) * (w * psi);
+}
+
 // MIP: the texel gradients of a bin go through THREE LDS windows, for the finest level any of its sampled pixels uses (lb) and the two
 // above it -- a pixel's lookup blends two adjacent levels, so a bin whose level of detail spans less than two levels stays inside.  A
 // window is a rectangle of at most MWIN_CELLS[j] / CS cells whose shape follows the bin's footprint in its level (the prepass of
@@ -147,9 +200,9 @@ __device__ __forceinline__ int shade_row_pair(int k, int w) {
     return (int)((packed >> (4 * w)) & 15u);
 }
 
-template <int CS, int BMODE, bool MIP = false>
+template <int CS, int BMODE, bool MIP = false, bool WGT = false>
 __device__ __forceinline__ void shade_body(const int b, const int bxi, const int byi, const int OX, const int OY, const ObjArgs &a,
-                                           const KArgs ka, const MipO *ma = nullptr) {
+                                           const KArgs ka, const MipO *ma = nullptr, const WgtO *wa = nullptr) {
     const int boundary = BMODE >= 0 ? BMODE : a.boundary;
     __shared__ int s_mred[18];      // MIP prepass: min level, min / max keys of the prepared u and v, and of both shifted by half a period
     __shared__ unsigned int s_id[(OB + 2) * OS];
@@ -161,7 +214,7 @@ __device__ __forceinline__ void shade_body(const int b, const int bxi, const int
     __shared__ unsigned int s_cmask[OB];
     __shared__ __attribute__((aligned(16))) int s_vote[8];      // block4_any: one slot per wave and vote
     __shared__ float s_fy[OB];
-    __shared__ float s_lpart[ONT / 64];
+    __shared__ float s_lpart[(WGT ? 2 : 1) * (ONT / 64)];      // (WGT: the waves' sums of w - w0 behind their loss sums)
     const VTable vt = {s_vkey, s_vacc};
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -242,6 +295,7 @@ __device__ __forceinline__ void shade_body(const int b, const int bxi, const int
     const float cs = a.color_scale, gs = a.grad_scale;
     const float bgs = a.bg * cs;
     float lsum = 0.0f;
+    float wacc = 0.0f;      // WGT: sum of w - w0 over this lane's covered pixels
     bool any_def = false;
     bool owrap = false;      // the window reaches across the edge of a periodic coordinate
     int ox = 0, oy = 0, ows = 1, owr = 1;      // origin, row stride and rows of the texel window (set behind the barrier after pass 0; stride 1: none)
@@ -350,6 +404,17 @@ __device__ __forceinline__ void shade_body(const int b, const int bxi, const int
             const size_t off = bin_off + poff;
             const float rf = (float)ld32(a.ref + bin_off, poff);
             const float d0 = rf - bgs;
+            // WGT: the pixel's weight w and what its background term weighed, w0 * rho(d0) (the same for every channel)
+            float wpx = 1.0f, w0rho = 0.0f;
+            if (WGT) {
+                const float wm = mask_weight(wa, wa->mask + bin_off, poff, rf);
+                const float w0 = wm * wa->w_outside;
+                wpx = wm * face_weight(wa, t);
+                wacc += wpx - w0;
+                float rho0, psi0;
+                rho_psi(wa, d0, rho0, psi0);
+                w0rho = w0 * rho0;
+            }
             float colv[CS], gq[CS];
             float gfx = 0.f, gfy = 0.f;
             bool nz = false;
@@ -375,8 +440,15 @@ __device__ __forceinline__ void shade_body(const int b, const int bxi, const int
                 // background elsewhere (fit.py:161); squared error against the 8-bit reference (fit.py:579), as the difference to a
                 // background pixel (the all-background share of the loss depends on the references alone: fpcdr_ref_bg_sumsq)
                 const float dd = rf - colv[c] * cs;
+                if (WGT) {
+                    float rho, psi;
+                    rho_psi(wa, dd, rho, psi);
+                    lsum += wpx * rho - w0rho;
+                    gq[c] = (-2.0f * cs * gs) * (wpx * psi);      // (= loss_grad_w: the expression k_fix<1> takes away again)
+                } else {
                 lsum += dd * dd - d0 * d0;
                 gq[c] = loss_grad(dd, cs, gs);
+                }
                 nz |= gq[c] != 0.0f;
                 gfx += gq[c] * ((t10 - t00) * (1.0f - tp.fy) + (t11 - t01) * tp.fy);
                 gfy += gq[c] * ((t01 + (t11 - t01) * tp.fx) - (t00 + (t10 - t00) * tp.fx));
@@ -666,6 +738,10 @@ __device__ __forceinline__ void shade_body(const int b, const int bxi, const int
 
     lsum = wave_sum_dpp(lsum);
     if (lane == 0) s_lpart[wave] = lsum;
+    if (WGT) {
+        wacc = wave_sum_dpp(wacc);
+        if (lane == 0) s_lpart[ONT / 64 + wave] = wacc;
+    }
     OPROF_T(5);
     const bool bin_def = block4_any(s_vote + 4, any_def);
     OPROF_T(6);
@@ -682,6 +758,10 @@ __device__ __forceinline__ void shade_body(const int b, const int bxi, const int
         const double tot = (double)s_lpart[0] + (double)s_lpart[1] + (double)s_lpart[2] + (double)s_lpart[3];
         const unsigned int slot = ((unsigned int)bxi + 31u * (unsigned int)byi + 977u * (unsigned int)b) % FPCDR_LOSS_SLOTS;
         if (tot != 0.0) atomicAdd(ke->loss_sum + slot, tot);
+        if (WGT) {
+            const double totw = (double)s_lpart[4] + (double)s_lpart[5] + (double)s_lpart[6] + (double)s_lpart[7];
+            if (totw != 0.0) atomicAdd(wa->wsum + slot % WSLOTS, (double)CS * totw);
+        }
     }
     OPROF_ADD(0, 0, 1); OPROF_ADD(1, 1, 2); OPROF_ADD(2, 2, 3); OPROF_ADD(3, 3, 4); OPROF_ADD(4, 4, 5); OPROF_ADD(5, 5, 6);
     if (!want_grad) return;
@@ -733,6 +813,29 @@ __global__ void __launch_bounds__(ONT) FPCDR_SHADE_WPE k_shade_list(const ShadeK
     int b, byi, bxi;
     fpcdr_decode_bin(lin, k.dc, b, byi, bxi);
     shade_body<CS, BMODE>(b, bxi, byi, k.OX, k.OY, k.a, kernarg_objargs<ShadeK>());
+}
+
+// the WEIGHTED instantiations: the weights as a kernel parameter of their own; one wave a SIMD less than the plain kernel is theirs to take
+#define FPCDR_SHADE_W_WPE __attribute__((amdgpu_waves_per_eu(CS == 1 ? 6 : 1, 8)))
+template <int CS, int BMODE>
+__global__ void __launch_bounds__(ONT) FPCDR_SHADE_W_WPE k_shade_list_w(const ShadeK k, const WgtO wa) {
+    const int item = fpcdr_list_item(*k.count, k.cap);
+    if (item < 0) return;
+    const int lin = __builtin_amdgcn_readfirstlane(k.list[item]);
+    int b, byi, bxi;
+    fpcdr_decode_bin(lin, k.dc, b, byi, bxi);
+    shade_body<CS, BMODE, false, true>(b, bxi, byi, k.OX, k.OY, k.a, kernarg_objargs<ShadeK>(), nullptr, &wa);
+}
+template <int CS>
+__global__ void __launch_bounds__(ONT) k_shade_queue_w(const ShadeK k, const WgtO wa) {
+    const int n = *k.count;
+    for (int item = k.cap + blockIdx.x; item < n; item += gridDim.x) {
+        const int lin = __builtin_amdgcn_readfirstlane(k.list[item]);
+        int b, byi, bxi;
+        fpcdr_decode_bin(lin, k.dc, b, byi, bxi);
+        shade_body<CS, -1, false, true>(b, bxi, byi, k.OX, k.OY, k.a, kernarg_objargs<ShadeK>(), nullptr, &wa);
+        __syncthreads();
+    }
 }
 
 // the MIP instantiation (boundary mode at run time): list form and strided sweep
@@ -823,9 +926,9 @@ __device__ __noinline__ void aa_edge_pos_grad(float *gp, int *vkeys, double *vac
     hacc_vadd(gp, vkeys, vacc, vb, g_qbx * hw, g_qby * hh, g_wb - fxp * g_qbx - fyp * g_qby);
 }
 
-template <int CS, int PASS, bool MIP = false>
+template <int CS, int PASS, bool MIP = false, bool WGT = false>
 __device__ __forceinline__ void fix_body(const int b, const int bxi, const int byi, const int OX, const int OY, const ObjArgs &a,
-                                         const MipO *ma = nullptr) {
+                                         const MipO *ma = nullptr, const WgtO *wa = nullptr) {
     __shared__ unsigned int s_mask[OB];
     __shared__ unsigned short s_list[OB * OB];
     __shared__ int s_n;
@@ -1018,16 +1121,39 @@ __device__ __forceinline__ void fix_body(const int b, const int bxi, const int b
 #pragma unroll
             for (int c = 0; c < CS; ++c) { acc[c] += cme[c]; if (PASS == 1) go[c] += a.g_aa[ro * CS + c]; }
             const float rf = (float)a.ref[off];
+            // WGT: the weight k_shade gave this pixel, by the same expressions
+            float wpx = 1.0f, wmx = 1.0f;
+            if (WGT) {
+                wmx = wa->mask ? (float)wa->mask[off] * (1.0f / 255.0f) : 1.0f;
+                if (wa->sat > 0 && rf >= (float)wa->sat) wmx = 0.0f;
+                wpx = wmx * face_weight(wa, (int)(me & 0xffffffu) - 1);
+            }
             if (PASS == 0) {
                 if (hit_any) {      // the antialiased colour replaces the plain one in this pixel's loss term and gradient
                     atomicOr(a.hitmask + bin_lin * OB + (pix >> 5), 1u << (pix & 31));
                     const float d0 = rf - bgs;
+                    float w0rho = 0.0f;
+                    if (WGT) {
+                        float rho0, psi0;
+                        rho_psi(wa, d0, rho0, psi0);
+                        w0rho = (wmx * wa->w_outside) * rho0;
+                    }
 #pragma unroll
                     for (int c = 0; c < CS; ++c) {
                         const float dn = rf - acc[c] * cs, dd = rf - cme[c] * cs;
+                        if (WGT) {
+                            // (the two terms in k_shade's form, background share and all: neutral weights give the plain kernel's bits)
+                            float rn, pn, rd, pd;
+                            rho_psi(wa, dn, rn, pn);
+                            rho_psi(wa, dd, rd, pd);
+                            lsum += wpx * rn - w0rho;
+                            lsum -= wpx * rd - w0rho;
+                            a.g_aa[ro * CS + c] = loss_grad_w(wa, wpx, dn, cs, gs);
+                        } else {
                         lsum += dn * dn - d0 * d0;
                         lsum -= dd * dd - d0 * d0;
                         a.g_aa[ro * CS + c] = loss_grad(dn, cs, gs);
+                        }
                     }
                 }
             } else {
@@ -1035,7 +1161,10 @@ __device__ __forceinline__ void fix_body(const int b, const int bxi, const int b
                 float dl[CS];
                 bool nz = false;
 #pragma unroll
-                for (int c = 0; c < CS; ++c) { dl[c] = go[c] - loss_grad(rf - cme[c] * cs, cs, gs); nz |= dl[c] != 0.0f; }
+                for (int c = 0; c < CS; ++c) {
+                    dl[c] = go[c] - (WGT ? loss_grad_w(wa, wpx, rf - cme[c] * cs, cs, gs) : loss_grad(rf - cme[c] * cs, cs, gs));
+                    nz |= dl[c] != 0.0f;
+                }
                 if (nz && MIP) {
                     // the mip-mapped lookup (fit.py:153-155): footprint from the rasteriser's derivatives (recomputed), texel gradients of
                     // every level straight to memory (a few dozen pixels per bin), the footprint's gradient back through the derivatives
@@ -1284,6 +1413,29 @@ __global__ void __launch_bounds__(FNT) k_fix_list(const int32_t *__restrict__ li
     fpcdr_decode_bin(lin, dc, b, byi, bxi);
     fix_body<CS, PASS>(b, bxi, byi, OX, OY, a);
 }
+// the WEIGHTED instantiations
+template <int CS, int PASS>
+__global__ void __launch_bounds__(FNT) k_fix_list_w(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int cap, int OX, int OY,
+                                                    fpcdr_bin_decode dc, ObjArgs a, WgtO wa) {
+    const int item = fpcdr_list_item(*count, cap);
+    if (item < 0) return;
+    const int lin = __builtin_amdgcn_readfirstlane(list[item]);
+    int b, byi, bxi;
+    fpcdr_decode_bin(lin, dc, b, byi, bxi);
+    fix_body<CS, PASS, false, true>(b, bxi, byi, OX, OY, a, nullptr, &wa);
+}
+template <int CS, int PASS>
+__global__ void __launch_bounds__(FNT) k_fix_queue_w(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int first, int OX, int OY,
+                                                     fpcdr_bin_decode dc, ObjArgs a, WgtO wa) {
+    const int n = *count;
+    for (int item = first + blockIdx.x; item < n; item += gridDim.x) {
+        const int lin = __builtin_amdgcn_readfirstlane(list[item]);
+        int b, byi, bxi;
+        fpcdr_decode_bin(lin, dc, b, byi, bxi);
+        fix_body<CS, PASS, false, true>(b, bxi, byi, OX, OY, a, nullptr, &wa);
+        __syncthreads();
+    }
+}
 template <int CS, int PASS>
 __global__ void __launch_bounds__(FNT) k_fix_queue(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int first, int OX, int OY,
                                                    fpcdr_bin_decode dc, ObjArgs a) {
@@ -1347,7 +1499,8 @@ extern "C" int fpcdr_silhouette_bits(const float *pos, const int32_t *tri, const
     return fpcdr_launch_sil(pos, tri, adj, B, V, T, H, W, sil, nullptr, 0, (hipStream_t)stream);
 }
 
-extern "C" int fpcdr_objective_fwd(const fpcdr_objective_params *p, void *stream) {
+// the call of both entries; wgt: the weighted form's kernel parameter (checked by its entry), or null
+static int fpcdr_objective_fwd_impl(const fpcdr_objective_params *p, const WgtO *wgt, void *stream) {
     FPCDR_REQUIRE(p != nullptr, "null params");
     FPCDR_REQUIRE(p->pos && p->tri && p->adj && p->scratch && p->uv && p->uv_tri && p->tex && p->ref, "null pointer");
     FPCDR_REQUIRE(p->sil && p->idp && p->occ && p->cmask && p->empty_color && p->loss_sum, "null pointer");
@@ -1390,6 +1543,7 @@ extern "C" int fpcdr_objective_fwd(const fpcdr_objective_params *p, void *stream
         if (p->mip && p->grad_tex)
             for (int lvl = 1; lvl <= p->n_levels; ++lvl) zl.add(p->grad_tex_mip[lvl - 1], (long long)(p->Ht >> lvl) * (p->Wt >> lvl) * p->C);
     }
+    if (wgt) zl.add(wgt->wsum, (long long)WSLOTS * 2);
     if (p->zero_extra) {
         FPCDR_REQUIRE(p->zero_extra_bytes >= 0 && (p->zero_extra_bytes & 3) == 0 && ((size_t)p->zero_extra & 3) == 0, "zero_extra: 4-byte units");
         zl.add(p->zero_extra, p->zero_extra_bytes / 4);
@@ -1440,6 +1594,38 @@ extern "C" int fpcdr_objective_fwd(const fpcdr_objective_params *p, void *stream
     do {                                                                                                                          \
         if (fin.esum || fin.value_out || fin.counts_out || fin.skip_out) hipLaunchKernelGGL(k_objective_finish<CS>, dim3(1), dim3(64), 0, st, a, fin); \
     } while (0)
+    if (wgt) {      // the weighted instantiations (no mip: refused by the entry)
+        const WgtO wa = *wgt;
+#define SHADE_W(CS, BM)                                                                                                           \
+    do {                                                                                                                          \
+        hipLaunchKernelGGL((k_shade_list_w<CS, BM>), grid, dim3(ONT), 0, st, shade_k, wa);                                         \
+        if (sweep) hipLaunchKernelGGL(k_shade_queue_w<CS>, dim3(FPCDR_SWEEP_WGS), dim3(ONT), 0, st, shade_k, wa);                  \
+    } while (0)
+#define FIX_W(CS, PASS)                                                                                                           \
+    do {                                                                                                                          \
+        hipLaunchKernelGGL((k_fix_list_w<CS, PASS>), grid_d, dim3(FNT), 0, st, a.def_list, a.def_count, cap_d, OX, OY, dc, a, wa); \
+        if (sweep_d) hipLaunchKernelGGL((k_fix_queue_w<CS, PASS>), dim3(FPCDR_SWEEP_WGS), dim3(FNT), 0, st, a.def_list, a.def_count, cap_d, OX, OY, dc, a, wa); \
+    } while (0)
+        if (p->C == 1) {
+            if (p->boundary_mode == FPCDR_BOUNDARY_WRAP && p->tri_uv) SHADE_W(1, FPCDR_BOUNDARY_WRAP);
+            else SHADE_W(1, -1);
+            FIX_W(1, 0);
+            if (grads) FIX_W(1, 1);
+            FINISH(1);
+        } else if (p->C == 3) {
+            SHADE_W(3, -1);
+            FIX_W(3, 0);
+            if (grads) FIX_W(3, 1);
+            FINISH(3);
+        } else {
+            SHADE_W(4, -1);
+            FIX_W(4, 0);
+            if (grads) FIX_W(4, 1);
+            FINISH(4);
+        }
+#undef SHADE_W
+#undef FIX_W
+    } else
     if (p->mip) {      // the reference's enable_mip branch (fit.py:153-155)
         MipO ma;
         ma.lv.tex[0] = p->tex;
@@ -1490,3 +1676,20 @@ extern "C" int fpcdr_objective_fwd(const fpcdr_objective_params *p, void *stream
     return FPCDR_OK;
 }
 
+extern "C" int fpcdr_objective_fwd(const fpcdr_objective_params *p, void *stream) { return fpcdr_objective_fwd_impl(p, nullptr, stream); }
+
+extern "C" int fpcdr_objective_weighted_fwd(const fpcdr_objective_weighted_params *p, void *stream) {
+    FPCDR_REQUIRE(p != nullptr, "null params");
+    FPCDR_REQUIRE(!p->base.mip, "the mip branch has no weighted form (base.mip must be 0)");
+    FPCDR_REQUIRE(p->kind == FPCDR_ROBUST_L2 || p->kind == FPCDR_ROBUST_CHARBONNIER || p->kind == FPCDR_ROBUST_GEMAN_MCCLURE,
+                  "kind must be FPCDR_ROBUST_L2, _CHARBONNIER or _GEMAN_MCCLURE");
+    FPCDR_REQUIRE(p->kind == FPCDR_ROBUST_L2 || (std::isfinite(p->inv_c) && p->inv_c > 0.0f),
+                  "inv_c = 1 / scale must be finite and positive for a kind other than L2");
+    FPCDR_REQUIRE(std::isfinite(p->w_outside) && p->w_outside >= 0.0f, "w_outside must be finite and not negative");
+    FPCDR_REQUIRE(p->sat >= 0 && p->sat <= 255, "sat must lie in 0 .. 255 (0: off)");
+    FPCDR_REQUIRE(!p->face_w || p->T_weights > 0, "face_w needs T_weights > 0");
+    FPCDR_REQUIRE(p->wsum != nullptr, "null wsum");
+    FPCDR_REQUIRE(((uintptr_t)p->wsum & 7) == 0 && ((uintptr_t)p->face_w & 3) == 0, "a misaligned buffer");
+    const WgtO wa = {p->mask, p->face_w, p->face_w ? p->T_weights : 0, p->kind, p->inv_c, p->w_outside, p->sat, p->wsum};
+    return fpcdr_objective_fwd_impl(&p->base, &wa, stream);
+}

@@ -25,6 +25,7 @@
 // Constant indices only: no private segment.
 #include "u8_chunk.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace {
@@ -149,7 +150,83 @@ __global__ void __launch_bounds__(256) k_robust_loss(const float *__restrict__ c
     }
 }
 
+// The all-background share of the WEIGHTED one-pass objective (objective.hip; DESIGN.md 3, "Weighted objective rule"): an empty pixel
+// always shows the background, so its term w0 * rho(ref - bg_scaled), w0 = wm * w_outside, depends on the capture and the mask alone.  Per
+// image (gridDim.y) the sums of w0 * rho and of w0.  A thread owns chunks of 16 consecutive pixels, read in the two forms of u8_chunk.h;
+// lane sums in float32 -> wave -> block -> one float64 atomic per sum and workgroup, as above.  Constant indices only: no private segment.
+template <int KIND>
+__global__ void __launch_bounds__(256) k_robust_bg(const uint8_t *__restrict__ ref, const uint8_t *__restrict__ mask, long long px, float bgs,
+                                                   float inv_c, float w_outside, int sat, double *__restrict__ out) {
+    __shared__ float s_part[2][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint8_t *r = ref + (size_t)blockIdx.y * px;
+    const uint8_t *m = mask ? mask + (size_t)blockIdx.y * px : nullptr;
+    const long long n_chunks = (px + 15) / 16;
+    float acc_rho = 0.0f, acc_w = 0.0f;
+    for (long long ch = (long long)blockIdx.x * 256 + threadIdx.x; ch < n_chunks; ch += (long long)gridDim.x * 256) {
+        const long long j0 = ch * 16;
+        const int rem = px - j0 < 16 ? (int)(px - j0) : 16;      // pixels of this chunk inside the image
+        uint32_t rw[4] = {0u, 0u, 0u, 0u}, mw[4] = {0u, 0u, 0u, 0u};
+        load_chunk_u8(r + j0, rem == 16, 0, rem, rw);
+        if (m) load_chunk_u8(m + j0, rem == 16, 0, rem, mw);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if (k >= rem) continue;
+            const uint32_t rb = (rw[k >> 2] >> (8 * (k & 3))) & 255u, mb = (mw[k >> 2] >> (8 * (k & 3))) & 255u;
+            float wm = m ? (float)mb * (1.0f / 255.0f) : 1.0f;
+            if (sat > 0 && (int)rb >= sat) wm = 0.0f;
+            const float w0 = wm * w_outside;
+            const float d = (float)rb - bgs;
+            const float dd = d * d;
+            float rho = dd;
+            if (KIND != FPCDR_ROBUST_L2) {
+                const float z = d * inv_c;
+                const float t = z * z;
+                if (KIND == FPCDR_ROBUST_CHARBONNIER) rho = (2.0f * dd) / (1.0f + sqrtf(1.0f + t));
+                else rho = dd / (1.0f + t);
+            }
+            acc_rho += w0 * rho;
+            acc_w += w0;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        acc_rho += __shfl_xor(acc_rho, o, 64);
+        acc_w += __shfl_xor(acc_w, o, 64);
+    }
+    if (lane == 0) {
+        s_part[0][wave] = acc_rho;
+        s_part[1][wave] = acc_w;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(out + 2 * (size_t)blockIdx.y, (double)s_part[0][0] + (double)s_part[0][1] + (double)s_part[0][2] + (double)s_part[0][3]);
+        atomicAdd(out + 2 * (size_t)blockIdx.y + 1, (double)s_part[1][0] + (double)s_part[1][1] + (double)s_part[1][2] + (double)s_part[1][3]);
+    }
+}
+
 }  // namespace
+
+extern "C" int fpcdr_ref_bg_wsum(const uint8_t *ref, const uint8_t *mask, int64_t n_images, int64_t px_per_image, float bg_scaled, int32_t kind,
+                                 float inv_c, float w_outside, int32_t sat, double *out, void *stream) {
+    FPCDR_REQUIRE(ref && out, "null pointer");
+    FPCDR_REQUIRE(n_images > 0 && n_images <= 65535 && px_per_image > 0, "bad sizes");
+    FPCDR_REQUIRE(kind == FPCDR_ROBUST_L2 || kind == FPCDR_ROBUST_CHARBONNIER || kind == FPCDR_ROBUST_GEMAN_MCCLURE,
+                  "kind must be FPCDR_ROBUST_L2, _CHARBONNIER or _GEMAN_MCCLURE");
+    FPCDR_REQUIRE(kind == FPCDR_ROBUST_L2 || (std::isfinite(inv_c) && inv_c > 0.0f),
+                  "inv_c = 1 / scale must be finite and positive for a kind other than L2");
+    FPCDR_REQUIRE(std::isfinite(w_outside) && w_outside >= 0.0f, "w_outside must be finite and not negative");
+    FPCDR_REQUIRE(sat >= 0 && sat <= 255, "sat must lie in 0 .. 255 (0: off)");
+    FPCDR_REQUIRE(((uintptr_t)out & 7) == 0, "a misaligned buffer");
+    const long long n_chunks = ((long long)px_per_image + 15) / 16;
+    const unsigned blocks = (unsigned)std::min<long long>(64, (n_chunks + 255) / 256);      // (a thread: at least one chunk, up to 64 workgroups an image)
+    auto kern = kind == FPCDR_ROBUST_L2 ? k_robust_bg<FPCDR_ROBUST_L2>
+              : kind == FPCDR_ROBUST_CHARBONNIER ? k_robust_bg<FPCDR_ROBUST_CHARBONNIER> : k_robust_bg<FPCDR_ROBUST_GEMAN_MCCLURE>;
+    hipLaunchKernelGGL(kern, dim3(blocks, (unsigned)n_images), dim3(256), 0, (hipStream_t)stream, ref, mask, (long long)px_per_image, bg_scaled,
+                       inv_c, w_outside, sat, out);
+    FPCDR_CHECK_LAUNCH();
+    return FPCDR_OK;
+}
 
 extern "C" int fpcdr_robust_loss(const fpcdr_robust_loss_params *p, void *stream) {
     FPCDR_REQUIRE(p != nullptr, "null params");

@@ -367,6 +367,17 @@ def pixel_term(cfg, i, weighted=False):
     return ('robust', 'l2', None) if weighted else None
 
 
+def weighted_one_pass_term(cfg, term, mip, channels=1):
+    """Whether an iteration whose pixel term is `term` (pixel_term's answer) runs the WEIGHTED one-pass objective ("Weighted
+    objective rule"; ops.pixel_objective with weights) instead of render_from_clip + pixel_loss_robust: cfg.weighted_one_pass is set, the
+    term is the robust one, every flag of the one-pass step is on (fused_objective, fused_render, fused_loss, one_pass, sparse_objective),
+    the shading is the texture's with 1, 3 or 4 `channels`, and the active level runs without mip (`mip`: the level's enable_mip -- a
+    pyramid level under pyramid_mip, the cheap levels, stays on the operator path).  Needs no GPU."""
+    return bool(cfg.weighted_one_pass and term is not None and term[0] == 'robust' and cfg.fused_objective and cfg.fused_render
+                and cfg.fused_loss and cfg.one_pass and cfg.sparse_objective and cfg.shading == 'texture' and channels in (1, 3, 4)
+                and not mip)
+
+
 def pixel_term_loss(term, colour, rast_out, ref_u8, n_total, **weights):
     """(sums f64, d mean / d colour) of `term` (pixel_term's answer; None: the plain L2); weights: pixel_loss_robust's keyword arguments."""
     if term is None:
@@ -736,6 +747,11 @@ class FitConfig:
                                     # != 1 -- makes the iteration run render_from_clip + pixel_loss_robust in the place of the one-pass
                                     # objective (kind 'l2' when only weights are on).  Not together with blur_sigma > 0 or norm_sigma > 0,
                                     # nor with hip_graph (ValueError).  All off: a step is exactly the path it was
+    weighted_one_pass: bool = False # an iteration on the robust term runs the WEIGHTED ONE-PASS objective ("Weighted objective
+                                    # rule") where it can -- fused_objective, fused_render, fused_loss, one_pass, sparse_objective, texture
+                                    # shading, a level without mip (fit.weighted_one_pass_term) -- and the operator path elsewhere: the same
+                                    # term, the image never in memory.  False: the operator path everywhere, as it was.  hip_graph with
+                                    # weights keeps raising
     log_interval: int = 0           # every n steps one JSON line {it, loss, lr, frames_per_s} (reference print, fit.py:621-623); an
                                     # iteration on the robust term adds "wsum", the sum of its weights over rank 0's batch
     reg_log_interval: int = 500     # every n steps the regulariser breakdown MEL / LAP / MNC (reference fit.py:597-601)
@@ -941,6 +957,8 @@ class Fitter:
                 raise ValueError(f"the masks {tuple(self.masks.shape)} do not match the targets {tuple(self.targets.shape)}")
         self.full_masks = self.masks
         self._wsum = None                     # (the sum of the weights of the last iteration on the robust term, for the step log)
+        self._bg_wsum_key = None
+        self._bg_wsum = {}                    # weighted one-pass: (level, kind, scale) -> [F_local * n_cam, 2] f64, cached like target_bg_sumsq
         # ---- pyramid levels: per factor in use (targets, (H, W), target_bg_sumsq, masks), each made from this rank's full-size targets ----
         self._levels, self._level = None, 1
         if self._pyramid:
@@ -1085,6 +1103,16 @@ class Fitter:
                 return s
             i -= n
         return 1
+
+    def _level_bg_wsum(self, kind, scale):
+        """[F_local * n_cam, 2] f64: per image of the active level, the all-background share of the weighted one-pass objective of (kind,
+        scale) and of its weights (ops.reference_background_weighted) -- made once per level and kind, as target_bg_sumsq is per level."""
+        key = (self._level, kind, scale)
+        if key not in self._bg_wsum:
+            masks = self.masks.reshape(-1, *self.resolution) if self.masks is not None else None
+            self._bg_wsum[key] = dr.reference_background_weighted(self.targets.reshape(-1, *self.resolution), masks, kind, scale,
+                                                                  self.cfg.weight_outside, self.cfg.saturation, BACKGROUND)
+        return self._bg_wsum[key]
 
     def _set_level(self, s):
         """Make the level of factor s the active one: `resolution`, `targets`, `target_bg_sumsq` and `enable_mip` are that level's, and the
@@ -1377,9 +1405,10 @@ class Fitter:
         # (the mip branch of the reference's render(), fit.py:153-155, runs inside the same kernels)
         one_shot = (cfg.fused_objective and cfg.fused_render and cfg.fused_loss and C in (1, 3, 4) and cfg.shading == 'texture'
                     and (not mip or cfg.sparse_objective))
-        term = pixel_term(cfg, i, self._weighted)      # a windowed or a weighted loss needs the image in memory: the operator path
-        one_shot = one_shot and term is None
-        robust = term is not None and term[0] == 'robust'
+        term = pixel_term(cfg, i, self._weighted)      # a windowed loss needs the image in memory: the operator path; so does a weighted
+        robust = term is not None and term[0] == 'robust'      # one, unless the weighted one-pass objective takes it
+        weighted_shot = weighted_one_pass_term(cfg, term, mip, C)
+        one_shot = one_shot and (term is None or weighted_shot)
         # one flat buffer for the small accumulators of this step's backward kernels, zero-filled by the objective's first kernel; the
         # pool around it goes to the functions whose backward takes views of it
         zero_buf, pool = None, None
@@ -1430,7 +1459,7 @@ class Fitter:
         self.optimizer.zero_grad(set_to_none=True)
         if one_shot:
             bg_sum = None
-            if cfg.sparse_objective:
+            if cfg.sparse_objective and not weighted_shot:
                 bg = self.target_bg_sumsq.reshape(-1)
                 if isinstance(rows, slice):      # the whole shard, every view: the same number every step
                     if self._bg_sum_key != rows:
@@ -1440,12 +1469,26 @@ class Fitter:
                     bg = bg.index_select(0, rows)
                     bg_sum = bg.reshape(()) if bg.numel() == 1 else bg.sum()
             self._skip_cur = self._skip_target() if (cfg.one_pass and cfg.sparse_objective) else None
+            wkw = {}
+            if weighted_shot:      # the same weights pixel_loss_robust takes, and the level's all-background share of this term
+                mask = self._take(self.masks.reshape(-1, *self.resolution), 0, rows) if self.masks is not None else None
+                bgw = self._level_bg_wsum(term[1], term[2])
+                if isinstance(rows, slice):      # the whole shard, every view: the same two numbers every step of this level and kind
+                    key = (self._level, term[1], term[2], rows.start, rows.stop)
+                    if self._bg_wsum_key != key:
+                        self._bg_wsum_key, self._bg_wsum_all = key, bgw[rows].sum(0)
+                    bgw = self._bg_wsum_all
+                else:
+                    bgw = bgw.index_select(0, rows).sum(0)
+                sums = (None, torch.empty(1, dtype=torch.float64, device=self.device))
+                wkw = dict(robust=(term[1], term[2]), mask=mask, face_weights=self.face_w, weight_outside=cfg.weight_outside,
+                           saturation=cfg.saturation, ref_bg_wsum=bgw, wsum_out=sums[1], check_weights=False)
             pix = dr.pixel_objective(self.glctx, pos_clip, self.pos_idx, self.uv, self.uv_idx, self.tex_opt, ref, self.resolution,
                                      n_total, BACKGROUND, sparse=cfg.sparse_objective, ref_bg_sumsq=bg_sum,
                                      enable_mip=mip, max_mip_level=cfg.max_mip_level,
                                      queued_backward=cfg.queued_backward and not self.use_graph,
                                      one_pass=cfg.one_pass, unit_upstream=True, zero_extra=zero_buf,      # (the seeds below are 1)
-                                     skip_out=self._skip_cur)
+                                     skip_out=self._skip_cur, **wkw)
             self._backward(pix, self._one, reg, *terms)
             value = pix.detach()
         elif cfg.fused_loss:
@@ -1471,7 +1514,7 @@ class Fitter:
             loss = value + reg.detach() if (chained or not one_shot) else value
             for t in terms:
                 loss = loss + t.detach()
-        self._wsum = sums[1] if robust else None      # (the sum of the weights of an iteration on the robust term, for the step log)
+        self._wsum = sums[1].reshape(()) if robust else None      # (the sum of the weights of an iteration on the robust term, for the step log)
         self._store_result(frame_ids, vtx_pos.detach())
         return loss.detach()
 

@@ -519,7 +519,7 @@ class _pixel_objective_onepass(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, tex, tri, adj, uv, uv_tri, ref, H, W, n_total, bg, boundary, ref_bg_sumsq, use_hints, want_grad, unit_upstream,
                 flags_out=None, mip_levels=None, zero_extra=None, bin_lists=True, idp_out=None, record_slots=None,
-                skip_out=None):
+                skip_out=None, weights=None):
         lib = _lib.load()
         B, V, _ = pos.shape
         T = tri.shape[0]
@@ -607,13 +607,27 @@ class _pixel_objective_onepass(torch.autograd.Function):
         g_aa = torch.empty(n_rec, C, dtype=torch.float32, device=dev)
         p.rec, p.color, p.grad_aa = _ptr(rec), _ptr(color), _ptr(g_aa)
         # the value from the call's last kernel: (loss slots + C * background share) / n_total
-        bg_sum = (reference_background_sumsq(ref, bg).sum() if ref_bg_sumsq is None
-                  else torch.as_tensor(ref_bg_sumsq, device=dev)).to(torch.float64).contiguous()
+        if weights is None:
+            bg_sum = (reference_background_sumsq(ref, bg).sum() if ref_bg_sumsq is None
+                      else torch.as_tensor(ref_bg_sumsq, device=dev)).to(torch.float64).contiguous()
+        else:      # (the weighted background share: [2] = sum of w0 * rho(d0), sum of w0 over the call's images; the kernel reads [0])
+            bg_sum = weights['bg']
         out = torch.empty((), dtype=torch.float32, device=dev)
         p.bg_sumsq, p.bg_coeff, p.n_total, p.value_out = _ptr(bg_sum), float(C), float(n_total), _ptr(out)
         if zero_extra is not None:      # (a caller's own small accumulators, zero-filled by the call's first kernel)
             p.zero_extra, p.zero_extra_bytes = _ptr(zero_extra), zero_extra.numel() * zero_extra.element_size()
-        _lib.call("fpcdr_objective_fwd", ctypes.byref(p), _stream())
+        if weights is None:
+            _lib.call("fpcdr_objective_fwd", ctypes.byref(p), _stream())
+        else:
+            # the weighted instantiations of the same kernels ("Weighted objective rule"); the counting call above is the plain one
+            wslots = torch.empty(_lib.WSUM_SLOTS, dtype=torch.float64, device=dev)      # (zero-filled by the call's first kernel)
+            face_w = weights['face_w']
+            pw = _lib.ObjectiveWeighted(base=p, kind=weights['kind'], inv_c=weights['inv_c'], w_outside=weights['w_outside'], sat=weights['sat'],
+                                        T_weights=0 if face_w is None else int(face_w.shape[0]), mask=_ptr(weights['mask']), face_w=_ptr(face_w),
+                                        wsum=_ptr(wslots))
+            _lib.call("fpcdr_objective_weighted_fwd", ctypes.byref(pw), _stream())
+            if weights['wsum_out'] is not None:      # the sum of all weights: the covered pixels' w - w0 and the all-background share
+                weights['wsum_out'].reshape(-1)[:1].copy_((wslots.sum() + float(C) * bg_sum[1]).reshape(1))
         if g_chain:
             _fold_mip_grads([g_tex[None]] + g_chain)
         ctx.save_for_backward(*(t for t in (g_pos, g_tex) if t is not None))
@@ -632,7 +646,7 @@ class _pixel_objective_onepass(torch.autograd.Function):
             g = g.to(torch.float32)
             g_pos = g_pos * g if g_pos is not None else None
             g_tex = g_tex * g if g_tex is not None else None
-        return (g_pos if ctx.needs_input_grad[0] else None, g_tex if ctx.needs_input_grad[1] else None) + (None,) * 21
+        return (g_pos if ctx.needs_input_grad[0] else None, g_tex if ctx.needs_input_grad[1] else None) + (None,) * 22
 
 
 def reference_background_sumsq(ref_u8, background=45.0 / 255.0):
@@ -644,6 +658,26 @@ def reference_background_sumsq(ref_u8, background=45.0 / 255.0):
     out = torch.zeros(ref_u8.shape[0], dtype=torch.float64, device=ref_u8.device)
     _lib.call("fpcdr_ref_bg_sumsq", _ptr(ref_u8), ref_u8.shape[0], ref_u8.shape[1] * ref_u8.shape[2], float(background) * 255.0,
               _ptr(out), _stream())
+    return out
+
+
+def reference_background_weighted(ref_u8, mask=None, kind='l2', scale=None, weight_outside=1.0, saturation=0, background=45.0 / 255.0):
+    """Per image (sum over pixels of w0 * rho(ref - 255 * background), sum of w0), w0 = wm * weight_outside with wm from the mask byte
+    and the saturation level ("Weighted objective rule"; fpcdr_ref_bg_wsum): f64 [B,2].  The weighted one-pass objective's
+    share of an image that shows nothing but background -- it depends on the captures and the masks alone, so a fit loop computes it once
+    per kind and hands its sum over a call's images to pixel_objective(ref_bg_wsum=...).  mask: uint8 [B,H,W] or None."""
+    kind_no, inv_c, weight_outside, saturation = robust_args(kind, scale, weight_outside, saturation)
+    _check_tensor('ref_u8', ref_u8, torch.uint8, 3)
+    ref_u8 = ref_u8.contiguous()
+    if mask is not None:
+        _check_tensor('mask', mask, torch.uint8, 3)
+        if tuple(mask.shape) != tuple(ref_u8.shape) or mask.device != ref_u8.device:
+            raise ValueError(f"mask must be [B,H,W] = {tuple(ref_u8.shape)} on the device of ref_u8 (got {tuple(mask.shape)})")
+        mask = mask.contiguous()
+    with torch.cuda.device(ref_u8.device):
+        out = torch.zeros(ref_u8.shape[0], 2, dtype=torch.float64, device=ref_u8.device)
+        _lib.call("fpcdr_ref_bg_wsum", _ptr(ref_u8), _ptr(mask), ref_u8.shape[0], ref_u8.shape[1] * ref_u8.shape[2], float(background) * 255.0,
+                  kind_no, inv_c, weight_outside, saturation, _ptr(out), _stream())
     return out
 
 
@@ -1170,7 +1204,8 @@ def downsample_images(images, factor):
 def pixel_objective(glctx, pos, tri, uv, uv_tri, tex, ref_u8, resolution, n_total=None, background=45.0 / 255.0,
                     boundary_mode='wrap', sparse=True, ref_bg_sumsq=None, launch_hints=True, queued_backward=False,
                     enable_mip=False, max_mip_level=None, one_pass=True, unit_upstream=False, aa_flags_out=None, zero_extra=None,
-                    id_plane_out=None, record_slots=None, skip_out=None):
+                    id_plane_out=None, record_slots=None, skip_out=None, robust=None, mask=None, face_weights=None, weight_outside=1.0,
+                    saturation=0, ref_bg_wsum=None, wsum_out=None, check_weights=True):
     """The whole pixel term of the reference's loss (fit.py:151-161 + the first term of :579) for a minibatch,
     as three kernels:  mean((ref - 255 * where(rast.w > 0, antialias(texture(interpolate(rasterize(pos)))), bg))^2)
     over n_total elements (default: all of this call's).  pos [B,V,4], tex [Ht,Wt,C] (C in 1,3,4), ref_u8 [B,H,W] uint8.
@@ -1197,7 +1232,16 @@ def pixel_objective(glctx, pos, tri, uv, uv_tri, tex, ref_u8, resolution, n_tota
     skip_out (one_pass): a one-element float32 device tensor that receives 1.0 when the call ran out of record slots -- its value is then
     NaN and its gradients are incomplete -- and 0.0 otherwise, written by the call's last kernel: hand it to GroupedAdam.skip_flag (summed
     over the ranks under data parallelism) and the update of such a step does not happen, without a host read-back.  Without it the
-    NEXT call on the batch shape raises."""
+    NEXT call on the batch shape raises.
+    WEIGHTS (one_pass, sparse, no mip; DESIGN.md 3, "Weighted objective rule"): robust=(kind, scale) -- 'l2' | 'charbonnier' |
+    'geman_mcclure', scale c in grey levels, None for 'l2' --, mask uint8 [B,H,W] (255 = trust, 0 = ignore), face_weights float32 [T]
+    (finite, >= 0; check_weights=False for a caller that has checked them), weight_outside for uncovered pixels, saturation 1..255
+    (capture pixels at or above it count nothing): the term of ops.robust_pixel_loss on the antialiased image, from the weighted
+    instantiations of the same kernels (fpcdr_objective_weighted_fwd) -- the image never exists in memory.  The weights get no gradient;
+    the mean's denominator stays n_total.  ref_bg_wsum: f64 [2] or [B,2], reference_background_weighted(...) of this call's images
+    (summed over them when [B,2]; computed here when None).  wsum_out: a float64 device tensor whose first element receives the sum of
+    all weights of the call (robust_loss_call's sums[1]).  Giving any of these without one_pass and sparse, or with enable_mip, raises
+    ValueError; with none given the call is the plain one."""
     assert isinstance(glctx, RasterizeHipContext)
     _check_tensor('pos', pos, torch.float32, 3)
     _check_tensor('tri', tri, torch.int32, 2)
@@ -1229,11 +1273,50 @@ def pixel_objective(glctx, pos, tri, uv, uv_tri, tex, ref_u8, resolution, n_tota
             raise ValueError("zero_extra must be a contiguous float32 / int32 tensor on the device of pos")
         if not (one_pass and sparse):
             zero_extra.zero_()
+    weighted = (robust is not None or mask is not None or face_weights is not None or float(weight_outside) != 1.0 or saturation != 0
+                or ref_bg_wsum is not None or wsum_out is not None)
+    weights = None
+    if weighted:
+        if not (one_pass and sparse) or enable_mip:
+            raise ValueError("pixel_objective: robust / mask / face_weights / weight_outside / saturation / ref_bg_wsum / wsum_out belong to "
+                             "the one-pass sparse form without mip (use the separate operators and robust_pixel_loss otherwise)")
+        if ref_bg_sumsq is not None:
+            raise ValueError("pixel_objective: a weighted call takes ref_bg_wsum (reference_background_weighted), not ref_bg_sumsq")
+        if robust is not None and not (isinstance(robust, (tuple, list)) and len(robust) == 2):
+            raise ValueError(f"robust must be (kind, scale) (got {robust!r})")
+        kind, scale = robust if robust is not None else ('l2', None)
+        kind_no, inv_c, weight_outside, saturation = robust_args(kind, scale, weight_outside, saturation)
+        ref_u8 = ref_u8.contiguous()
+        if mask is not None:
+            _check_tensor('mask', mask, torch.uint8, 3)
+            if tuple(mask.shape) != tuple(ref_u8.shape) or mask.device != pos.device:
+                raise ValueError(f"mask must be [B,H,W] = {tuple(ref_u8.shape)} on the device of pos (got {tuple(mask.shape)})")
+            mask = mask.contiguous()
+        if face_weights is not None:
+            _check_tensor('face_weights', face_weights, torch.float32, 1)
+            if int(face_weights.shape[0]) != int(tri.shape[0]) or face_weights.device != pos.device:
+                raise ValueError(f"face_weights must have one entry per triangle ({tri.shape[0]}) on the device of pos (got {tuple(face_weights.shape)})")
+            face_weights = face_weights.detach().contiguous()
+            if check_weights and not bool((torch.isfinite(face_weights) & (face_weights >= 0)).all()):
+                raise ValueError("face_weights must be finite and not negative")
+        if wsum_out is not None and not (torch.is_tensor(wsum_out) and wsum_out.dtype == torch.float64 and wsum_out.device == pos.device
+                                         and wsum_out.numel() >= 1 and wsum_out.is_contiguous()):
+            raise ValueError("wsum_out must be a contiguous float64 tensor of at least one element on the device of pos")
+        if ref_bg_wsum is None:
+            bgw = reference_background_weighted(ref_u8, mask, kind, scale, weight_outside, saturation, background).sum(0)
+        else:
+            bgw = torch.as_tensor(ref_bg_wsum, device=pos.device).to(torch.float64)
+            if bgw.dim() == 2:
+                bgw = bgw.sum(0)
+            if tuple(bgw.shape) != (2,):
+                raise ValueError(f"ref_bg_wsum must be [2] or [B,2] (got {tuple(bgw.shape)})")
+        weights = dict(kind=kind_no, inv_c=inv_c, w_outside=weight_outside, sat=saturation, mask=mask, face_w=face_weights,
+                       bg=bgw.contiguous(), wsum_out=wsum_out)
     if one_pass and sparse:
         return _pixel_objective_onepass.apply(pos.contiguous(), tex.contiguous(), tri, adj, uv.contiguous(), uv_tri.contiguous(),
                                               ref_u8.contiguous(), H, W, n_total, background, _lib.BOUNDARY[boundary_mode], ref_bg_sumsq,
                                               bool(launch_hints), torch.is_grad_enabled(), bool(unit_upstream), aa_flags_out, mip_levels, zero_extra,
-                                              True, id_plane_out, record_slots, skip_out)
+                                              True, id_plane_out, record_slots, skip_out, weights)
     if skip_out is not None:
         raise ValueError("skip_out belongs to the one-pass form")
     if record_slots is not None:

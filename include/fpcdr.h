@@ -788,6 +788,51 @@ struct fpcdr_robust_loss_params {
 };
 int fpcdr_robust_loss(const fpcdr_robust_loss_params *p, void *stream);
 
+/* WEIGHTED one-pass objective: the weights and the three kinds of fpcdr_robust_loss inside the kernels of fpcdr_objective_fwd, so that a
+ * fit with masks, face weights, a saturation level, weight_outside != 1 or a robust kind keeps the one-pass step (the operator path writes
+ * the image, rast and the gradient planes to memory and reads them back).  Pure additions: FPCDR_ABI_VERSION stays 16, no existing entry
+ * or struct changes, and the plain kernels contain none of this.  DESIGN.md 3, "Weighted objective rule".  Per pixel and channel, with
+ * rho, psi, wm, w = wm * face_w[id - 1] and w0 = wm * w_outside exactly as above (d0 = ref - color_scale * bg, dd / dn the residual of the
+ * un-antialiased / the blended colour, K = -2 color_scale grad_scale):
+ *   covered pixel            loss_sum += w rho(dd) - w0 rho(d0)          d objective / d colour = K (w psi(dd))
+ *   blended (deferred) pixel loss_sum += w rho(dn) - w rho(dd)           d objective / d antialiased colour = K (w psi(dn))
+ *   value_out = (sum of loss_sum + bg_coeff * bg_sumsq[0]) / n_total,    bg_sumsq[0] = the sum over the call's images of
+ *                                                                        fpcdr_ref_bg_wsum's out[i][0] (an empty pixel always shows
+ *                                                                        the background: its term depends on the capture alone)
+ *   wsum[slot] += C * (w - w0) over the covered pixels: the sum of all weights of the call is
+ *                 sum of the FPCDR_WSUM_SLOTS slots + C * (sum over the call's images of out[i][1])
+ * The weights carry no gradient; the mean's denominator stays n_total.  With kind L2, no mask, no face_w, w_outside 1 and sat 0 every
+ * per-pixel term is fpcdr_objective_fwd's bit for bit.  The mask byte is read where the capture byte is, the face weight is one gather on
+ * the pixel's triangle (an id past T_weights weighs 0).  Everything else -- scratch, hints, records, NaN / skip_out / counts_out on a call
+ * short of record slots, count_only -- is fpcdr_objective_fwd's, through `base`.
+ * Errors, before any launch: what fpcdr_objective_fwd refuses in `base`; base.mip != 0 (the mip branch has no weighted form); an unknown
+ * kind; inv_c not finite or <= 0 for a kind other than L2; w_outside negative or not finite; sat outside 0 .. 255; face_w with
+ * T_weights <= 0 or not 4-byte aligned; wsum NULL or not 8-byte aligned. */
+#define FPCDR_WSUM_SLOTS 32
+typedef struct fpcdr_objective_weighted_params fpcdr_objective_weighted_params;
+struct fpcdr_objective_weighted_params
+{   /* (its size is held to the ctypes mirror's by tests/test_weighted_objective_host.py) */
+    fpcdr_objective_params base;
+    int32_t kind;          /* FPCDR_ROBUST_* */
+    float inv_c;           /* float32(1 / c); ignored for L2 */
+    float w_outside;       /* weight of uncovered pixels, finite and >= 0 */
+    int32_t sat;           /* 1 .. 255: capture pixels >= sat get weight 0; 0 = off */
+    int32_t T_weights;     /* entries of face_w */
+    const uint8_t *mask;   /* [B,H,W] 255 = trust, 0 = ignore, or NULL; any address */
+    const float *face_w;   /* [T_weights] finite and >= 0, or NULL */
+    double *wsum;          /* [FPCDR_WSUM_SLOTS] f64, zero-filled by the call's first kernel and accumulated by its shading kernel */
+};
+int fpcdr_objective_weighted_fwd(const fpcdr_objective_weighted_params *p, void *stream);
+
+/* Per image, the all-background share of the weighted objective and of its weights: out[i][0] += sum over the px_per_image pixels of
+ * image i of w0 * rho(ref - bg_scaled), out[i][1] += sum of w0, w0 = wm * w_outside with wm from the mask byte and sat as above.  ref
+ * [n_images, px_per_image] uint8, mask the same or NULL, both at any address (16-byte loads where base and length allow); out
+ * [n_images][2] f64, zero-filled by the caller.  Lane sums in float32 -> wave -> block -> one float64 atomic per sum and workgroup.  It
+ * depends on the captures alone: a fit loop computes it once per level and kind.  Errors as fpcdr_robust_loss's for kind, inv_c,
+ * w_outside and sat; NULL ref or out; counts <= 0; out not 8-byte aligned. */
+int fpcdr_ref_bg_wsum(const uint8_t *ref, const uint8_t *mask, int64_t n_images, int64_t px_per_image, float bg_scaled, int32_t kind,
+                      float inv_c, float w_outside, int32_t sat, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
