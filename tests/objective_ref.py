@@ -40,7 +40,26 @@ units of u of its own scale; the constructions move a triangle and its uv until 
 float32_in_kernel_order() is reference(dtype=float32) per pixel -- the text above is written in the kernels' operation order -- and
 names the texels that hold exactly ONE term, from a pixel outside every blend: there g_tex must equal gq * w_k bit for bit (one
 addend through the window's double, the float cast and an atomic onto 0 is exact).  plan() restates in integers how k_shade places
-its texel windows and which tables overflow; predicted_zeros() names the entries without a term."""
+its texel windows and which tables overflow; predicted_zeros() names the entries without a term.
+
+The MIP call (inp['mip_levels'] = the number of levels below the base; None: the call above) is stated on the same skeleton, for
+tests/test_gpu_objective_mip_ref.py and tests/test_objective_mip_ref.py: k_shade_mip_list/_queue, k_fix_mip_list/_queue, the host's
+_build_mips / _fold_mip_grads.
+    the footprint   da = (db.x e0x + db.z e1x, db.y e0x + db.w e1x, db.x e0y + db.z e1y, db.y e0y + db.w e1y), db the restated rast_db of
+                    rasterize_ref._Pixels, e0 = q0 - q2, e1 = q1 - q2 the triangle's uv edges (shade_body)
+    the lookup      _MipLookup = mip_lookup_fwd: compute_lod, the clamp to [0, n_levels], l0 = floor, fl, l1 = min(l0 + 1, n_levels), two
+                    _Lookup on texture_ref.box_chain (a level's texel has the box average of |tex| as its scale), col = c0 + (c1 - c0) fl
+    backward        per level g (1 - fl) and g fl times the four weights into that level's gradient; gtu = gfx0 w0 + gfx1 w1 with mu, mv;
+                    gfl = sum_c g_c (c1 - c0) gated by 0 <= raw <= n_levels; gl2 -> gdf, gbq -> gA, gC -> gda; gdb through e0, e1 and
+                    shade_pixel_bwd with derivative inputs (_uv_bwd(gd=)); the same chain on a blended pixel's difference dl (k_fix forms
+                    tu, tv from the float32 u, v of the record and recomputes da: the same formulas, one rounding of u apart)
+    the fold        g_tex = level 0's gradient + the box filter's backward of every coarser level, coarse to fine; S the same fold
+    empty pixels    their colour is level 0's bilinear value at uv = (0, 0) (empty_color, written by the rasteriser's list round from tex) and k_objective_finish scatters esum
+                    through make_taps(0, 0) into grad_tex: level 0 only.  The oracle agrees: a footprint of 0 clamps at level 0, gate closed.
+The level's choices (lo = raw < 0, hi = raw > n_levels and with them the gate, l0) and the tap choices of both levels join choices() /
+margins(); the level is measured in texture_ref's L_s plus the footprint's own scale through |d level / d da_k|.  plan()['mipbins'] restates
+the prepass (mlb, the extent of the prepared coordinates over the pass-0 rows, the half-period view under wrap), place() for the three
+windows of MipWinCaps and the routing of every pixel's two levels into a window or to memory -- it proves reach only, evaluate() never calls it."""
 import functools
 import math
 
@@ -71,14 +90,20 @@ OUTPUTS = ('g_tex', 'g_pos')
 # deferred pixels of the bin --, the six DPP steps of wave_sum_dpp, and the float cast of the quotient.  The four wave sums of a bin,
 # the slots, the background share and the division are double.
 N_VALUE_PIXEL, N_VALUE_BLEND = 29, 35
+# The mip call's longest path runs through the level's fraction: b0 8 as above; da0x = w2 p1y - w1 p2y 4, datx the sum of three 6, b0 datx 10,
+# da0x - . 11, * iw 12, * sx 13 (rast_db); the uv edge e0x 1, db.x e0x 15, the sum of two 16 (da); texture_ref.N_LEVEL = 12 operations from
+# da to fl (the device's log2f counted as one of them): 28; c1 - c0 is shorter (26), (c1 - c0) fl 29, + c0 30; * cs 31, rf - . 32, dd^2 33,
+# - d0^2 34.  A blended pixel adds the same six as above: 40.
+N_VALUE_PIXEL_MIP, N_VALUE_BLEND_MIP = 16 + TR.N_LEVEL + 6, 16 + TR.N_LEVEL + 12
 
 
 # The bar is (n_value + 2) u of S, as in fitstep_ref.py: n_value + 1 is the first-order bound of a path of n_value operations, and one more u
 # stands for the second-order terms (n^2 u^2, far below u at these counts).  It is a worst-case count against a scale summed over thousands
 # of pixels, so measured errors are a hundredth of a u: this bar sees a wrong term, a wrong factor or a lost pixel, not a lost bit.
-def n_value(C, max_deferred_in_a_bin):
+def n_value(C, max_deferred_in_a_bin, mip=False):
     trips = -(-4 * max_deferred_in_a_bin // 64)
-    return max(N_VALUE_PIXEL + 4 * C, N_VALUE_BLEND + 2 * C * trips) + 6 + 1
+    pixel, blend = (N_VALUE_PIXEL_MIP, N_VALUE_BLEND_MIP) if mip else (N_VALUE_PIXEL, N_VALUE_BLEND)
+    return max(pixel + 4 * C, blend + 2 * C * trips) + 6 + 1
 
 
 def _coef(x):
@@ -101,7 +126,8 @@ class _Lookup:
     """make_taps / make_taps_fast + load_taps + mask_taps for n pixels at (tu, tv) (Q) in tex [Ht,Wt,C].  ch: the float32 choices
     (a dict this fills when it is empty, and follows otherwise).  Taps k = 0..3 are (00, 10, 01, 11)."""
 
-    def __init__(self, tex, tu, tv, boundary, dtype, ch):
+    def __init__(self, tex, tu, tv, boundary, dtype, ch, tex_S=None):
+        """tex_S: the texels' scales (a level of the box chain: the box average of |tex|); None: the texels are inputs, S = |t|."""
         Ht, Wt, C = tex.shape
         make = len(ch) == 0
         self.gates = []      # Q whose value must stay positive for the choice to hold
@@ -139,6 +165,7 @@ class _Lookup:
         vx = (TR._inside(self.x0, Wt, boundary), TR._inside(self.x0 + 1, Wt, boundary))
         vy = (TR._inside(self.y0, Ht, boundary), TR._inside(self.y0 + 1, Ht, boundary))
         t = tex.detach().to('cpu', dtype)
+        tS = t.abs() if tex_S is None else tex_S.detach().to('cpu', dtype)
         self.flat, self.valid, self.t = [], [], []
         for k in range(4):
             jx, jy = k & 1, k >> 1
@@ -146,7 +173,7 @@ class _Lookup:
             self.flat.append(iy[jy] * Wt + ix[jx])
             self.valid.append(ok)
             m = ok.to(dtype)
-            self.t.append([Q(t[iy[jy], ix[jx], c] * m, t[iy[jy], ix[jx], c].abs() * m) for c in range(C)])
+            self.t.append([Q(t[iy[jy], ix[jx], c] * m, tS[iy[jy], ix[jx], c] * m) for c in range(C)])
         fx, fy = self.fx, self.fy
         self.col = []
         for c in range(C):
@@ -180,9 +207,184 @@ class _Lookup:
                 GS.index_add_(0, idx, term.S[ok])
 
 
-def _uv_bwd(px, gu, gv):
+LN2 = 0.6931471805599453
+
+
+def _pick(q, m):
+    return Q(q.v[m], q.S[m])
+
+
+def _spread(q, m, n, fill_v=0.0):
+    """Q over the pixels m of n -> Q [n] (fill_v with no scale elsewhere)."""
+    v, S = torch.full((n,), fill_v, dtype=q.v.dtype), torch.zeros(n, dtype=q.v.dtype)
+    v[m], S[m] = q.v, q.S
+    return Q(v, S)
+
+
+class _MipLookup:
+    """mip_lookup_fwd / mip_lookup_bwd (csrc/texsample.h; mip_sample_bwd in k_fix is the same formulas) for n pixels at (tu, tv) with the
+    footprint da (four Q: dudx, dudy, dvdx, dvdy of the texture coordinate per pixel) in the box chain of tex [Ht,Wt,C], levels 0..n_levels.
+    The level's discrete choices (float32, ch['level']): lo = raw < 0 and hi = raw > n_levels (the two clamps, and with them the gate
+    raw in [0, n_levels] of the level's gradient), l0 = min(floor(level), n_levels); the tap choices of each level's lookup are those of
+    _Lookup on the pixels of that l0 (ch[('a', l)], ch[('b', l)]).
+    The raw level carries texture_ref's L_s -- |0.5 log2 l2| + 0.5 / ln 2 (tr + rt_s) / l2, which counts the device's log2f (not correctly
+    rounded) as one of the N_LEVEL operations behind it -- plus, to first order, |d level / d da_k| S(da_k): here the footprint is no input."""
+
+    def __init__(self, tex, n_levels, tu, tv, da, boundary, dtype, ch):
+        Ht, Wt, C = tex.shape
+        n = tu.v.numel()
+        self.n, self.C, self.Ht, self.Wt, self.nl, self.dtype = n, C, Ht, Wt, n_levels, dtype
+        chain, chainA = TR.box_chain(tex[None], n_levels, dtype)
+        self.dims = [(t.shape[1], t.shape[2]) for t in chain]
+        # compute_lod
+        dudx, dudy, dvdx, dvdy = da[0] * float(Wt), da[1] * float(Wt), da[2] * float(Ht), da[3] * float(Ht)
+        if MUTANT == 'level_from_Wt_alone':
+            dvdx, dvdy = da[2] * float(Wt), da[3] * float(Wt)
+        A, Bq, Cc = dudx * dudx + dudy * dudy, dudx * dvdx + dudy * dvdy, dvdx * dvdx + dvdy * dvdy
+        tr, df = (A + Cc) * 0.5, (A - Cc) * 0.5
+        arg = df * df + Bq * Bq + 1e-30
+        rtv = torch.sqrt(arg.v)
+        rt = Q(rtv, arg.S / (2.0 * rtv))
+        l2 = tr + rt
+        raw_v = 0.5 * torch.log2(l2.v.clamp(min=1e-30))
+        self.L = dict(dudx=dudx, dudy=dudy, dvdx=dvdx, dvdy=dvdy, df=df, bq=Bq, rt=rt, l2=l2)
+        # L_s of texture_ref.level_of_detail on the values, and the footprint's own scale through |d level / d da_k|
+        BqA = (dudx.v * dvdx.v).abs() + (dudy.v * dvdy.v).abs()
+        rtS = (tr.v * tr.v + BqA * BqA + 1e-30) / rtv
+        Ls = raw_v.abs() + (0.5 / math.log(2.0)) * (tr.v + rtS) / l2.v
+        one = Q(torch.ones(n, dtype=dtype), torch.zeros(n, dtype=dtype))
+        for k, sens in enumerate(self._footprint_bwd(one, absolute=True)):
+            Ls = Ls + sens.v * da[k].S
+        raw = Q(raw_v, Ls)
+        lev = ch.setdefault('level', {})
+        if not lev:
+            lev['lo'], lev['hi'] = raw_v < 0, raw_v > float(n_levels)
+            level32 = raw_v.clamp(0.0, float(n_levels))
+            lev['l0'] = torch.floor(level32).long().clamp(max=n_levels)
+        lo, hi, l0 = lev['lo'], lev['hi'], lev['l0']
+        self.lo, self.hi, self.l0, self.raw = lo, hi, l0, raw
+        self.passes = ~(lo | hi)
+        if MUTANT == 'level_gate_ignored':
+            self.passes = torch.ones_like(lo)
+        zero = _zeros(n, dtype)
+        level = _where(lo, zero, _where(hi, Q(torch.full((n,), float(n_levels), dtype=dtype), torch.zeros(n, dtype=dtype)), raw))
+        l0f = l0.to(dtype)
+        self.fl = fl = Q(level.v - l0f, level.S)
+        self.l1 = (l0 + 1).clamp(max=n_levels)
+        safe = Q(torch.ones(n, dtype=dtype), torch.zeros(n, dtype=dtype))
+        free = self.passes
+        # the clamps (raw against 0 and n_levels), floor(level) -- a clamped level is exact and has none
+        self.gates = [Q(torch.where(lo, -raw.v, raw.v), raw.S), Q(torch.where(hi, raw.v - float(n_levels), float(n_levels) - raw.v), raw.S),
+                      _where(free, fl, safe), _where(free, Q(l0f + 1.0 - level.v, level.S), safe)]
+        self.level_gates = list(self.gates)
+        if MUTANT == 'fl_and_1_minus_fl_exchanged':
+            fl = 1.0 - fl
+        # the two bilinear lookups, level by level
+        self.groups = []
+        mu, mv = torch.ones(n, dtype=dtype), torch.ones(n, dtype=dtype)
+        c0 = [zero for _ in range(C)]
+        c1 = [zero for _ in range(C)]
+        for l in range(n_levels + 1):
+            m = torch.nonzero(l0 == l, as_tuple=True)[0]
+            if not m.numel():
+                continue
+            lu = min(l + 1, n_levels)
+            tum, tvm = _pick(tu, m), _pick(tv, m)
+            a = _Lookup(chain[l][0], tum, tvm, boundary, dtype, ch.setdefault(('a', l), {}), chainA[l][0])
+            b = _Lookup(chain[lu][0], tum, tvm, boundary, dtype, ch.setdefault(('b', l), {}), chainA[lu][0])
+            self.groups.append((m, l, lu, a, b))
+            mu[m], mv[m] = a.mu, a.mv
+            for q in a.gates + b.gates:
+                self.gates.append(_spread(q, m, n, 1.0))
+            for c in range(C):
+                c0[c] = c0[c] + _spread(a.col[c], m, n)
+                c1[c] = c1[c] + _spread(b.col[c], m, n)
+        self.mu, self.mv, self.c0, self.c1, self.fl_used = mu, mv, c0, c1, fl
+        self.col = [c0[c] + (c1[c] - c0[c]) * fl for c in range(C)]
+
+    def _footprint_bwd(self, glevel, absolute=False):
+        """glevel Q [n] = d loss / d level (already gated) -> d loss / d da, four Q.  absolute: every factor by its absolute value and
+        every subtraction an addition (the sensitivities |d level / d da_k| of the level's scale)."""
+        L = self.L
+        f = (lambda q: Q(q.v.abs(), q.S)) if absolute else (lambda q: q)
+        l2, rt = L['l2'], L['rt']
+        gl2 = _where(l2.v >= 1e-30, glevel * 0.5 / (l2 * LN2), 0.0)
+        gdf, gbq = gl2 * f(L['df']) / rt, gl2 * f(L['bq']) / rt
+        gA = gl2 * 0.5 + gdf * 0.5
+        gC = gl2 * 0.5 + gdf * 0.5 if absolute else gl2 * 0.5 - gdf * 0.5
+        dudx, dudy, dvdx, dvdy = f(L['dudx']), f(L['dudy']), f(L['dvdx']), f(L['dvdy'])
+        g_dudx = dudx * 2.0 * gA + dvdx * gbq
+        g_dudy = dudy * 2.0 * gA + dvdy * gbq
+        g_dvdx = dvdx * 2.0 * gC + dudx * gbq
+        g_dvdy = dvdy * 2.0 * gC + dudy * gbq
+        Wt, Ht = float(self.Wt), float(self.Ht)
+        return [g_dudx * Wt, g_dudy * Wt, g_dvdx * Ht, g_dvdy * Ht]
+
+    def backward(self, g):
+        """g: C Q [n] -> (gtu, gtv) masked by mu, mv, and gda (four Q): the gradient of the footprint."""
+        n, fl = self.n, self.fl_used
+        gtu = gtv = gfl = _zeros(n, self.dtype)
+        for m, l, lu, a, b in self.groups:
+            flm = _pick(fl, m)
+            ga, gb = [_pick(g[c], m) * (1.0 - flm) for c in range(self.C)], [_pick(g[c], m) * flm for c in range(self.C)]
+            au, av = a.backward(ga)
+            bu, bv = b.backward(gb)
+            gtu, gtv = gtu + _spread(au + bu, m, n), gtv + _spread(av + bv, m, n)
+        for c in range(self.C):
+            gfl = gfl + g[c] * (self.c1[c] - self.c0[c])
+        glevel = _where(self.passes, gfl, 0.0)
+        gda = self._footprint_bwd(glevel)
+        if MUTANT == 'gda_dropped':
+            gda = [q * 0.0 for q in gda]
+        return gtu, gtv, gda
+
+    def scatter(self, G, GS, g, rows):
+        """Per level l, G[l] += (g_c (1 - fl)) w_k at level l0's taps and (g_c fl) w_k at level l1's, for the pixels `rows`."""
+        sel = torch.zeros(self.n, dtype=torch.bool)
+        sel[rows] = True
+        for m, l, lu, a, b in self.groups:
+            local = torch.nonzero(sel[m], as_tuple=True)[0]
+            if not local.numel():
+                continue
+            flm = _pick(self.fl_used, m)
+            a.scatter(G[l], GS[l], [_pick(g[c], m) * (1.0 - flm) for c in range(self.C)], local)
+            b.scatter(G[lu], GS[lu], [_pick(g[c], m) * flm for c in range(self.C)], local)
+
+    def level_reach(self):
+        """Per level, [h*w] the number of tap terms from the choices alone (an upper level whose fraction is the exact 0 of a clamp has none)."""
+        count = [torch.zeros(h * w, dtype=torch.int64) for h, w in self.dims]
+        for m, l, lu, a, b in self.groups:
+            live_b = self.passes[m]
+            for k in range(4):
+                count[l].index_add_(0, a.flat[k][a.valid[k]], torch.ones(int(a.valid[k].sum()), dtype=torch.int64))
+                ok = b.valid[k] & live_b
+                count[lu].index_add_(0, b.flat[k][ok], torch.ones(int(ok.sum()), dtype=torch.int64))
+        return count
+
+    def any_valid(self):
+        out = torch.zeros(self.n, dtype=torch.bool)
+        for m, l, lu, a, b in self.groups:
+            va = a.valid[0] | a.valid[1] | a.valid[2] | a.valid[3]
+            vb = (b.valid[0] | b.valid[1] | b.valid[2] | b.valid[3]) & self.passes[m]
+            out[m] = va | vb
+        return out
+
+
+def fold_levels(G, scale=False):
+    """_fold_mip_grads: the box filter's backward, coarse to fine: every coarse texel's quarter to its four fine ones -> level 0's [h,w,C]."""
+    wq = 0.5 if (MUTANT == 'fold_weight_half' and scale is False) else 0.25
+    if scale is None:      # (counts of terms: summed as they are)
+        wq = 1
+    g = G[-1]
+    for l in range(len(G) - 1, 0, -1):
+        g = G[l - 1] + wq * g.repeat_interleave(2, dim=0).repeat_interleave(2, dim=1)
+    return g
+
+
+def _uv_bwd(px, gu, gv, gd=None):
     """shade_uv_bwd on the kept values of px (= shade_pixel_bwd<false>, which recomputes the same operations): (gu, gv) Q [n] -> the
-    nine components (vertex 0: x, y, w; vertex 1; vertex 2)."""
+    nine components (vertex 0: x, y, w; vertex 1; vertex 2).  gd: four Q = d loss / d rast_db (shade_pixel_bwd<true>, the mip call: the
+    statement of rasterize_ref._Pixels.backward on Q inputs)."""
     p0x, p0y, p1x, p1y, p2x, p2y = px.p
     fx, fy, a0, a1, iw, b0, b1, uc, vc = px.fx, px.fy, px.a0, px.a1, px.iw, px.b0, px.b1, px.uc, px.vc
     s = 1.0 / px.sum
@@ -191,6 +393,37 @@ def _uv_bwd(px, gu, gv):
     open0, open1 = (b0.v >= 0.0) & (b0.v <= 1.0), (b1.v >= 0.0) & (b1.v <= 1.0)
     gb0, gb1 = _where(open0, guc, 0.0), _where(open1, gvc, 0.0)
     zero = _zeros(px.n, px.dtype)
+    if gd is not None:
+        w0, w1, w2 = px.w
+        sx, sy = px.sx, px.sy
+        da0x, da0y, da1x, da1y, da2x, da2y = px.da
+        datx, daty = px.datx, px.daty
+        gw0 = gw1 = gw2 = gp0x = gp0y = gp1x = gp1y = gp2x = gp2y = zero
+        hx0, hy0, hx1, hy1 = gd[0] * sx, gd[1] * sy, gd[2] * sx, gd[3] * sy
+        n0x, n0y = da0x - b0 * datx, da0y - b0 * daty
+        n1x, n1y = da1x - b1 * datx, da1y - b1 * daty
+        giw = hx0 * n0x + hy0 * n0y + hx1 * n1x + hy1 * n1y
+        gn0x, gn0y, gn1x, gn1y = hx0 * iw, hy0 * iw, hx1 * iw, hy1 * iw
+        gb0 = gb0 - (gn0x * datx + gn0y * daty)
+        gb1 = gb1 - (gn1x * datx + gn1y * daty)
+        gdatx, gdaty = -(gn0x * b0 + gn1x * b1), -(gn0y * b0 + gn1y * b1)
+        gda0x, gda0y = gn0x + gdatx, gn0y + gdaty
+        gda1x, gda1y = gn1x + gdatx, gn1y + gdaty
+        gda2x, gda2y = gdatx, gdaty
+        gw2 = gw2 + gda0x * p1y; gp1y = gp1y + gda0x * w2; gw1 = gw1 - gda0x * p2y; gp2y = gp2y - gda0x * w1
+        gw1 = gw1 + gda0y * p2x; gp2x = gp2x + gda0y * w1; gw2 = gw2 - gda0y * p1x; gp1x = gp1x - gda0y * w2
+        gw0 = gw0 + gda1x * p2y; gp2y = gp2y + gda1x * w0; gw2 = gw2 - gda1x * p0y; gp0y = gp0y - gda1x * w2
+        gw2 = gw2 + gda1y * p0x; gp0x = gp0x + gda1y * w2; gw0 = gw0 - gda1y * p2x; gp2x = gp2x - gda1y * w0
+        gw1 = gw1 + gda2x * p0y; gp0y = gp0y + gda2x * w1; gw0 = gw0 - gda2x * p1y; gp1y = gp1y - gda2x * w0
+        gw0 = gw0 + gda2y * p1x; gp1x = gp1x + gda2y * w0; gw1 = gw1 - gda2y * p0x; gp0x = gp0x - gda2y * w1
+        ga0, ga1 = gb0 * iw, gb1 * iw
+        giw = giw + (gb0 * a0 + gb1 * a1)
+        gat = -giw * iw * iw
+        ga0, ga1, ga2 = ga0 + gat, ga1 + gat, gat
+        gp1x = gp1x + ga0 * p2y; gp2y = gp2y + ga0 * p1x; gp1y = gp1y - ga0 * p2x; gp2x = gp2x - ga0 * p1y
+        gp2x = gp2x + ga1 * p0y; gp0y = gp0y + ga1 * p2x; gp2y = gp2y - ga1 * p0x; gp0x = gp0x - ga1 * p2y
+        gp0x = gp0x + ga2 * p1y; gp1y = gp1y + ga2 * p0x; gp0y = gp0y - ga2 * p1x; gp1x = gp1x - ga2 * p0y
+        return [gp0x, gp0y, gw0 - fx * gp0x - fy * gp0y, gp1x, gp1y, gw1 - fx * gp1x - fy * gp1y, gp2x, gp2y, gw2 - fx * gp2x - fy * gp2y]
     ga0, ga1 = gb0 * iw, gb1 * iw
     giw = gb0 * a0 + gb1 * a1
     gat = -giw * iw * iw
@@ -269,7 +502,17 @@ def _forward(inp, dtype, ch):
     H, W = inp['res']
     st.px = px = RR._Pixels(inp['pos'], inp['tri'], inp['ids'], (H, W), dtype)
     st.q, st.tu, st.tv = _tex_coord(px, inp, dtype)
-    st.lk = _Lookup(inp['tex'], st.tu, st.tv, inp['boundary'], dtype, ch.setdefault('taps', {}))
+    st.mip = inp.get('mip_levels')
+    if st.mip is None:
+        st.lk = _Lookup(inp['tex'], st.tu, st.tv, inp['boundary'], dtype, ch.setdefault('taps', {}))
+    else:
+        # shade_body: da from the barycentrics' screen derivatives (rasterize_ref: rast_db) and the triangle's two uv edges
+        q, db = st.q, px.db
+        st.e = e0x, e0y, e1x, e1y = q[0][0] - q[2][0], q[0][1] - q[2][1], q[1][0] - q[2][0], q[1][1] - q[2][1]
+        st.da = [db[0] * e0x + db[2] * e1x, db[1] * e0x + db[3] * e1x, db[0] * e0y + db[2] * e1y, db[1] * e0y + db[3] * e1y]
+        if MUTANT == 'dudy_and_dvdx_swapped_in_da':
+            st.da = [st.da[0], st.da[2], st.da[1], st.da[3]]
+        st.lk = _MipLookup(inp['tex'], st.mip, st.tu, st.tv, st.da, inp['boundary'], dtype, ch.setdefault('taps', {}))
     zero = _zeros(1, dtype)
     if MUTANT == 'esum_with_wrap_taps_under_clamp' and inp['boundary'] == 'clamp':
         st.lk0 = _Lookup(inp['tex'], zero, zero, 'wrap', dtype, {})
@@ -279,7 +522,7 @@ def _forward(inp, dtype, ch):
         ch['ren'], ch['open0'], ch['open1'] = px.ren, (px.b0.v >= 0) & (px.b0.v <= 1), (px.b1.v >= 0) & (px.b1.v <= 1)
         ch['lo0'], ch['lo1'] = px.b0.v < 0, px.b1.v < 0
         rast = torch.zeros(px.B, H, W, 4)
-        rast[px.bi, px.yy, px.xx, 2] = px.uvz[2].v
+        rast[px.bi, px.yy, px.xx, 2] = px.uvz[2].v.float()      # (float64 only on _unsafe's way out of a gate the two dtypes decide differently)
         rast[..., 3] = inp['ids'].float()
         ch['rast'] = rast
         ch['adj'] = AR.topology(inp['tri'])
@@ -330,18 +573,31 @@ def evaluate(inp, dtype=torch.float64):
     d0 = rf - Q(bgs.expand(n), bgs.abs().expand(n))
     dd = [rf - lk.col[c] * CS_SCALE for c in range(C)]
     gq = [Kq * dd[c] for c in range(C)]
-    G_tex, S_tex = torch.zeros(Ht * Wt * C, dtype=dtype), torch.zeros(Ht * Wt * C, dtype=dtype)
+    mip = st.mip is not None
+    if mip:      # one gradient per level of the chain, folded into level 0's at the end (_fold_mip_grads)
+        L_tex = [torch.zeros(h * w * C, dtype=dtype) for h, w in lk.dims]
+        LS_tex = [torch.zeros(h * w * C, dtype=dtype) for h, w in lk.dims]
+        G_tex, S_tex = L_tex[0], LS_tex[0]
+    else:
+        G_tex, S_tex = torch.zeros(Ht * Wt * C, dtype=dtype), torch.zeros(Ht * Wt * C, dtype=dtype)
     G_pos, S_pos = torch.zeros(B * px.V, 4, dtype=dtype), torch.zeros(B * px.V, 4, dtype=dtype)
     every = torch.arange(n)
 
     def chain(g, rows):
         """texture, interpolate and rasterize backward of d loss / d colour g (C Q [n]) for the pixels `rows`."""
-        lk.scatter(G_tex, S_tex, g, rows)
-        gtu, gtv = lk.backward(g)
         q = st.q
+        if mip:
+            lk.scatter(L_tex, LS_tex, g, rows)
+            gtu, gtv, gda = lk.backward(g)
+            e0x, e0y, e1x, e1y = st.e
+            gdb = [gda[0] * e0x + gda[2] * e0y, gda[1] * e0x + gda[3] * e0y, gda[0] * e1x + gda[2] * e1y, gda[1] * e1x + gda[3] * e1y]
+        else:
+            lk.scatter(G_tex, S_tex, g, rows)
+            gtu, gtv = lk.backward(g)
+            gdb = None
         gu = gtu * (q[0][0] - q[2][0]) + gtv * (q[0][1] - q[2][1])
         gv = gtu * (q[1][0] - q[2][0]) + gtv * (q[1][1] - q[2][1])
-        nine = _uv_bwd(px, gu, gv)
+        nine = _uv_bwd(px, gu, gv, gdb)
         for k in range(3):
             for c3, colm in enumerate((0, 1, 3)):
                 G_pos[:, colm].index_add_(0, px.rows[k][rows], nine[3 * k + c3].v[rows])
@@ -415,6 +671,10 @@ def evaluate(inp, dtype=torch.float64):
             S_pos[:, colm].index_add_(0, rows[rc], q.S[rc])
             if MUTANT == 'd_alpha_counted_by_both_pixels':
                 G_pos[:, colm].index_add_(0, rows[keep & both], q.v[keep & both])
+    levels = None
+    if mip:      # _fold_mip_grads: level 0's gradient plus the box filter's backward of every coarser level; the scales fold alike
+        levels = [(g.reshape(h, w, C), s.reshape(h, w, C)) for g, s, (h, w) in zip(L_tex, LS_tex, lk.dims)]
+        G_tex, S_tex = fold_levels([g for g, _ in levels]).reshape(-1), fold_levels([s for _, s in levels], scale=True).reshape(-1)
     # ---- the value ----
     tv_, tS_ = torch.zeros((), dtype=dtype), torch.zeros((), dtype=dtype)
     d0h = _at(d0, hrow)
@@ -436,7 +696,7 @@ def evaluate(inp, dtype=torch.float64):
             'g_tex': (G_tex.reshape(Ht, Wt, C), S_tex.reshape(Ht, Wt, C)), 'st': st, 'D': D, 'E': E, 'hit': hit, 'hit2': hit2, 'pix': pix,
             'cov': cov, 'rowof': rowof, 'gq': torch.stack([q.v for q in gq], 1), 'dd': torch.stack([q.v for q in dd], 1),
             'dn': torch.stack([q.v for q in dn], 1) if hit.numel() else torch.zeros(0, C, dtype=dtype), 'n_esum': n_esum, 'col': col_img,
-            'bgs': float(bgs), 'b': b, 'n_total': n_total}
+            'bgs': float(bgs), 'b': b, 'n_total': n_total, 'levels': levels}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -476,18 +736,27 @@ def _structure(inp):
     pix = (px.bi * H + px.yy) * W + px.xx
     cov = torch.zeros(B * H * W, dtype=torch.bool)
     cov[pix] = True
-    count = torch.zeros(Ht * Wt, dtype=torch.int64)
-    for k in range(4):
-        count.index_add_(0, lk.flat[k][lk.valid[k]], torch.ones(int(lk.valid[k].sum()), dtype=torch.int64))
+    level_count = None
+    if st.mip is None:
+        count = torch.zeros(Ht * Wt, dtype=torch.int64)
+        for k in range(4):
+            count.index_add_(0, lk.flat[k][lk.valid[k]], torch.ones(int(lk.valid[k].sum()), dtype=torch.int64))
+        anyv = lk.valid[0] | lk.valid[1] | lk.valid[2] | lk.valid[3]
+    else:      # the taps of every level, folded: a coarse texel's terms reach its four fine ones
+        level_count = lk.level_reach()
+        count = fold_levels([c.reshape(h, w) for c, (h, w) in zip(level_count, lk.dims)], scale=None).reshape(-1)
+        anyv = lk.any_valid()
     rc = cov[D.er]
     n_esum = int((rc & ~cov[D.eo]).sum())
     reach = count > 0
     if n_esum:
         for k in range(4):
             reach[lk0.flat[k][lk0.valid[k]]] = True
-    anyv = lk.valid[0] | lk.valid[1] | lk.valid[2] | lk.valid[3]
     term = (ch['open0'] | ch['open1']) & ((lk.mu != 0) | (lk.mv != 0)) & anyv
     off_centre = (px.fx.v != 0) | (px.fy.v != 0)      # (the w column's term is -fx g_x - fy g_y: none at the image's centre)
+    if st.mip is not None:      # the footprint's gradient reaches x, y and w of all three vertices wherever the level's gate is open
+        through_level = lk.passes & anyv
+        term, off_centre = term | through_level, off_centre | through_level
     rows, rows_w = torch.zeros(B * px.V, dtype=torch.bool), torch.zeros(B * px.V, dtype=torch.bool)
     for k in range(3):
         rows[px.rows[k][term]] = True
@@ -500,7 +769,7 @@ def _structure(inp):
     for r_ in (rows, rows_w):
         r_[(base + D.E['va'][D.ei, D.ee])[ent]] = True
         r_[(base + D.E['vb'][D.ei, D.ee])[ent]] = True
-    return dict(reach=reach, rows=rows, rows_w=rows_w, count=count, n_esum=n_esum, cov=cov, pix=pix, st=st, D=D)
+    return dict(reach=reach, rows=rows, rows_w=rows_w, count=count, n_esum=n_esum, cov=cov, pix=pix, st=st, D=D, level_count=level_count)
 
 
 def predicted_zeros(inp):
@@ -522,6 +791,9 @@ def float32_in_kernel_order(inp):
     [m] flat indices of the texels that hold exactly one plain term, of a pixel outside every blend, and no share of the empty pixels, and
     'g_tex' [m,C] the float32 product gq * w_k there; 'gq_w' [n,4,C] all the products."""
     r = evaluate(inp, torch.float32)
+    if r['st'].mip is not None:      # (the mip call's one-term texels are held through `mip/magnified/C1/wrap`, on the non-mip statement)
+        C = inp['tex'].shape[2]
+        return {'r': r, 'texel': torch.zeros(0, dtype=torch.int64), 'g_tex': torch.zeros(0, C), 'gq_w': None}
     s = _structure(inp)
     lk, C = r['st'].lk, inp['tex'].shape[2]
     n = r['st'].px.n
@@ -575,6 +847,83 @@ def _window(x0, y0, Ht, Wt, cells, boundary):
     return dict(ox=sx0, oy=sy0, ows=stride, owr=rows, owrap=owrap, centred=centred, fits=fits, box=(nw, nh))
 
 
+MIP_WIN_CELLS = {1: (2304, 704, 256), 3: (1088, 384, 128), 4: (1088, 384, 128)}      # MipWinCaps<CS>
+MIP_PASS0_ROWS = (0, 1, 10, 11, 20, 21, 30, 31)      # shade_row_pair(0, wave): row pairs 0, 5, 10, 15 of the WHOLE bin
+
+
+def _mip_place(ua, ub, va, vb, wl, hl, cap):
+    """place() of shade_body's prepass for one level of wl x hl texels: the window (x, y, stride, rows) and whether it fits."""
+    f = np.float32
+    big = f(1073741824.0)
+    fl_ = lambda t, n: int(min(max(np.floor(f(f(t) * f(n)) - f(0.5)), -big), big))
+    xa, ya = fl_(ua, wl) - 1, fl_(va, hl) - 1
+    nw, nh = fl_(ub, wl) + 2 - xa + 1, fl_(vb, hl) + 2 - ya + 1
+    fits = nw * nh <= cap
+    if fits:
+        stride = nw
+        rows = cap // stride
+        ya -= (rows - nh) >> 1
+    else:
+        aspect = min(max(f(nw) / f(nh), f(1.0) / f(cap)), f(cap))
+        stride = min(max(int(np.sqrt(f(f(cap) * aspect))), 2), cap // 2)
+        rows = cap // stride
+        xa += (nw - stride) >> 1
+        ya += (nh - rows) >> 1
+    return dict(x=xa, y=ya, s=stride, r=rows, fits=fits, box=(nw, nh))
+
+
+def _plan_mip_bin(st, m, by, boundary, C):
+    """The prepass, place() and the routing of one bin (pixels m of the float32 forward st) -> dict: mlb (None: no pass-0 pixel, no window),
+    windows (three dicts or None), wrap (w0wrap, w1wrap, w2wrap), shifted (the half-period view taken for u, for v),
+    levels {l: [tap sets into a window, tap sets to memory]} over both levels of every pixel, below_mlb (pixels with l0 < mlb)."""
+    px, lk = st.px, st.lk
+    f32 = torch.float32
+    Ht, Wt, nl = lk.Ht, lk.Wt, lk.nl
+    prep = lambda t: t - torch.floor(t) if boundary == 'wrap' else (t.clamp(0.0, 1.0) if boundary == 'clamp' else t)
+    pu, pv = prep(st.tu.v.to(f32)), prep(st.tv.v.to(f32))
+    zy = px.yy - by * BIN
+    p0 = m & torch.isin(zy, torch.tensor(MIP_PASS0_ROWS))
+    out = dict(mlb=None, windows=[None, None, None], wrap=[False, False, False], shifted=(False, False), levels={}, below_mlb=0)
+    wins = [None, None, None]
+    if bool(p0.any()):
+        mlb = int(lk.l0[p0].min())
+        ua, ub, va, vb = float(pu[p0].min()), float(pu[p0].max()), float(pv[p0].min()), float(pv[p0].max())
+        su_, sv_ = False, False
+        if boundary == 'wrap':
+            half = lambda t: (t + 0.5) - torch.floor(t + 0.5)
+            su, sv = half(pu[p0]), half(pv[p0])
+            ua2, ub2, va2, vb2 = float(su.min()), float(su.max()), float(sv.min()), float(sv.max())
+            f = np.float32
+            if f(ub2) - f(ua2) < f(ub) - f(ua):
+                ua, ub, su_ = float(f(ua2) - f(0.5)), float(f(ub2) - f(0.5)), True
+            if f(vb2) - f(va2) < f(vb) - f(va):
+                va, vb, sv_ = float(f(va2) - f(0.5)), float(f(vb2) - f(0.5)), True
+        for j in range(3):
+            l = mlb + j
+            if l <= nl:
+                wins[j] = _mip_place(ua, ub, va, vb, Wt >> l, Ht >> l, MIP_WIN_CELLS[C][j])
+        wrap = [w is not None and (w['x'] < 0 or w['y'] < 0 or w['x'] + w['s'] > (Wt >> (mlb + j)) or w['y'] + w['r'] > (Ht >> (mlb + j)))
+                for j, w in enumerate(wins)]
+        out.update(mlb=mlb, windows=wins, wrap=wrap, shifted=(su_, sv_), below_mlb=int((lk.l0[m] < mlb).sum()))
+    wc = lambda d, n: torch.where(d < 0, d + n, torch.where(d >= n, d - n, d))
+    for which, lev, live in ((0, lk.l0, torch.ones_like(m)), (1, lk.l1, lk.passes)):      # (an upper level with fl = 0 scatters nothing)
+        for l in torch.unique(lev[m & live]).tolist():
+            sel = m & live & (lev == l)
+            inside = torch.zeros_like(sel)
+            j = None if out['mlb'] is None else l - out['mlb']
+            if j is not None and 0 <= j <= 2 and wins[j] is not None:
+                w = wins[j]
+                lx = torch.floor(pu * float(Wt >> l) - 0.5).long() - w['x']
+                ly = torch.floor(pv * float(Ht >> l) - 0.5).long() - w['y']
+                if boundary == 'wrap' and out['wrap'][j]:
+                    lx, ly = wc(lx, Wt >> l), wc(ly, Ht >> l)
+                inside = sel & (lx >= 0) & (lx < w['s'] - 1) & (ly >= 0) & (ly < w['r'] - 1)
+            acc = out['levels'].setdefault(l, [0, 0])
+            acc[0] += int(inside.sum())
+            acc[1] += int((sel & ~inside).sum())
+    return out
+
+
 def plan(inp):
     """In integers, per occupied bin (b, by, bx) and half, what k_shade and k_fix do with the call -> dict:
     'halves': {(b, by, bx, half): window dict + 'inside' / 'outside' (pixels whose four adds go into the window / to memory)},
@@ -610,13 +959,15 @@ def plan(inp):
     hit2[D.eo[rc & s['cov'][D.eo]]] = True
     hit2 = hit2.reshape(B, H, W)
     key = (px.bi * 1000 + px.yy // BIN) * 1000 + px.xx // BIN
-    halves, bins = {}, {}
+    halves, bins, mipbins = {}, {}, {}
     is_hit = hit2[px.bi, px.yy, px.xx]
     ent_bin = lambda p: ((p // (H * W)) * 1000 + ((p // W) % H) // BIN) * 1000 + (p % W) // BIN
     for k in torch.unique(key).tolist():
         b, by, bx = k // 1000000, (k // 1000) % 1000, k % 1000
         m = key == k
-        for half in (0, 1):
+        if st.mip is not None:
+            mipbins[(b, by, bx)] = _plan_mip_bin(st, m, by, bd, C)
+        for half in ((0, 1) if st.mip is None else ()):
             zy = px.yy - by * BIN
             mh = m & (zy // 16 == half)
             if not bool(mh.any()):
@@ -646,13 +997,13 @@ def plan(inp):
         bins[(b, by, bx)] = dict(
             vertices=int(torch.unique(px.vi[m].reshape(-1)).numel()), deferred=int(deferred[b, y0:y0 + BIN, x0:x0 + BIN].sum()),
             hit=int(mhit.sum()), hit_vertices=int(torch.unique(hv).numel()),
-            hit_texels=int(torch.unique(torch.cat([lk.flat[t][mhit & lk.valid[t]] for t in range(4)])).numel()),
+            hit_texels=0 if st.mip is not None else int(torch.unique(torch.cat([lk.flat[t][mhit & lk.valid[t]] for t in range(4)])).numel()),
             sil=bool((((apron >> 24) != 0) & sub).any()), entries=int(ent.sum()))
     pr = D.pairs
     blended = D.active.any(1)
     p0, p1 = pr.p0[blended], pr.p1[blended]
     on_border = lambda p: ((p % W) == 0) | ((p % W) == W - 1) | (((p // W) % H) == 0) | (((p // W) % H) == H - 1)
-    return dict(halves=halves, bins=bins, pairs=int(blended.sum()), cross=int((ent_bin(p0) != ent_bin(p1)).sum()),
+    return dict(halves=halves, bins=bins, mipbins=mipbins, pairs=int(blended.sum()), cross=int((ent_bin(p0) != ent_bin(p1)).sum()),
                 cross_x31=int(((pr.x0[blended] % BIN == BIN - 1) & (pr.d[blended] == 0)).sum()),
                 cross_y31=int(((pr.y0[blended] % BIN == BIN - 1) & (pr.d[blended] == 1)).sum()),
                 empty_partner=s['n_esum'], image_border=int((on_border(p0) | on_border(p1)).sum()),
@@ -707,7 +1058,7 @@ def _settle(g, ids_of, gen, rounds=200):
         pos = _clip(g['X'], g['z'], g['w'], H, W)
         uv = g['uv_fn'](g['X'], g['off']) if 'uv_fn' in g else g['uv']
         inp = dict(pos=pos, tri=g['tri'], ids=ids_of(pos, g['tri']), res=g['res'], uv=uv.float().contiguous(), uv_tri=g['uv_tri'], tex=g['tex'],
-                   ref_u8=g['ref_u8'], boundary=g['boundary'])
+                   ref_u8=g['ref_u8'], boundary=g['boundary'], mip_levels=g.get('mip_levels'))
         shared = bool(g.get('shared'))
         rows, uvr = _unsafe(inp, shared)
         if rows.numel() == 0 and uvr.numel() == 0:
@@ -813,6 +1164,49 @@ CASE_IDS = [c['name'] for c in CASES]
 _case_cache = {}
 
 
+# The mip call (enable_mip=True; tests/test_gpu_objective_mip_ref.py).  Levels settle by construction: within a triangle every vertex has the
+# same w, so the uv map is affine in the screen and the level ONE number per triangle, log2 of the major axis of its texels per pixel; the
+# minor axis is `aniso` of it (df far from 0: rt is well conditioned) and alternates between u and v from triangle to triangle.  Each
+# triangle has its own place in the texture (drawn again when a tap is too close to a cell border), so a bin's pass-0 extent covers much of
+# the texture.  The second image shows the first one's triangles (3, -2) pixels away, with another depth order.
+# pass-0 rows of a bin are 0, 1, 10, 11, 20, 21, 30, 31: a triangle whose pixel centres lie in rows 3 .. 8 of image 0 (1 .. 6 + 2 of image 1's
+# shift: rows 5 .. 8 and 3 .. 6) covers none of them
+OFF_PASS0_TRIS = [[(8.0, 4.7), (19.0, 5.2), (12.5, 9.2)], [(40.0, 36.8), (52.0, 37.1), (45.0, 41.2)]]
+# six large triangles, w varying within each by a factor of 1.12 (a quarter of a level, log2 1.12^2 = 0.33, centred by the construction)
+PERSPECTIVE_TRIS = [[(2.0, 2.0), (30.0, 4.0), (12.0, 26.0)], [(34.0, 3.0), (66.0, 6.0), (48.0, 28.0)], [(4.0, 24.0), (26.0, 42.0), (3.0, 43.0)],
+                    [(28.0, 22.0), (50.0, 40.0), (26.0, 41.0)], [(52.0, 24.0), (68.0, 43.0), (50.0, 42.0)], [(14.0, 8.0), (44.0, 12.0), (30.0, 34.0)]]
+
+
+def _mip_cases():
+    out = []
+    c = lambda *a, **kw: out.append(_case(*a, mip=True, **kw))
+    c('mip/mid/C1/wrap/seam', '24 x 16 texels over several periods, levels near 1.5 (three levels: 24 -> 3 is odd): the shifted view, w0wrap / w1wrap',
+      'levels', 1, 'wrap', (16, 24), n_tri=60, size=10.0, levels=(1.5, 1.35, 1.65), uv_range=(0.0, 3.0))
+    c('mip/mid/C3/clamp', '32 x 32 texels, uv beyond [0, 1]: mu / mv = 0, taps in the padding at both levels; levels near 0.5 and 2.5',
+      'levels', 3, 'clamp', (32, 32), n_tri=60, size=10.0, levels=(0.4, 2.6), uv_range=(-0.3, 1.3))
+    c('mip/mid/C4/zero', 'the same under zero: taps with corners in the padding at both levels', 'levels', 4, 'zero', (32, 32), n_tri=60, size=10.0,
+      levels=(0.4, 2.6), uv_range=(-0.3, 1.3))
+    c('mip/span', '64 x 64, the whole chain: levels near 1.5 .. 4.5 in one bin and 0.5 in triangles off the pass-0 rows: levels >= mlb + 3 and < mlb go to memory',
+      'levels', 1, 'wrap', (64, 64), n_tri=90, size=8.0, levels=(1.45, 2.55, 3.5, 4.6), uv_range=(0.0, 3.0), extra=OFF_PASS0_TRIS, extra_level=0.5)
+    c('mip/top', '16 x 16 with all four levels: one group clamps at the 1 x 1 top (l1 == l0, both taps of an axis on one texel), one sits between 3 and 4, one clamps at level 0',
+      'levels', 1, 'wrap', (16, 16), n_tri=60, size=10.0, levels=(5.5, 3.5, -0.6), uv_range=(0.0, 3.0))
+    c('mip/no-levels', 'a 15 x 17 texture has no chain: the mip kernels with level 0 alone', 'levels', 3, 'wrap', (15, 17), n_tri=60, size=10.0,
+      levels=(0.5, 1.5), uv_range=(0.0, 3.0))
+    c('mip/overflow/C3', 'a footprint stretched 4 : 1 at level 0.4: the pass-0 extent does not fit 1088 cells, place() takes its aspect branch', 'levels', 3,
+      'wrap', (64, 64), n_tri=60, size=10.0, levels=(0.4,), aniso=0.25, uv_range=(0.0, 1.0))
+    c('mip/perspective', 'w varies WITHIN each of six large triangles: the level moves inside one integer interval, the w column gets terms through gdb',
+      'perspective', 1, 'wrap', (16, 16), level=1.5)
+    c('mip/islands/zero', 'separated triangles on an empty frame: k_fix_mip\'s difference term and the empty share alone near uv = (0, 0)', 'islands', 4,
+      'zero', (16, 16), uv_box=(0.55, 0.8))      # (about a texel a pixel: levels below 1, so no tap of level 1 comes near texel (0, 0))
+    for k in TINY:
+        c(f'mip/tiny/{k}', 'an image of one or two pixels', 'tiny', 3 if k == '1x1' else 1, 'wrap', (8, 8), res=TINY[k][0], B=1, tiny=k)
+    return out
+
+
+MIP_CASES = _mip_cases()
+MIP_CASE_IDS = [c['name'] for c in MIP_CASES]
+
+
 def _geometry(c, gen):
     """-> X [B,V,2], z, w [B,V], tri, uv [Vt,2] float64, uv_tri."""
     (H, W), B, (Ht, Wt) = c['res'], c['B'], c['tex_hw']
@@ -842,6 +1236,47 @@ def _geometry(c, gen):
         else:
             uv = _screen_uv(X[0], Ht, Wt, c['tpp'], origin=(-7.3, -5.1))
         return X, z, w, tri, uv, tri.clone(), {}
+    if c['geom'] in ('levels', 'perspective'):
+        rnd = lambda *shape: torch.rand(*shape, generator=gen, dtype=torch.float64)
+        if c['geom'] == 'levels':
+            X, z, w, tri = _fat_soup(B, c['n_tri'], gen, H, W, c['size'])
+            lev = [c['levels'][i % len(c['levels'])] for i in range(c['n_tri'])]
+            if 'extra' in c:      # hand-placed triangles in front of the soup (z/w = -0.95), at a level of their own
+                E = torch.tensor(c['extra'], dtype=torch.float64).reshape(1, -1, 2).repeat(B, 1, 1)
+                X, z = torch.cat([X, E], 1), torch.cat([z, torch.full((B, E.shape[1]), -0.95, dtype=torch.float64)], 1)
+                w = torch.cat([w, rnd(B, E.shape[1]) * 2.5 + 0.5], 1)
+                lev += [c['extra_level']] * (E.shape[1] // 3)
+            w = w.reshape(B, -1, 3)[..., :1].expand(-1, -1, 3).reshape(B, -1).contiguous()      # one w per triangle
+        else:
+            P = torch.tensor(PERSPECTIVE_TRIS, dtype=torch.float64)
+            P = P.mean(1, keepdim=True) + 0.6 * (P - P.mean(1, keepdim=True))      # (over a hundred pixels each; larger ones do not settle: every pixel has 20 choices)
+            X = P.reshape(1, -1, 2).repeat(B, 1, 1)
+            n = X.shape[1] // 3
+            z = rnd(B, 3 * n) * 1.8 - 0.9
+            w = ((rnd(1, n, 1) * 2.0 + 0.7) * torch.tensor([1.0, 1.06, 1.12], dtype=torch.float64)).reshape(1, -1).repeat(B, 1)
+            lev = [0.0] * n      # (case_inputs centres every triangle's level on c['level'] through `scale`)
+        T = X.shape[1] // 3
+        tri = torch.arange(3 * T, dtype=torch.int32).reshape(T, 3)
+        shift = torch.tensor([[3.0, -2.0]], dtype=torch.float64) * torch.arange(B, dtype=torch.float64).reshape(B, 1, 1)
+        X = X[:1] + shift
+        major = 2.0 ** torch.tensor(lev, dtype=torch.float64)
+        minor = major * c.get('aniso', 0.5)
+        even = (torch.arange(T) % 2 == 0)
+        tpp = torch.stack([torch.where(even, major, minor), torch.where(even, minor, major)], 1)      # texels a pixel along u, along v
+        scale = torch.ones(T, dtype=torch.float64)
+        lo, hi = c.get('uv_range', (0.0, 3.0))
+        draw = lambda n_: lo + (hi - lo) * rnd(n_, 2)
+        size = torch.tensor([Wt, Ht], dtype=torch.float64)
+
+        # (perspective: the screen is turned before it is scaled, so dudy != dvdx -- with both 0 their exchange would change nothing)
+        ang = (0.5 + 0.3 * torch.arange(T, dtype=torch.float64)) if c['geom'] == 'perspective' else torch.zeros(T, dtype=torch.float64)
+        rot = torch.stack([torch.stack([torch.cos(ang), -torch.sin(ang)], 1), torch.stack([torch.sin(ang), torch.cos(ang)], 1)], 1)      # [T,2,2]
+
+        def fn(X_, off):
+            P = X_[0].reshape(-1, 3, 2)
+            turned = torch.einsum('tij,tkj->tki', rot, P - P.mean(1, keepdim=True))
+            return (turned * (tpp * scale[:, None] / size)[:, None] + off[:, None]).reshape(-1, 2)
+        return X, z, w, tri, None, tri.clone(), dict(uv_fn=fn, off=draw(T), draw_off=draw, shift=shift, scale=scale)
     if c['geom'] == 'mesh':
         v, tri = _subdivided(*AR._octahedron())      # 66 vertices, 128 triangles, closed
         Xs, zs, ws = [], [], []
@@ -861,7 +1296,8 @@ def _geometry(c, gen):
     w = torch.rand(B, 3 * n, generator=gen, dtype=torch.float64) * 2.5 + 0.5
     z = torch.rand(B, 3 * n, generator=gen, dtype=torch.float64) * 1.8 - 0.9
     tri = torch.arange(3 * n, dtype=torch.int32).reshape(n, 3)
-    uv = 0.3 + 0.4 * torch.rand(3 * n, 2, generator=gen, dtype=torch.float64)
+    uv_lo, uv_span = c.get('uv_box', (0.3, 0.4))
+    uv = uv_lo + uv_span * torch.rand(3 * n, 2, generator=gen, dtype=torch.float64)
     return X, z, w, tri, uv, tri.clone(), {}
 
 
@@ -870,17 +1306,42 @@ def case_inputs(name, oracle_ops):
     [Ht,Wt,C], ref_u8 [B,H,W], boundary.  Cached: treat as read-only."""
     if name in _case_cache:
         return _case_cache[name]
-    c = CASES[CASE_IDS.index(name)]
-    gen = torch.Generator().manual_seed(4000 + sum(ord(ch) for ch in name.split('/')[0]) + 7 * c['C'])
+    mip = name in MIP_CASE_IDS
+    c = MIP_CASES[MIP_CASE_IDS.index(name)] if mip else CASES[CASE_IDS.index(name)]
+    gen = torch.Generator().manual_seed(4000 + sum(ord(ch) for ch in (name if mip else name.split('/')[0])) + 7 * c['C'])
     X, z, w, tri, uv, uv_tri, extra = _geometry(c, gen)
     (H, W), B, (Ht, Wt), C = c['res'], c['B'], c['tex_hw'], c['C']
     tex = (torch.rand(Ht, Wt, C, generator=gen) * 0.5 + 0.01).contiguous()
     ref = torch.randint(1, 141, (B, H, W), generator=gen, dtype=torch.uint8)      # (never 0: a pixel that shows only zero-mode padding has colour 0, and dd = 0 must not occur)
     g = dict(X=X, z=z, w=w, tri=tri, uv=uv, uv_tri=uv_tri, tex=tex, ref_u8=ref, boundary=c['boundary'], res=(H, W), **dict(dict(off=None), **extra))
-    inp = _settle(g, lambda p, t: oracle_ops.rasterize_ids(p, t, (H, W)), gen)
+    ids_of = lambda p, t: oracle_ops.rasterize_ids(p, t, (H, W))
+    if mip:
+        g['mip_levels'] = TR.num_levels(Ht, Wt, c.get('max_mip_level'))
+    if c['geom'] == 'perspective':      # centre every triangle's level on c['level']: the level is log2 of the triangle's uv scale plus a term of its geometry
+        pos = _clip(X, z, w, H, W)
+        probe = dict(pos=pos, tri=tri, ids=ids_of(pos, tri), res=(H, W), uv=extra['uv_fn'](X, g['off']).float().contiguous(), uv_tri=uv_tri, tex=tex,
+                     ref_u8=ref, boundary=c['boundary'], mip_levels=g['mip_levels'])
+        ch = {}
+        _forward(probe, torch.float32, ch)
+        st = _forward(probe, torch.float64, ch)
+        for t in range(tri.shape[0]):
+            raw = st.lk.raw.v[st.px.t == t]
+            extra['scale'][t] *= 2.0 ** (c['level'] - 0.5 * float(raw.min() + raw.max()))
+    inp = _settle(g, ids_of, gen)
+    if mip:
+        inp['max_mip_level'] = c.get('max_mip_level')
     inp['name'] = name
     _case_cache[name] = inp
     return inp
+
+
+def with_mip(inp, max_mip_level=None):
+    """The inputs of a non-mip case for the call with enable_mip=True (a copy under the name 'mip/' + its name, cached like a case)."""
+    name = 'mip/' + inp['name']
+    if name not in _case_cache:
+        Ht, Wt, _ = inp['tex'].shape
+        _case_cache[name] = dict(inp, name=name, mip_levels=TR.num_levels(Ht, Wt, max_mip_level), max_mip_level=max_mip_level)
+    return _case_cache[name]
 
 
 @functools.lru_cache(maxsize=None)
@@ -926,7 +1387,7 @@ def failures(inp, ref, r32, got, k32=None):
         for (row, e), (_, e32) in zip(rows, rows32):
             if not e <= 8 * e32 + 4:
                 bad.append((row, 'bound', round(e, 2), round(8 * e32 + 4, 2)))
-    n = n_value(inp['tex'].shape[2], plan(inp)['max_deferred'])
+    n = n_value(inp['tex'].shape[2], plan(inp)['max_deferred'], inp.get('mip_levels') is not None)
     if not value_error(got['value'], ref) <= n + 2:
         bad.append(('value', value_error(got['value'], ref), n + 2))
     if k32 is not None and not torch.equal(got['g_tex'].reshape(-1, inp['tex'].shape[2])[k32['texel']].float(), k32['g_tex']):

@@ -67,7 +67,7 @@ def _call(dr, inp, want=('pos', 'tex'), **kw):
     return got
 
 
-def _hold(name, inp, got, tag, calls=1):
+def _hold(name, inp, got, tag, calls=1, word='OBJ'):
     ref, r32, k32 = R.reference(inp), R.reference(inp, torch.float32), R.float32_in_kernel_order(inp)
     D = ref['D']
     assert torch.equal(got['ids'], R.id_planes(inp)), (name, tag, 'id planes')
@@ -78,9 +78,9 @@ def _hold(name, inp, got, tag, calls=1):
     for k in R.OUTPUTS:
         if k in got:
             for (row, e), (_, e32) in zip(R.measure_rows(got[k], ref, k), R.measure_rows(r32[k][0], ref, k)):
-                print(f"OBJ {name}{tag} {row} {calls} {e:.3f} {e32:.3f} {8 * e32 + 4:.2f}")
-    n = R.n_value(inp['tex'].shape[2], R.plan(inp)['max_deferred'])
-    print(f"OBJ {name}{tag} value {calls} {R.value_error(got['value'], ref):.3f} {R.value_error(r32['value'][0], ref):.3f} {n + 2}")
+                print(f"{word} {name}{tag} {row} {calls} {e:.3f} {e32:.3f} {8 * e32 + 4:.2f}")
+    n = R.n_value(inp['tex'].shape[2], R.plan(inp)['max_deferred'], inp.get('mip_levels') is not None)
+    print(f"{word} {name}{tag} value {calls} {R.value_error(got['value'], ref):.3f} {R.value_error(r32['value'][0], ref):.3f} {n + 2}")
     assert R.failures(inp, ref, r32, full, k32 if 'g_tex' in got else None) == [], (name, tag)
 
 
