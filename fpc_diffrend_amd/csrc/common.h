@@ -156,6 +156,31 @@ __device__ __forceinline__ int fpcdr_list_item(int n_entries, int cap) {
     const int idx = x * chunk + j;
     return idx < m ? idx : -1;
 }
+// The walk of a bin list, shared by the list / sweep kernels of objective.hip; body(b, bxi, byi) is the kernel's work on one bin.
+// (k_bins_list / k_bins_queue of rasterize.hip and the two-call kernels of fused.hip spell the same walk out.)
+// One entry of a hinted launch: XCD x takes the x-th eighth of the entries (above); a workgroup without an entry leaves at once.
+template <typename Body>
+__device__ __forceinline__ void fpcdr_list_entry(const int32_t *list, const int32_t *count, int cap, const fpcdr_bin_decode &dc, Body &&body) {
+    const int item = fpcdr_list_item(*count, cap);
+    if (item < 0) return;
+    const int lin = __builtin_amdgcn_readfirstlane(list[item]);
+    int b, byi, bxi;
+    fpcdr_decode_bin(lin, dc, b, byi, bxi);
+    body(b, bxi, byi);
+}
+// The strided sweep of the entries beyond a hinted launch (normally none): first + blockIdx.x, + gridDim.x, ...  The loop variable is
+// scalar by construction, so the loop and the body's barriers stay uniform for the compiler (see k_bins_queue in rasterize.hip).
+template <typename Body>
+__device__ __forceinline__ void fpcdr_list_sweep(const int32_t *list, const int32_t *count, int first, const fpcdr_bin_decode &dc, Body &&body) {
+    const int n = *count;
+    for (int item = first + blockIdx.x; item < n; item += gridDim.x) {
+        const int lin = __builtin_amdgcn_readfirstlane(list[item]);
+        int b, byi, bxi;
+        fpcdr_decode_bin(lin, dc, b, byi, bxi);
+        body(b, bxi, byi);
+        __syncthreads();     // the next bin's first LDS writes must not overtake this bin's last LDS reads
+    }
+}
 
 // ---- region hints (include/fpcdr.h) ----------------------------------------------------------
 // plane: 0 = the bin itself is occupied, 1 = the bin or one of its eight neighbours is

@@ -805,75 +805,48 @@ __device__ __forceinline__ void shade_body(const int b, const int bxi, const int
 // ONE kernel parameter, a struct: the position of ObjArgs in the kernel-argument segment is then offsetof(K, a) (kernarg_objargs)
 struct ShadeK { const int32_t *list; const int32_t *count; int cap, OX, OY; fpcdr_bin_decode dc; ObjArgs a; };      // cap: of a sweep, its first entry
 struct ShadeMipK { const int32_t *list; const int32_t *count; int cap, OX, OY; fpcdr_bin_decode dc; ObjArgs a; MipO ma; };
+// Every list / sweep kernel below is one of the two walks of common.h (fpcdr_list_entry, fpcdr_list_sweep) around its body.
 template <int CS, int BMODE>
 __global__ void __launch_bounds__(ONT) FPCDR_SHADE_WPE k_shade_list(const ShadeK k) {
-    const int item = fpcdr_list_item(*k.count, k.cap);      // (XCD x takes the x-th eighth of the entries: common.h)
-    if (item < 0) return;
-    const int lin = __builtin_amdgcn_readfirstlane(k.list[item]);
-    int b, byi, bxi;
-    fpcdr_decode_bin(lin, k.dc, b, byi, bxi);
-    shade_body<CS, BMODE>(b, bxi, byi, k.OX, k.OY, k.a, kernarg_objargs<ShadeK>());
+    fpcdr_list_entry(k.list, k.count, k.cap, k.dc, [&](int b, int bxi, int byi) {
+        shade_body<CS, BMODE>(b, bxi, byi, k.OX, k.OY, k.a, kernarg_objargs<ShadeK>());
+    });
+}
+template <int CS>
+__global__ void __launch_bounds__(ONT) k_shade_queue(const ShadeK k) {
+    fpcdr_list_sweep(k.list, k.count, k.cap, k.dc, [&](int b, int bxi, int byi) {
+        shade_body<CS, -1>(b, bxi, byi, k.OX, k.OY, k.a, kernarg_objargs<ShadeK>());
+    });
 }
 
 // the WEIGHTED instantiations: the weights as a kernel parameter of their own; one wave a SIMD less than the plain kernel is theirs to take
 #define FPCDR_SHADE_W_WPE __attribute__((amdgpu_waves_per_eu(CS == 1 ? 6 : 1, 8)))
 template <int CS, int BMODE>
 __global__ void __launch_bounds__(ONT) FPCDR_SHADE_W_WPE k_shade_list_w(const ShadeK k, const WgtO wa) {
-    const int item = fpcdr_list_item(*k.count, k.cap);
-    if (item < 0) return;
-    const int lin = __builtin_amdgcn_readfirstlane(k.list[item]);
-    int b, byi, bxi;
-    fpcdr_decode_bin(lin, k.dc, b, byi, bxi);
-    shade_body<CS, BMODE, false, true>(b, bxi, byi, k.OX, k.OY, k.a, kernarg_objargs<ShadeK>(), nullptr, &wa);
+    fpcdr_list_entry(k.list, k.count, k.cap, k.dc, [&](int b, int bxi, int byi) {
+        shade_body<CS, BMODE, false, true>(b, bxi, byi, k.OX, k.OY, k.a, kernarg_objargs<ShadeK>(), nullptr, &wa);
+    });
 }
 template <int CS>
 __global__ void __launch_bounds__(ONT) k_shade_queue_w(const ShadeK k, const WgtO wa) {
-    const int n = *k.count;
-    for (int item = k.cap + blockIdx.x; item < n; item += gridDim.x) {
-        const int lin = __builtin_amdgcn_readfirstlane(k.list[item]);
-        int b, byi, bxi;
-        fpcdr_decode_bin(lin, k.dc, b, byi, bxi);
+    fpcdr_list_sweep(k.list, k.count, k.cap, k.dc, [&](int b, int bxi, int byi) {
         shade_body<CS, -1, false, true>(b, bxi, byi, k.OX, k.OY, k.a, kernarg_objargs<ShadeK>(), nullptr, &wa);
-        __syncthreads();
-    }
+    });
 }
 
-// the MIP instantiation (boundary mode at run time): list form and strided sweep
+// the MIP instantiation (boundary mode at run time)
 template <int CS>
 __global__ void __launch_bounds__(ONT) k_shade_mip_list(const ShadeMipK k) {
-    const int item = fpcdr_list_item(*k.count, k.cap);
-    if (item < 0) return;
-    const int lin = __builtin_amdgcn_readfirstlane(k.list[item]);
-    int b, byi, bxi;
-    fpcdr_decode_bin(lin, k.dc, b, byi, bxi);
-    shade_body<CS, -1, true>(b, bxi, byi, k.OX, k.OY, k.a, kernarg_objargs<ShadeMipK>(), &k.ma);
+    fpcdr_list_entry(k.list, k.count, k.cap, k.dc, [&](int b, int bxi, int byi) {
+        shade_body<CS, -1, true>(b, bxi, byi, k.OX, k.OY, k.a, kernarg_objargs<ShadeMipK>(), &k.ma);
+    });
 }
 // (the level chain as a kernel parameter of its own: as a member of the one struct, indexed at run time inside the loop, it was copied
 //  to a 48-byte private segment -- and a kernel with a private segment is dispatched several times slower, taken or not)
 template <int CS>
 __global__ void __launch_bounds__(ONT) k_shade_mip_queue(const ShadeK k, const MipO ma) {
-    const int n = *k.count;
     const KArgs ka = kernarg_objargs<ShadeK>();
-    for (int item = k.cap + blockIdx.x; item < n; item += gridDim.x) {
-        const int lin = __builtin_amdgcn_readfirstlane(k.list[item]);
-        int b, byi, bxi;
-        fpcdr_decode_bin(lin, k.dc, b, byi, bxi);
-        shade_body<CS, -1, true>(b, bxi, byi, k.OX, k.OY, k.a, ka, &ma);
-        __syncthreads();
-    }
-}
-
-// strided sweep of the entries beyond the hinted launch (normally none; scalar loop variable: see k_bins_queue in rasterize.hip)
-template <int CS>
-__global__ void __launch_bounds__(ONT) k_shade_queue(const ShadeK k) {
-    const int n = *k.count;
-    for (int item = k.cap + blockIdx.x; item < n; item += gridDim.x) {
-        const int lin = __builtin_amdgcn_readfirstlane(k.list[item]);
-        int b, byi, bxi;
-        fpcdr_decode_bin(lin, k.dc, b, byi, bxi);
-        shade_body<CS, -1>(b, bxi, byi, k.OX, k.OY, k.a, kernarg_objargs<ShadeK>());
-        __syncthreads();     // the next bin's first LDS writes must not overtake this bin's last LDS reads
-    }
+    fpcdr_list_sweep(k.list, k.count, k.cap, k.dc, [&](int b, int bxi, int byi) { shade_body<CS, -1, true>(b, bxi, byi, k.OX, k.OY, k.a, ka, &ma); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1303,6 +1276,7 @@ __device__ __forceinline__ void fix_body(const int b, const int bxi, const int b
 __global__ void __launch_bounds__(ONT) k_count_sil(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int OX, int OY,
                                                    fpcdr_bin_decode dc, ObjArgs a) {
     const int n = *count;
+    // (its own walk, not fpcdr_list_sweep: the body keeps nothing in LDS across trips, so it places no barrier behind it)
     for (int item = blockIdx.x; item < n; item += gridDim.x) {      // (uniform trip count)
         const int lin = __builtin_amdgcn_readfirstlane(list[item]);
         int b, byi, bxi;
@@ -1380,73 +1354,38 @@ __global__ void __launch_bounds__(64) k_objective_finish(ObjArgs a, FinishArgs f
     }
 }
 
-template <int CS>
-__global__ void __launch_bounds__(FNT) k_fix_mip_list(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int cap, int OX, int OY,
-                                                      fpcdr_bin_decode dc, ObjArgs a, MipO ma) {
-    const int item = fpcdr_list_item(*count, cap);
-    if (item < 0) return;
-    const int lin = __builtin_amdgcn_readfirstlane(list[item]);
-    int b, byi, bxi;
-    fpcdr_decode_bin(lin, dc, b, byi, bxi);
-    fix_body<CS, 1, true>(b, bxi, byi, OX, OY, a, &ma);
-}
-template <int CS>
-__global__ void __launch_bounds__(FNT) k_fix_mip_queue(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int first, int OX, int OY,
-                                                       fpcdr_bin_decode dc, ObjArgs a, MipO ma) {
-    const int n = *count;
-    for (int item = first + blockIdx.x; item < n; item += gridDim.x) {
-        const int lin = __builtin_amdgcn_readfirstlane(list[item]);
-        int b, byi, bxi;
-        fpcdr_decode_bin(lin, dc, b, byi, bxi);
-        fix_body<CS, 1, true>(b, bxi, byi, OX, OY, a, &ma);
-        __syncthreads();
-    }
-}
-
+// k_fix's kernels over (a.def_list, a.def_count); cap: the launch hint, of a sweep its first entry
 template <int CS, int PASS>
-__global__ void __launch_bounds__(FNT) k_fix_list(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int cap, int OX, int OY,
-                                                  fpcdr_bin_decode dc, ObjArgs a) {
-    const int item = fpcdr_list_item(*count, cap);
-    if (item < 0) return;
-    const int lin = __builtin_amdgcn_readfirstlane(list[item]);
-    int b, byi, bxi;
-    fpcdr_decode_bin(lin, dc, b, byi, bxi);
-    fix_body<CS, PASS>(b, bxi, byi, OX, OY, a);
+__global__ void __launch_bounds__(FNT) k_fix_list(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int cap, int OX, int OY, fpcdr_bin_decode dc,
+        ObjArgs a) {
+    fpcdr_list_entry(list, count, cap, dc, [&](int b, int bxi, int byi) { fix_body<CS, PASS>(b, bxi, byi, OX, OY, a); });
+}
+template <int CS, int PASS>
+__global__ void __launch_bounds__(FNT) k_fix_queue(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int cap, int OX, int OY, fpcdr_bin_decode dc,
+        ObjArgs a) {
+    fpcdr_list_sweep(list, count, cap, dc, [&](int b, int bxi, int byi) { fix_body<CS, PASS>(b, bxi, byi, OX, OY, a); });
 }
 // the WEIGHTED instantiations
 template <int CS, int PASS>
-__global__ void __launch_bounds__(FNT) k_fix_list_w(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int cap, int OX, int OY,
-                                                    fpcdr_bin_decode dc, ObjArgs a, WgtO wa) {
-    const int item = fpcdr_list_item(*count, cap);
-    if (item < 0) return;
-    const int lin = __builtin_amdgcn_readfirstlane(list[item]);
-    int b, byi, bxi;
-    fpcdr_decode_bin(lin, dc, b, byi, bxi);
-    fix_body<CS, PASS, false, true>(b, bxi, byi, OX, OY, a, nullptr, &wa);
+__global__ void __launch_bounds__(FNT) k_fix_list_w(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int cap, int OX, int OY, fpcdr_bin_decode dc,
+        ObjArgs a, WgtO wa) {
+    fpcdr_list_entry(list, count, cap, dc, [&](int b, int bxi, int byi) { fix_body<CS, PASS, false, true>(b, bxi, byi, OX, OY, a, nullptr, &wa); });
 }
 template <int CS, int PASS>
-__global__ void __launch_bounds__(FNT) k_fix_queue_w(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int first, int OX, int OY,
-                                                     fpcdr_bin_decode dc, ObjArgs a, WgtO wa) {
-    const int n = *count;
-    for (int item = first + blockIdx.x; item < n; item += gridDim.x) {
-        const int lin = __builtin_amdgcn_readfirstlane(list[item]);
-        int b, byi, bxi;
-        fpcdr_decode_bin(lin, dc, b, byi, bxi);
-        fix_body<CS, PASS, false, true>(b, bxi, byi, OX, OY, a, nullptr, &wa);
-        __syncthreads();
-    }
+__global__ void __launch_bounds__(FNT) k_fix_queue_w(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int cap, int OX, int OY, fpcdr_bin_decode dc,
+        ObjArgs a, WgtO wa) {
+    fpcdr_list_sweep(list, count, cap, dc, [&](int b, int bxi, int byi) { fix_body<CS, PASS, false, true>(b, bxi, byi, OX, OY, a, nullptr, &wa); });
 }
-template <int CS, int PASS>
-__global__ void __launch_bounds__(FNT) k_fix_queue(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int first, int OX, int OY,
-                                                   fpcdr_bin_decode dc, ObjArgs a) {
-    const int n = *count;
-    for (int item = first + blockIdx.x; item < n; item += gridDim.x) {
-        const int lin = __builtin_amdgcn_readfirstlane(list[item]);
-        int b, byi, bxi;
-        fpcdr_decode_bin(lin, dc, b, byi, bxi);
-        fix_body<CS, PASS>(b, bxi, byi, OX, OY, a);
-        __syncthreads();
-    }
+// the MIP instantiation: pass 1 only (its pass 0 is the plain k_fix_list<CS, 0>)
+template <int CS>
+__global__ void __launch_bounds__(FNT) k_fix_mip_list(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int cap, int OX, int OY, fpcdr_bin_decode dc,
+        ObjArgs a, MipO ma) {
+    fpcdr_list_entry(list, count, cap, dc, [&](int b, int bxi, int byi) { fix_body<CS, 1, true>(b, bxi, byi, OX, OY, a, &ma); });
+}
+template <int CS>
+__global__ void __launch_bounds__(FNT) k_fix_mip_queue(const int32_t *__restrict__ list, const int32_t *__restrict__ count, int cap, int OX, int OY, fpcdr_bin_decode dc,
+        ObjArgs a, MipO ma) {
+    fpcdr_list_sweep(list, count, cap, dc, [&](int b, int bxi, int byi) { fix_body<CS, 1, true>(b, bxi, byi, OX, OY, a, &ma); });
 }
 
 // per-image silhouette classification (same arithmetic as k_sil in antialias.hip).  The kernel is a chain of gathers with two dozen
@@ -1497,6 +1436,61 @@ extern "C" int fpcdr_silhouette_bits(const float *pos, const int32_t *tri, const
     FPCDR_REQUIRE(pos && tri && adj && sil, "null pointer");
     FPCDR_REQUIRE(B > 0 && V > 0 && T > 0 && H > 0 && W > 0 && B <= 65535, "bad sizes");
     return fpcdr_launch_sil(pos, tri, adj, B, V, T, H, W, sil, nullptr, 0, (hipStream_t)stream);
+}
+
+// ---- the launches of one call -------------------------------------------------------------------
+// What they share.  The FORM of the call -- plain, weighted (wgt) or mip (mip) -- selects which kernel each step launches.
+struct ObjLaunch {
+    hipStream_t st;
+    long long nbins;
+    const int32_t *occ_list, *n_occ;      // k_shade: over the occupied bins
+    int cap, cap_d;                       // launch hints of k_shade's list and of k_fix's (a.def_list: the bins k_shade found a deferred pixel in)
+    int OX, OY;
+    fpcdr_bin_decode dc;
+    ObjArgs a;
+    const WgtO *wgt;
+    const MipO *mip;
+    bool wrap_uv;                         // the reference's case (wrap, tri_uv): compile-time constants in the one-channel k_shade
+    bool grads;
+    FinishArgs fin;
+};
+// a hinted list launch and, when the hint lies below the list's bound, the strided sweep of the entries beyond it (same arguments)
+template <typename KL, typename KS, typename... A>
+static void launch_list(const ObjLaunch &o, int cap, unsigned nt, KL list_k, KS sweep_k, const A &...args) {
+    hipLaunchKernelGGL(list_k, dim3(fpcdr_list_grid(cap)), dim3(nt), 0, o.st, args...);
+    if (cap < o.nbins) hipLaunchKernelGGL(sweep_k, dim3(FPCDR_SWEEP_WGS), dim3(nt), 0, o.st, args...);
+}
+template <int CS, int BMODE>
+static void launch_shade(const ObjLaunch &o) {
+    const ShadeK k = {o.occ_list, o.n_occ, o.cap, o.OX, o.OY, o.dc, o.a};
+    if (o.wgt) launch_list(o, o.cap, ONT, k_shade_list_w<CS, BMODE>, k_shade_queue_w<CS>, k, *o.wgt);
+    else if (!o.mip) launch_list(o, o.cap, ONT, k_shade_list<CS, BMODE>, k_shade_queue<CS>, k);
+    else {      // (the level chain: a member of the list kernel's one struct, a parameter of its own in the sweep -- see k_shade_mip_queue)
+        const ShadeMipK mk = {o.occ_list, o.n_occ, o.cap, o.OX, o.OY, o.dc, o.a, *o.mip};
+        hipLaunchKernelGGL(k_shade_mip_list<CS>, dim3(fpcdr_list_grid(o.cap)), dim3(ONT), 0, o.st, mk);
+        if (o.cap < o.nbins) hipLaunchKernelGGL(k_shade_mip_queue<CS>, dim3(FPCDR_SWEEP_WGS), dim3(ONT), 0, o.st, k, *o.mip);
+    }
+}
+template <int CS, int PASS>
+static void launch_fix(const ObjLaunch &o) {
+    const ObjArgs &a = o.a;
+    const auto over_deferred = [&](auto list_k, auto sweep_k, const auto &...more) {
+        launch_list(o, o.cap_d, FNT, list_k, sweep_k, a.def_list, a.def_count, o.cap_d, o.OX, o.OY, o.dc, a, more...);
+    };
+    if (o.wgt) over_deferred(k_fix_list_w<CS, PASS>, k_fix_queue_w<CS, PASS>, *o.wgt);
+    else if (o.mip && PASS == 1) over_deferred(k_fix_mip_list<CS>, k_fix_mip_queue<CS>, *o.mip);      // (the mip form's pass 0 is the plain one)
+    else over_deferred(k_fix_list<CS, PASS>, k_fix_queue<CS, PASS>);
+}
+template <int CS>
+static void launch_objective(const ObjLaunch &o) {
+    if constexpr (CS == 1) {
+        if (o.wrap_uv && !o.mip) launch_shade<1, FPCDR_BOUNDARY_WRAP>(o);
+        else launch_shade<1, -1>(o);
+    } else launch_shade<CS, -1>(o);
+    launch_fix<CS, 0>(o);
+    if (o.grads) launch_fix<CS, 1>(o);
+    const FinishArgs &fin = o.fin;
+    if (fin.esum || fin.value_out || fin.counts_out || fin.skip_out) hipLaunchKernelGGL(k_objective_finish<CS>, dim3(1), dim3(64), 0, o.st, o.a, fin);
 }
 
 // the call of both entries; wgt: the weighted form's kernel parameter (checked by its entry), or null
@@ -1558,24 +1552,6 @@ static int fpcdr_objective_fwd_impl(const fpcdr_objective_params *p, const WgtO 
                  p->bg, p->color_scale, p->grad_scale, (unsigned long long *)p->flags,
                  p->slot_map, (int32_t *)((char *)p->occ + q.occ_hdr) + 1, (int32_t *)((char *)p->occ + q.occ_hdr) + 4, p->rec_slots};
     const fpcdr_bin_decode dc = fpcdr_make_bin_decode(OX, OY);
-    const int cap = (p->cap_occ > 0 && p->cap_occ < nbins) ? p->cap_occ : (int)nbins;
-    const dim3 grid(fpcdr_list_grid(cap));
-    const bool sweep = cap < nbins;
-    const ShadeK shade_k = {occ_list, n_occ, cap, OX, OY, dc, a};
-#define SHADE(CS, BM)                                                                                                             \
-    do {                                                                                                                          \
-        hipLaunchKernelGGL((k_shade_list<CS, BM>), grid, dim3(ONT), 0, st, shade_k);                                               \
-        if (sweep) hipLaunchKernelGGL(k_shade_queue<CS>, dim3(FPCDR_SWEEP_WGS), dim3(ONT), 0, st, shade_k);                        \
-    } while (0)
-    // k_fix: over the bins k_shade found a deferred pixel in (count at occ header [0]; p->cap_def: launch hint)
-    const int cap_d = (p->cap_def > 0 && p->cap_def < nbins) ? p->cap_def : (int)nbins;
-    const dim3 grid_d(fpcdr_list_grid(cap_d));
-    const bool sweep_d = cap_d < nbins;
-#define FIX(CS, PASS)                                                                                                             \
-    do {                                                                                                                          \
-        hipLaunchKernelGGL((k_fix_list<CS, PASS>), grid_d, dim3(FNT), 0, st, a.def_list, a.def_count, cap_d, OX, OY, dc, a);       \
-        if (sweep_d) hipLaunchKernelGGL((k_fix_queue<CS, PASS>), dim3(FPCDR_SWEEP_WGS), dim3(FNT), 0, st, a.def_list, a.def_count, cap_d, OX, OY, dc, a); \
-    } while (0)
     if (p->count_only) {
         // the lists, the id planes and the number of bins that would take a record slot (header [1]), reported through counts_out: what a
         // caller without launch hints needs to size the compact record arrays of the real call (once per batch shape)
@@ -1586,48 +1562,9 @@ static int fpcdr_objective_fwd_impl(const fpcdr_objective_params *p, const WgtO 
         FPCDR_CHECK_LAUNCH();
         return FPCDR_OK;
     }
-    const bool grads = p->grad_pos || p->grad_tex;
-    const FinishArgs fin = {p->counts_out, p->counts_seq, p->bg_sumsq, p->bg_coeff, p->n_total, p->value_out, p->grad_tex ? 1 : 0,
-                            p->skip_out, p->rec_slots > 0 ? 1 : 0};
     FPCDR_REQUIRE(!p->value_out || p->n_total > 0.0, "value_out needs n_total > 0");
-#define FINISH(CS)                                                                                                                \
-    do {                                                                                                                          \
-        if (fin.esum || fin.value_out || fin.counts_out || fin.skip_out) hipLaunchKernelGGL(k_objective_finish<CS>, dim3(1), dim3(64), 0, st, a, fin); \
-    } while (0)
-    if (wgt) {      // the weighted instantiations (no mip: refused by the entry)
-        const WgtO wa = *wgt;
-#define SHADE_W(CS, BM)                                                                                                           \
-    do {                                                                                                                          \
-        hipLaunchKernelGGL((k_shade_list_w<CS, BM>), grid, dim3(ONT), 0, st, shade_k, wa);                                         \
-        if (sweep) hipLaunchKernelGGL(k_shade_queue_w<CS>, dim3(FPCDR_SWEEP_WGS), dim3(ONT), 0, st, shade_k, wa);                  \
-    } while (0)
-#define FIX_W(CS, PASS)                                                                                                           \
-    do {                                                                                                                          \
-        hipLaunchKernelGGL((k_fix_list_w<CS, PASS>), grid_d, dim3(FNT), 0, st, a.def_list, a.def_count, cap_d, OX, OY, dc, a, wa); \
-        if (sweep_d) hipLaunchKernelGGL((k_fix_queue_w<CS, PASS>), dim3(FPCDR_SWEEP_WGS), dim3(FNT), 0, st, a.def_list, a.def_count, cap_d, OX, OY, dc, a, wa); \
-    } while (0)
-        if (p->C == 1) {
-            if (p->boundary_mode == FPCDR_BOUNDARY_WRAP && p->tri_uv) SHADE_W(1, FPCDR_BOUNDARY_WRAP);
-            else SHADE_W(1, -1);
-            FIX_W(1, 0);
-            if (grads) FIX_W(1, 1);
-            FINISH(1);
-        } else if (p->C == 3) {
-            SHADE_W(3, -1);
-            FIX_W(3, 0);
-            if (grads) FIX_W(3, 1);
-            FINISH(3);
-        } else {
-            SHADE_W(4, -1);
-            FIX_W(4, 0);
-            if (grads) FIX_W(4, 1);
-            FINISH(4);
-        }
-#undef SHADE_W
-#undef FIX_W
-    } else
-    if (p->mip) {      // the reference's enable_mip branch (fit.py:153-155)
-        MipO ma;
+    MipO ma;      // the reference's enable_mip branch (fit.py:153-155); the weighted form has none (refused by its entry)
+    if (p->mip) {
         ma.lv.tex[0] = p->tex;
         ma.lv.grad[0] = p->grad_tex;
         for (int lvl = 1; lvl <= FPCDR_MAX_MIP; ++lvl) {
@@ -1635,43 +1572,17 @@ static int fpcdr_objective_fwd_impl(const fpcdr_objective_params *p, const WgtO 
             ma.lv.grad[lvl] = (lvl <= p->n_levels && p->grad_tex) ? p->grad_tex_mip[lvl - 1] : nullptr;
         }
         ma.n_levels = p->n_levels;
-        const ShadeMipK shade_mip_k = {occ_list, n_occ, cap, OX, OY, dc, a, ma};
-#define SHADE_MIP(CS)                                                                                                             \
-    do {                                                                                                                          \
-        hipLaunchKernelGGL(k_shade_mip_list<CS>, grid, dim3(ONT), 0, st, shade_mip_k);                                             \
-        if (sweep) hipLaunchKernelGGL(k_shade_mip_queue<CS>, dim3(FPCDR_SWEEP_WGS), dim3(ONT), 0, st, shade_k, ma);               \
-    } while (0)
-#define FIX_MIP(CS)                                                                                                               \
-    do {                                                                                                                          \
-        hipLaunchKernelGGL(k_fix_mip_list<CS>, grid_d, dim3(FNT), 0, st, a.def_list, a.def_count, cap_d, OX, OY, dc, a, ma);       \
-        if (sweep_d) hipLaunchKernelGGL(k_fix_mip_queue<CS>, dim3(FPCDR_SWEEP_WGS), dim3(FNT), 0, st, a.def_list, a.def_count, cap_d, OX, OY, dc, a, ma); \
-    } while (0)
-        if (p->C == 1) { SHADE_MIP(1); FIX(1, 0); if (grads) FIX_MIP(1); FINISH(1); }
-        else if (p->C == 3) { SHADE_MIP(3); FIX(3, 0); if (grads) FIX_MIP(3); FINISH(3); }
-        else { SHADE_MIP(4); FIX(4, 0); if (grads) FIX_MIP(4); FINISH(4); }
-#undef SHADE_MIP
-#undef FIX_MIP
-    } else
-    if (p->C == 1) {
-        if (p->boundary_mode == FPCDR_BOUNDARY_WRAP && p->tri_uv) SHADE(1, FPCDR_BOUNDARY_WRAP);      // the reference's case, as compile-time constants
-        else SHADE(1, -1);
-        FIX(1, 0);
-        if (grads) FIX(1, 1);
-        FINISH(1);
-    } else if (p->C == 3) {
-        SHADE(3, -1);
-        FIX(3, 0);
-        if (grads) FIX(3, 1);
-        FINISH(3);
-    } else {
-        SHADE(4, -1);
-        FIX(4, 0);
-        if (grads) FIX(4, 1);
-        FINISH(4);
     }
-#undef SHADE
-#undef FIX
-#undef FINISH
+    const auto hint = [&](int cap) { return (cap > 0 && cap < nbins) ? cap : (int)nbins; };      // (no hint: one workgroup per bin, no sweep)
+    const ObjLaunch o = {st, nbins, occ_list, n_occ, hint(p->cap_occ), hint(p->cap_def), OX, OY, dc, a, wgt, (!wgt && p->mip) ? &ma : nullptr,
+                         p->boundary_mode == FPCDR_BOUNDARY_WRAP && p->tri_uv, p->grad_pos || p->grad_tex,
+                         {p->counts_out, p->counts_seq, p->bg_sumsq, p->bg_coeff, p->n_total, p->value_out, p->grad_tex ? 1 : 0, p->skip_out,
+                          p->rec_slots > 0 ? 1 : 0}};
+    switch (p->C) {
+    case 1: launch_objective<1>(o); break;
+    case 3: launch_objective<3>(o); break;
+    default: launch_objective<4>(o);
+    }
     FPCDR_CHECK_LAUNCH();
     return FPCDR_OK;
 }

@@ -174,6 +174,8 @@ __device__ __forceinline__ void bin_ids(BinLds &lds, const int b, const int bxi,
 // Dispatching one workgroup per bin of the whole batch costs 0.21 ms for 588 k workgroups that mostly leave at once; the caller
 // sizes this launch from the count of an EARLIER call (`cap`), and whatever lies beyond it is swept up by the strided form
 // below, so the result never depends on the hint.
+// (Both spell the walk out instead of calling fpcdr_list_entry / fpcdr_list_sweep of common.h: through the helper the compiler schedules
+//  k_bins_list's inner loop, tuned instruction by instruction, differently.)
 __global__ void __launch_bounds__(256) FPCDR_BINS_WPE k_bins_list(const int32_t *__restrict__ list, const int32_t *__restrict__ count,
                                               int cap, int OX, int OY, fpcdr_bin_decode dc, int T, int H, int W,
                                               const TriRec *__restrict__ recs, const TriBox *__restrict__ boxes,

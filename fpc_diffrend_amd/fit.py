@@ -942,7 +942,7 @@ class Fitter:
         # the pixel loss of an all-background image, per (frame, camera): depends on the targets only (sparse objective)
         t = self.targets
         self.target_bg_sumsq = dr.reference_background_sumsq(t.reshape(-1, *self.resolution), BACKGROUND).reshape(t.shape[:2])
-        self._bg_sum_key = None      # (the cached sum over the whole shard, loss_and_backward)
+        self._shard_sums = {}        # (the cached sums over the whole shard, _rows_sum)
         self.full_targets = self.targets      # (always the captures; `targets` is the active pyramid level's, the same tensor without one)
         # ---- the masks of the captures, sharded and reduced exactly as the targets: 8 bit [F_local, n_cam, H, W], or None ----
         self.masks = None
@@ -957,7 +957,6 @@ class Fitter:
                 raise ValueError(f"the masks {tuple(self.masks.shape)} do not match the targets {tuple(self.targets.shape)}")
         self.full_masks = self.masks
         self._wsum = None                     # (the sum of the weights of the last iteration on the robust term, for the step log)
-        self._bg_wsum_key = None
         self._bg_wsum = {}                    # weighted one-pass: (level, kind, scale) -> [F_local * n_cam, 2] f64, cached like target_bg_sumsq
         # ---- pyramid levels: per factor in use (targets, (H, W), target_bg_sumsq, masks), each made from this rank's full-size targets ----
         self._levels, self._level = None, 1
@@ -1121,7 +1120,7 @@ class Fitter:
             return
         self.targets, self.resolution, self.target_bg_sumsq, self.masks = self._levels[s]
         self.enable_mip = bool(self.cfg.enable_mip or (s > 1 and self.cfg.pyramid_mip))
-        self._bg_sum_key, self._targets_f32 = None, None
+        self._shard_sums, self._targets_f32 = {}, None
         self._level = s
 
     @staticmethod
@@ -1181,6 +1180,21 @@ class Fitter:
                 return t      # every frame (one rank, frames_per_step = 0): no slice node, whose backward is a zero-fill and a copy
             return t[ids] if dim == 0 else t[:, ids]
         return t.index_select(dim, ids)
+
+    def _step_masks(self, rows):
+        """The masks of the rows a batch names (_target_rows) [n, H, W], or None without masks."""
+        return self._take(self.masks.reshape(-1, *self.resolution), 0, rows) if self.masks is not None else None
+
+    def _rows_sum(self, name, key, table, rows):
+        """The sum over `rows` of a per-image table [F_local * n_cam, ...].  A slice is the whole shard, every view: the same numbers every
+        step, kept under `name` for as long as `key` and the slice stay what they were; an index tensor is summed anew."""
+        if isinstance(rows, slice):
+            key = (key, rows.start, rows.stop)
+            if self._shard_sums.get(name, (None,))[0] != key:
+                self._shard_sums[name] = (key, table[rows].sum(0))
+            return self._shard_sums[name][1]
+        t = table.index_select(0, rows)
+        return t.reshape(()) if t.numel() == 1 else t.sum(0)
 
     def _target_rows(self, frame_ids, view_ids=None):
         """The rows of the flat [F_local * n_cam, H, W] view of `targets` (and of target_bg_sumsq, flattened) that a batch names: frame numbers
@@ -1460,26 +1474,12 @@ class Fitter:
         if one_shot:
             bg_sum = None
             if cfg.sparse_objective and not weighted_shot:
-                bg = self.target_bg_sumsq.reshape(-1)
-                if isinstance(rows, slice):      # the whole shard, every view: the same number every step
-                    if self._bg_sum_key != rows:
-                        self._bg_sum_key, self._bg_sum_all = rows, bg[rows].sum()
-                    bg_sum = self._bg_sum_all
-                else:
-                    bg = bg.index_select(0, rows)
-                    bg_sum = bg.reshape(()) if bg.numel() == 1 else bg.sum()
+                bg_sum = self._rows_sum('bg_sumsq', None, self.target_bg_sumsq.reshape(-1), rows)
             self._skip_cur = self._skip_target() if (cfg.one_pass and cfg.sparse_objective) else None
             wkw = {}
             if weighted_shot:      # the same weights pixel_loss_robust takes, and the level's all-background share of this term
-                mask = self._take(self.masks.reshape(-1, *self.resolution), 0, rows) if self.masks is not None else None
-                bgw = self._level_bg_wsum(term[1], term[2])
-                if isinstance(rows, slice):      # the whole shard, every view: the same two numbers every step of this level and kind
-                    key = (self._level, term[1], term[2], rows.start, rows.stop)
-                    if self._bg_wsum_key != key:
-                        self._bg_wsum_key, self._bg_wsum_all = key, bgw[rows].sum(0)
-                    bgw = self._bg_wsum_all
-                else:
-                    bgw = bgw.index_select(0, rows).sum(0)
+                mask = self._step_masks(rows)
+                bgw = self._rows_sum('bg_wsum', (self._level, term[1], term[2]), self._level_bg_wsum(term[1], term[2]), rows)
                 sums = (None, torch.empty(1, dtype=torch.float64, device=self.device))
                 wkw = dict(robust=(term[1], term[2]), mask=mask, face_weights=self.face_w, weight_outside=cfg.weight_outside,
                            saturation=cfg.saturation, ref_bg_wsum=bgw, wsum_out=sums[1], check_weights=False)
@@ -1494,8 +1494,7 @@ class Fitter:
         elif cfg.fused_loss:
             weights = {}
             if robust:
-                mask = self._take(self.masks.reshape(-1, *self.resolution), 0, rows) if self.masks is not None else None
-                weights = dict(mask=mask, face_weights=self.face_w, weight_outside=cfg.weight_outside, saturation=cfg.saturation)
+                weights = dict(mask=self._step_masks(rows), face_weights=self.face_w, weight_outside=cfg.weight_outside, saturation=cfg.saturation)
             sums, g_colour = pixel_term_loss(term, colour, rast_out, ref, n_total, **weights)
             self._backward(colour, g_colour, reg, *terms)
             value = sums[0].to(torch.float32) / n_total

@@ -816,6 +816,27 @@ def robust_args(kind, scale, weight_outside=1.0, saturation=0):
     return _lib.ROBUST_KIND[kind], inv_c, weight_outside, int(saturation)
 
 
+def _weight_tensors(ref_u8, mask, face_weights, check_weights, device=None, n_tri=None):
+    """The per-pixel and per-face weights of a robust call, checked -> (mask, face_weights), contiguous, either None as given: mask uint8
+    [B,H,W] like ref_u8; face_weights float32 [T], T > 0, finite and >= 0 (a read-back: check_weights=False skips it).  What only the
+    objective knows: device, the device of pos, on which both must lie, and n_tri, the triangles of tri, one entry each."""
+    where = "" if device is None else " on the device of pos"
+    if mask is not None:
+        _check_tensor('mask', mask, torch.uint8, 3)
+        if tuple(mask.shape) != tuple(ref_u8.shape) or (device is not None and mask.device != device):
+            raise ValueError(f"mask must be [B,H,W] = {tuple(ref_u8.shape)}{where} (got {tuple(mask.shape)})")
+        mask = mask.contiguous()
+    if face_weights is not None:
+        _check_tensor('face_weights', face_weights, torch.float32, 1)
+        T = int(face_weights.shape[0])
+        if T == 0 or (n_tri is not None and T != n_tri) or (device is not None and face_weights.device != device):
+            raise ValueError(f"face_weights must have one entry per triangle{'' if n_tri is None else f' ({n_tri})'}{where} (got {T})")
+        face_weights = face_weights.detach().contiguous()
+        if check_weights and not bool((torch.isfinite(face_weights) & (face_weights >= 0)).all()):
+            raise ValueError("face_weights must be finite and not negative")
+    return mask, face_weights
+
+
 def robust_loss_call(colour, rast, ref_u8, kind, scale, grad_scale, mask=None, face_weights=None, weight_outside=1.0, saturation=0,
                      background=45.0 / 255.0, want_grad=True, check_weights=True):
     """One fpcdr_robust_loss call ("Robust loss rule"): -> (sums [2] f64 = (sum of w * rho, sum of w), grad_scale * d sums[0] /
@@ -825,20 +846,8 @@ def robust_loss_call(colour, rast, ref_u8, kind, scale, grad_scale, mask=None, f
     uncovered pixels; saturation 1..255: capture pixels at or above it count nothing.  The weights are constants: they get no gradient."""
     kind_no, inv_c, weight_outside, saturation = robust_args(kind, scale, weight_outside, saturation)
     colour, rast, ref_u8 = _pixel_tensors(colour, rast, ref_u8)
-    if mask is not None:
-        _check_tensor('mask', mask, torch.uint8, 3)
-        if tuple(mask.shape) != tuple(ref_u8.shape):
-            raise ValueError(f"mask must be [B,H,W] = {tuple(ref_u8.shape)} (got {tuple(mask.shape)})")
-        mask = mask.contiguous()
-    T = 0
-    if face_weights is not None:
-        _check_tensor('face_weights', face_weights, torch.float32, 1)
-        T = int(face_weights.shape[0])
-        if T == 0:
-            raise ValueError("face_weights must have one entry per triangle (got none)")
-        face_weights = face_weights.detach().contiguous()
-        if check_weights and not bool((torch.isfinite(face_weights) & (face_weights >= 0)).all()):
-            raise ValueError("face_weights must be finite and not negative")
+    mask, face_weights = _weight_tensors(ref_u8, mask, face_weights, check_weights)
+    T = 0 if face_weights is None else int(face_weights.shape[0])
     with torch.cuda.device(colour.device):
         sums = torch.zeros(2, dtype=torch.float64, device=colour.device)
         grad = torch.empty_like(colour) if want_grad else None
@@ -1287,18 +1296,7 @@ def pixel_objective(glctx, pos, tri, uv, uv_tri, tex, ref_u8, resolution, n_tota
         kind, scale = robust if robust is not None else ('l2', None)
         kind_no, inv_c, weight_outside, saturation = robust_args(kind, scale, weight_outside, saturation)
         ref_u8 = ref_u8.contiguous()
-        if mask is not None:
-            _check_tensor('mask', mask, torch.uint8, 3)
-            if tuple(mask.shape) != tuple(ref_u8.shape) or mask.device != pos.device:
-                raise ValueError(f"mask must be [B,H,W] = {tuple(ref_u8.shape)} on the device of pos (got {tuple(mask.shape)})")
-            mask = mask.contiguous()
-        if face_weights is not None:
-            _check_tensor('face_weights', face_weights, torch.float32, 1)
-            if int(face_weights.shape[0]) != int(tri.shape[0]) or face_weights.device != pos.device:
-                raise ValueError(f"face_weights must have one entry per triangle ({tri.shape[0]}) on the device of pos (got {tuple(face_weights.shape)})")
-            face_weights = face_weights.detach().contiguous()
-            if check_weights and not bool((torch.isfinite(face_weights) & (face_weights >= 0)).all()):
-                raise ValueError("face_weights must be finite and not negative")
+        mask, face_weights = _weight_tensors(ref_u8, mask, face_weights, check_weights, device=pos.device, n_tri=int(tri.shape[0]))
         if wsum_out is not None and not (torch.is_tensor(wsum_out) and wsum_out.dtype == torch.float64 and wsum_out.device == pos.device
                                          and wsum_out.numel() >= 1 and wsum_out.is_contiguous()):
             raise ValueError("wsum_out must be a contiguous float64 tensor of at least one element on the device of pos")

@@ -18,6 +18,10 @@ autograd: six cases x five kinds and scales x four option sets).  The whole file
   wsum against fpcdr_robust_loss's sums[1]    e 0.64 u at most (islands/C1/wrap, w_out 0.25, sat 100; its own bound 4.5), 0.14 of its bound at most
   neutral weights against the plain call      value 0; grad_pos 0 .. 3.0e-08; grad_tex 3.1e-08 .. 1.2e-07       1e-4
           two plain calls against each other  value 0; grad_pos 0 .. 4.5e-09; grad_tex 4.9e-08 .. 1.2e-07       (for scale)
+  hints frozen at (1, 1, 1): the sweeps       12 occupied bins, 12 with a deferred pixel in both cases; against autograd value 0 .. 8.3e-08,
+    (Charbonnier c = 20, w_out 0.25, sat 100) grad_pos 1.5e-07 .. 2.1e-07, grad_tex 1.7e-07 .. 5.1e-07 (bounds as above); against the unfrozen
+                                              call value 0, grad_pos 4.0e-09 .. 5.3e-08, grad_tex 6.1e-08 .. 8.3e-08 (1e-4); wsum e 0.30 u at most
+                                              (its bound 6.7).  The same at the parent of the change that adds the row (2.1e-07 / 5.4e-07 at most)
   all weights 0 (three ways, three kinds)     value, grad_pos, grad_tex exactly 0
   texels no weighted pixel reaches            93 of 720 (12 of them under pixels of weight 0), 96 of 720 (15): exactly those are 0.0 in grad_tex
   background sums, 9 pixel counts x 2 bases   sum w0 rho e 0.60 u at most (0.08 of its bound), sum w0 2.90 u (n = 16, mask, w_out 0.25; 0.44 of its bound)
@@ -151,6 +155,44 @@ def test_neutral_weights_through_the_weighted_kernels_are_the_plain_objective(ta
             print(f"WOBJ neutral {tag} {label} {name} rel_l2={e:.2e} two plain runs {spread:.2e} bound=1e-4")
             assert e < 1e-4, (tag, label, name, e)
         assert float(wsum) == float(g['ref'].numel() * g['C'])      # every weight is 1: w - w0 is exactly 0 everywhere
+    dr.clear_hints()
+
+
+@pytest.mark.parametrize("tag", ['soup/C1/wrap', 'soup/C3/clamp'])
+def test_weighted_sweeps_with_hints_frozen_at_one_entry(tag, oracle_ops):
+    """Launch hints frozen at (1, 1, 1): k_shade_queue_w and k_fix_queue_w<CS, 0 / 1> take every entry of their lists but the first (12
+    occupied bins, all 12 with a deferred pixel, in both cases: objective_ref.plan).  The twin of test_gpu_objective_ref.py's."""
+    import fpc_diffrend_amd.ops as dr
+    g = _inputs(tag, oracle_ops)
+    pos, tex, rast, col = _chain(dr, g)
+    kind, c, w_out, sat = 'charbonnier', 20.0, 0.25, 100
+    kw = dict(robust=(kind, c), mask=g['mask'], face_weights=g['face_w'], weight_outside=w_out, saturation=sat)
+    dr.clear_hints()
+    free = _objective(dr, g, wsum_out=torch.zeros(1, dtype=torch.float64, device='cuda'), **kw)
+    h = dr._list_hints[next(k for k in dr._list_hints if k[0] == 'onepass')]
+    h.poll()
+    h.caps, h.frozen = (1, 1, 1), True
+    wsum = torch.zeros(1, dtype=torch.float64, device='cuda')
+    got = _objective(dr, g, wsum_out=wsum, **kw)
+    torch.cuda.synchronize()
+    n_def, n_occ = int(h.host[0]), int(h.host[3])
+    # against autograd through the operators: the first test's bars
+    w32, _ = RR.weights(rast[..., 3], g['ref'], g['mask'], g['face_w'], w_out, sat, dtype=torch.float32)
+    loss = RR.loss_plain(col, rast[..., 3], g['ref'], kind, c, weight=w32.cuda())
+    gp, gt = torch.autograd.grad(loss, (pos, tex), retain_graph=True)
+    ev = abs(float(got[0]) - float(loss)) / abs(float(loss))
+    ep, et = float(R.rel_l2(got[1], gp)), float(R.rel_l2(got[2], gt))
+    # ... and against the unfrozen call (atomics reorder: the neutral-weights test's bar)
+    ef = [float(R.rel_l2(x.reshape(-1), r.reshape(-1))) for x, r in zip(got, free)]
+    print(f"WOBJ sweeps {tag} occupied bins {n_occ} with a deferred pixel {n_def}: value {float(got[0]):.6f} torch {float(loss):.6f} rel={ev:.2e} "
+          f"g_pos rel_l2={ep:.2e} g_tex rel_l2={et:.2e}; against the unfrozen call value {ef[0]:.2e} g_pos {ef[1]:.2e} g_tex {ef[2]:.2e}")
+    assert float(gp.abs().max()) > 0 and float(gt.abs().max()) > 0
+    assert ev <= 1e-5 and ep < 1e-4 and et < 1e-4, (tag, ev, ep, et)
+    assert all(e < 1e-4 for e in ef), (tag, ef)
+    sums, _ = dr.robust_loss_call(col.detach(), rast, g['ref'], kind, c, 1.0, mask=g['mask'], face_weights=g['face_w'], weight_outside=w_out,
+                                  saturation=sat, want_grad=False)
+    long_sum(f"sweeps {tag}", 'wsum', wsum[0], sums[1], sums[1], (w32.sum(dtype=torch.float32) * g['C']).double())
+    assert n_occ > 1 and n_def > 1, (tag, n_occ, n_def)      # the sweeps had work
     dr.clear_hints()
 
 
