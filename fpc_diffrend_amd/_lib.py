@@ -211,6 +211,8 @@ SYMBOLS = {
     "fpcdr_tex_prior": (_int, [_p, _p, _p, _p, ctypes.c_float, ctypes.c_float, ctypes.c_float, _p, _p, _p, _p, _i, _i, _i, _p]),
     "fpcdr_blend_fwd": (_int, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "fpcdr_blend_bwd_w": (_int, [_p, _p, _p, _i, _i, _i, _p]),
+    "fpcdr_blend_bwd_w_workspace_bytes": (_sz, [_i, _i, _i]),
+    "fpcdr_blend_bwd_w_ws": (_int, [_p, _p, _p, _p, _sz, _i, _i, _i, _p]),
     "fpcdr_blend_bwd_basis": (_int, [_p, _p, _p, _i, _i, _i, _p]),
     "fpcdr_rig_weights_fwd": (_int, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "fpcdr_rig_weights_bwd": (_int, [_p, _p, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p]),

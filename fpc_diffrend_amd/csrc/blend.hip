@@ -255,6 +255,166 @@ __global__ void __launch_bounds__(256) k_blend_bwd_w(const float *__restrict__ B
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Slab form of the weight gradient (K <= LDS_KMAX, 16-byte aligned Bmat and gout, a caller's workspace): the basis is read ONCE and
+// nothing is added atomically.  k_blend_bwd_w above fetches every 600-byte basis row as five 128-byte strips from five workgroups and
+// ends in 88 adders on each address of grad_w.  Here one workgroup takes a slab of rows for ALL K columns and walks it in chunks of RC
+// rows: a chunk of Bmat is one contiguous, 16-byte aligned run of RC K floats and goes to LDS as it lies (float4 in, float4 out, no
+// (row, k) bookkeeping: an MFMA B read is 32 consecutive floats of one row per lane half, conflict-free at any row stride); the 32
+// frames' gradient segments are fetched as aligned float4 as well and shifted to their row on the way into LDS (frame stride RC + 1:
+// the 32 frames of an A read land on 32 banks).  The next chunk's loads are in flight while this one is on the matrix cores.  The four
+// waves split the chunk's rows, each holds all KT = K / 32 column tiles; their tiles are summed through LDS in a fixed order and the
+// slab's [F][K] partial goes to the workspace.  k_blend_bwd_w_sum adds the slabs in a fixed order: grad_w is the same bits every run.
+constexpr int WS_WGS = 256;      // slabs are sized for about one workgroup per CU (the partials cost 2 x slabs x F K floats of traffic)
+static int ws_slab_rows(int M) { return fpcdr_cdiv(fpcdr_cdiv(M, WS_WGS) < 1 ? 1 : fpcdr_cdiv(M, WS_WGS), 64) * 64; }
+
+template <int KT>
+__global__ void __launch_bounds__(256) k_blend_bwd_w_slab(const float *__restrict__ Bmat, const float *__restrict__ gout,
+                                                          float *__restrict__ part, int M, int K, int F, int slab_rows) {
+    constexpr int RC = KT <= 6 ? 64 : 32;           // rows per chunk (s_b + s_g stay under 64 KB)
+    constexpr int GS = RC + 1;
+    constexpr int NQB = RC * KT / 32;               // float4 per thread of a Bmat chunk (>= RC K / 4 / 256)
+    constexpr int NQF = RC / 4 + 1;                 // aligned float4 that cover RC floats from any start
+    constexpr int NQG = (32 * NQF + 255) / 256;
+    extern __shared__ float smem[];
+    float *s_b = smem;                              // [RC][K] as in memory (+ 32 floats the last column tile reads and never uses)
+    float *s_g = smem + ((RC * K + 32 + 3) & ~3);   // [32 frames][GS]
+    float *s_red = smem;                            // [KT * 16][64]: one wave's tiles (aliases the chunk once it is consumed)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int col = lane & 31, h = lane >> 5;
+    const int slab0 = blockIdx.x * slab_rows, slab_end = min(slab0 + slab_rows, M);
+    const int f0 = blockIdx.y * 32;
+    const long long total = (long long)F * M;
+    const int n4 = RC * K / 4;
+    float4 vb[NQB], vg[NQG];
+    auto load_chunk = [&](int r0) {
+        const float *__restrict__ src = Bmat + (size_t)r0 * K;      // (r0 is a multiple of 32: 16-byte aligned)
+        const int nb = min(RC, slab_end - r0) * K;                  // floats of the chunk that exist; the rest is zero
+#pragma unroll
+        for (int j = 0; j < NQB; ++j) {
+            const int q = tid + 256 * j, e0 = 4 * q;
+            vb[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (q < n4) {
+                if (e0 + 3 < nb) vb[j] = *reinterpret_cast<const float4 *>(src + e0);
+                else {
+                    if (e0 < nb) vb[j].x = src[e0];
+                    if (e0 + 1 < nb) vb[j].y = src[e0 + 1];
+                    if (e0 + 2 < nb) vb[j].z = src[e0 + 2];
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NQG; ++j) {
+            const int idx = tid + 256 * j, f = idx / NQF, q = idx - f * NQF;
+            vg[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (f < 32 && f0 + f < F) {
+                const long long e0 = (((long long)(f0 + f) * M + r0) & ~3ll) + 4 * q;      // (what lies beyond the rows is dropped below)
+                if (e0 + 3 < total) vg[j] = *reinterpret_cast<const float4 *>(gout + e0);
+                else {
+                    if (e0 < total) vg[j].x = gout[e0];
+                    if (e0 + 1 < total) vg[j].y = gout[e0 + 1];
+                    if (e0 + 2 < total) vg[j].z = gout[e0 + 2];
+                }
+            }
+        }
+    };
+    auto store_chunk = [&](int r0) {
+        const int rows = min(RC, slab_end - r0);
+#pragma unroll
+        for (int j = 0; j < NQB; ++j) {
+            const int q = tid + 256 * j;
+            if (q < n4) *reinterpret_cast<float4 *>(s_b + 4 * q) = vb[j];
+        }
+#pragma unroll
+        for (int j = 0; j < NQG; ++j) {
+            const int idx = tid + 256 * j, f = idx / NQF, q = idx - f * NQF;
+            if (f < 32) {
+                const int r = 4 * q - (int)(((long long)(f0 + f) * M + r0) & 3ll);      // row of the quad's first float
+                const float vv[4] = {vg[j].x, vg[j].y, vg[j].z, vg[j].w};
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (r + c >= 0 && r + c < RC) s_g[f * GS + r + c] = r + c < rows ? vv[c] : 0.0f;      // every row of every frame is written
+            }
+        }
+    };
+    f32x16 acc[KT];
+#pragma unroll
+    for (int t = 0; t < KT; ++t) acc[t] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // each wave a quarter of the chunk's rows, lane half h a contiguous half of that (the k index trick of the file's head)
+    const int rbase = wave * (RC / 4) + h * (RC / 8);
+    load_chunk(slab0);
+    for (int r0 = slab0; r0 < slab_end; r0 += RC) {
+        store_chunk(r0);
+        __syncthreads();
+        if (r0 + RC < slab_end) load_chunk(r0 + RC);      // (uniform) in flight behind the MFMAs
+#pragma unroll
+        for (int s = 0; s < RC / 8; ++s) {
+            const float a = s_g[col * GS + rbase + s];                      // A[frame][row]
+            const float *pb = s_b + (rbase + s) * K + col;                  // B[row][k]
+#pragma unroll
+            for (int t = 0; t < KT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, pb[32 * t], acc[t], 0, 0, 0);
+        }
+        __syncthreads();                                  // the chunk is consumed: the next one, or s_red, may overwrite it
+    }
+    // ((wave 0 + wave 1) + wave 2) + wave 3, one wave's tiles through LDS at a time
+    for (int w = 1; w < 4; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int t = 0; t < KT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s_red[(t * 16 + r) * 64 + lane] = acc[t][r];
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int t = 0; t < KT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[t][r] += s_red[(t * 16 + r) * 64 + lane];
+        }
+        __syncthreads();
+    }
+    if (wave == 0) {
+        float *__restrict__ dst = part + (size_t)blockIdx.x * F * K;
+#pragma unroll
+        for (int t = 0; t < KT; ++t) {
+            const int k = 32 * t + col;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int f = f0 + acc_row(r, lane);
+                if (f < F && k < K) dst[(size_t)f * K + k] = acc[t][r];
+            }
+        }
+    }
+}
+
+// grad_w[e] += part[0][e] + part[1][e] + ... in a fixed order (e over the F K entries): sixteen threads per entry take every sixteenth
+// slab in ascending order -- a few loads each, all in flight together --, their sums are added in ascending order.  No atomics: the
+// call is the only writer of grad_w on its stream.
+__global__ void __launch_bounds__(256) k_blend_bwd_w_sum(const float *__restrict__ part, float *__restrict__ grad_w, int nslabs, int n) {
+    __shared__ float s_p[16][17];
+    const int tid = threadIdx.x, j = tid & 15, g = tid >> 4;
+    const int e = blockIdx.x * 16 + j;
+    float s = 0.0f;
+    if (e < n) {
+        for (int s0 = g; s0 < nslabs; s0 += 256) {      // (one trip: ws_slab_rows makes at most WS_WGS = 256 slabs)
+            // sixteen loads requested together, then added in slab order (a loop of load -> add waited for every load in turn: 6.9 us)
+            float v[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) v[u] = s0 + 16 * u < nslabs ? part[(size_t)(s0 + 16 * u) * n + e] : 0.0f;
+#pragma unroll
+            for (int u = 0; u < 16; ++u) s += v[u];
+        }
+    }
+    s_p[g][j] = s;
+    __syncthreads();
+    if (tid < 16 && e < n) {
+        float t = s_p[0][tid];
+#pragma unroll
+        for (int i = 1; i < 16; ++i) t += s_p[i][tid];
+        grad_w[e] += t;
+    }
+}
+
 // grad_B[i][k] = sum_f gout[f][i] w[f][k];  D[i = coord][j = k]
 __global__ void __launch_bounds__(256) k_blend_bwd_basis(const float *__restrict__ w, const float *__restrict__ gout,
                                                          float *__restrict__ grad_B, int M, int K, int F) {
@@ -371,6 +531,45 @@ extern "C" int fpcdr_blend_bwd_w(const float *Bmat, const float *grad_out, float
     FPCDR_REQUIRE(fpcdr_cdiv(M, SLAB) <= 65535 && fpcdr_cdiv(F, 32) <= 65535, "problem too large for one launch");
     dim3 grid(fpcdr_cdiv(K, 32), fpcdr_cdiv(M, SLAB), fpcdr_cdiv(F, 32));
     hipLaunchKernelGGL(k_blend_bwd_w, grid, dim3(256), 0, (hipStream_t)stream, Bmat, grad_out, grad_w, M, K, F);
+    FPCDR_CHECK_LAUNCH();
+    return FPCDR_OK;
+}
+
+extern "C" size_t fpcdr_blend_bwd_w_workspace_bytes(int32_t M, int32_t K, int32_t F) {
+    if (M <= 0 || K <= 0 || F <= 0) return 0;
+    return (size_t)fpcdr_cdiv(M, ws_slab_rows(M)) * (size_t)F * (size_t)K * sizeof(float);
+}
+
+template <int KT>
+static void launch_bwd_w_slab(const float *Bmat, const float *grad_out, float *part, int M, int K, int F, int slab_rows, hipStream_t st) {
+    constexpr int RC = KT <= 6 ? 64 : 32;
+    const size_t chunk = (size_t)((RC * K + 32 + 3) & ~3) + 32 * (RC + 1), red = (size_t)KT * 16 * 64;
+    hipLaunchKernelGGL(k_blend_bwd_w_slab<KT>, dim3(fpcdr_cdiv(M, slab_rows), fpcdr_cdiv(F, 32)), dim3(256),
+                       (chunk > red ? chunk : red) * sizeof(float), st, Bmat, grad_out, part, M, K, F, slab_rows);
+}
+
+extern "C" int fpcdr_blend_bwd_w_ws(const float *Bmat, const float *grad_out, float *grad_w, void *workspace, size_t workspace_bytes,
+                                    int32_t M, int32_t K, int32_t F, void *stream) {
+    FPCDR_REQUIRE(Bmat && grad_out && grad_w, "null pointer");
+    FPCDR_REQUIRE(M > 0 && K > 0 && F > 0, "sizes must be positive");
+    FPCDR_REQUIRE(!workspace || workspace_bytes >= fpcdr_blend_bwd_w_workspace_bytes(M, K, F), "workspace too small");
+    if (!workspace || K > LDS_KMAX || (((size_t)Bmat | (size_t)grad_out | (size_t)workspace) & 15) != 0 || fpcdr_cdiv(F, 32) > 65535 ||
+        (long long)F * K >= (1ll << 30))
+        return fpcdr_blend_bwd_w(Bmat, grad_out, grad_w, M, K, F, stream);
+    const int slab_rows = ws_slab_rows(M), nslabs = fpcdr_cdiv(M, slab_rows);
+    float *part = (float *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    switch (fpcdr_cdiv(K, 32)) {
+    case 1: launch_bwd_w_slab<1>(Bmat, grad_out, part, M, K, F, slab_rows, st); break;
+    case 2: launch_bwd_w_slab<2>(Bmat, grad_out, part, M, K, F, slab_rows, st); break;
+    case 3: launch_bwd_w_slab<3>(Bmat, grad_out, part, M, K, F, slab_rows, st); break;
+    case 4: launch_bwd_w_slab<4>(Bmat, grad_out, part, M, K, F, slab_rows, st); break;
+    case 5: launch_bwd_w_slab<5>(Bmat, grad_out, part, M, K, F, slab_rows, st); break;
+    case 6: launch_bwd_w_slab<6>(Bmat, grad_out, part, M, K, F, slab_rows, st); break;
+    default: launch_bwd_w_slab<7>(Bmat, grad_out, part, M, K, F, slab_rows, st); break;
+    }
+    FPCDR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_blend_bwd_w_sum, dim3(fpcdr_cdiv((long long)F * K, 16)), dim3(256), 0, st, part, grad_w, nslabs, F * K);
     FPCDR_CHECK_LAUNCH();
     return FPCDR_OK;
 }

@@ -100,7 +100,9 @@ class _blend_func(torch.autograd.Function):
         g_w = None
         if ctx.needs_input_grad[2]:
             g_w = _pool_zeros(ctx.pool, tuple(w.shape), w.device)
-            _lib.call("fpcdr_blend_bwd_w", _ptr(Bmat), _ptr(g), _ptr(g_w), M, K, F, _stream())
+            # per-slab partial sums instead of float atomics (csrc/blend.hip): the workspace is scratch for this one call
+            ws = torch.empty(lib.fpcdr_blend_bwd_w_workspace_bytes(M, K, F) // 4, dtype=torch.float32, device=w.device)
+            _lib.call("fpcdr_blend_bwd_w_ws", _ptr(Bmat), _ptr(g), _ptr(g_w), _ptr(ws), ws.numel() * 4, M, K, F, _stream())
         return g_vb, g_B, g_w, None
 
 

@@ -477,6 +477,14 @@ int fpcdr_blend_fwd(const float *v_base, const float *Bmat, const float *w, floa
 /* grad_w[f][k] += sum_i grad_out[f][i] * Bmat[i][k]  (accumulated: zero grad_w first)           */
 int fpcdr_blend_bwd_w(const float *Bmat, const float *grad_out, float *grad_w, int32_t M, int32_t K, int32_t F,
                       void *stream);
+/* The same sum with a workspace instead of float atomics (pure additions: FPCDR_ABI_VERSION stays 16): the basis is read once, per-slab
+ * partial sums [slabs,F,K] go to `workspace` and are added into grad_w in a fixed order, so grad_w holds the same bits on every run.
+ * grad_w is accumulated into as above (zero it first).  workspace: at least fpcdr_blend_bwd_w_workspace_bytes(M, K, F) bytes of
+ * device memory, 16-byte aligned, contents irrelevant on entry and undefined afterwards.  workspace NULL, K > 224, or a Bmat,
+ * grad_out or workspace that is not 16-byte aligned: the call is fpcdr_blend_bwd_w.                                              */
+size_t fpcdr_blend_bwd_w_workspace_bytes(int32_t M, int32_t K, int32_t F);
+int fpcdr_blend_bwd_w_ws(const float *Bmat, const float *grad_out, float *grad_w, void *workspace, size_t workspace_bytes,
+                         int32_t M, int32_t K, int32_t F, void *stream);
 /* grad_B[i][k] = sum_f grad_out[f][i] * w[f][k]      (free-form basis m3, reference fit.py:60; overwritten) */
 int fpcdr_blend_bwd_basis(const float *w, const float *grad_out, float *grad_B, int32_t M, int32_t K, int32_t F,
                           void *stream);
