@@ -59,7 +59,29 @@ _build_mips / _fold_mip_grads.
 The level's choices (lo = raw < 0, hi = raw > n_levels and with them the gate, l0) and the tap choices of both levels join choices() /
 margins(); the level is measured in texture_ref's L_s plus the footprint's own scale through |d level / d da_k|.  plan()['mipbins'] restates
 the prepass (mlb, the extent of the prepared coordinates over the pass-0 rows, the half-period view under wrap), place() for the three
-windows of MipWinCaps and the routing of every pixel's two levels into a window or to memory -- it proves reach only, evaluate() never calls it."""
+windows of MipWinCaps and the routing of every pixel's two levels into a window or to memory -- it proves reach only, evaluate() never calls it.
+
+The WEIGHTED call (inp['weights'] = dict(kind, c, mask [B,H,W] uint8 or None, face_weights [T] or None, weight_outside, saturation); absent:
+the calls above, their code path untouched) is DESIGN.md 3, "Weighted objective rule", on the same skeleton, for
+tests/test_gpu_objective_weighted_ref.py and tests/test_objective_weighted_ref.py: k_shade_list_w / k_shade_queue_w, k_fix_list_w / k_fix_queue_w,
+rho_psi, mask_weight, face_weight, loss_grad_w and the wsum slots of fpcdr_objective_weighted_fwd (_Weights below).
+    the weights     robust_ref.weights' rules: wm = mask byte * float32(1 / 255), 0 where sat > 0 and ref >= sat; a covered pixel has
+                    w = wm * face_w[id - 1] (an id past the table weighs 0) and w0 = wm * w_outside; they are coefficients (no scale of their own)
+    rho, psi        robust_ref.rho_psi with inv_c = robust_ref.inv_scale(c); S_psi = S_d and S_rho = S_d^2 (robust_ref's docstring: |psi'| <= 1,
+                    |rho'| <= 2 |d| <= 2 S_d), then times the weight: a weight of 0 gives the exact 0 with S = 0.  There S_d = ref + |a| is a
+                    magnitude; here it is CARRIED from the vertices and is thousands of times |d| on a pixel of an ill-conditioned triangle,
+                    where its square says nothing (on `islands/clamp` the value's scale came to 2.5e6 times the value, and a background
+                    share weighed by w instead of w0 moved the value by 0.41 u of it).  So S_rho is the smaller of S_d^2 and 2 |d| S_d, the
+                    scale the plain statement's product d d carries: never above the rule's, first order where the rule's is not
+    k_shade         value += w rho(dd) - w0 rho(d0);  gq = K (w psi(dd))
+    k_fix<0>        value += (w rho(dn) - w0 rho(d0)) - (w rho(dd) - w0 rho(d0));  g_aa[r] = K (w psi(dn))
+    k_fix<1>        dl = go - K (w psi(rf - cme cs)): the gq above
+    value           (the float sums + C * sum over ALL pixels of w0 rho(d0)) / n_total
+    wsum            C * sum over all pixels of w0 + C * sum over the covered pixels of (w - w0); S the same sums of w0 and of w + w0
+The weights add no float32 decision (mask bytes, captures and ids are integers): choices(), margins() and the settled geometry of the cases are
+those of the plain call.  The kernels skip a pixel whose gq is all zero and a difference dl that is all zero, so a pixel has a term when its weight
+is positive or when it is the partner of a blend entry whose receiver has one (_structure: `has`); an entry with a weight-0 receiver has no term
+at all (g_aa[r] = 0: nothing for d alpha / d pos, nothing for esum)."""
 import functools
 import math
 
@@ -68,6 +90,7 @@ import torch
 
 import antialias_ref as AR
 import rasterize_ref as RR
+import robust_ref as RB
 import texture_ref as TR
 from fitstep_ref import BACKGROUND, U, bg_sumsq, measure, rel_l2      # noqa: F401  (re-exported)
 from rasterize_ref import GATE_MARGIN, SETTLE_MARGIN, Q, _clip, _inp, _where
@@ -100,10 +123,28 @@ N_VALUE_PIXEL_MIP, N_VALUE_BLEND_MIP = 16 + TR.N_LEVEL + 6, 16 + TR.N_LEVEL + 12
 # The bar is (n_value + 2) u of S, as in fitstep_ref.py: n_value + 1 is the first-order bound of a path of n_value operations, and one more u
 # stands for the second-order terms (n^2 u^2, far below u at these counts).  It is a worst-case count against a scale summed over thousands
 # of pixels, so measured errors are a hundredth of a u: this bar sees a wrong term, a wrong factor or a lost pixel, not a lost bit.
-def n_value(C, max_deferred_in_a_bin, mip=False):
+def n_value(C, max_deferred_in_a_bin, mip=False, kind=None):
+    """kind: the weighted call's (None: the plain and the mip call)."""
     trips = -(-4 * max_deferred_in_a_bin // 64)
     pixel, blend = (N_VALUE_PIXEL_MIP, N_VALUE_BLEND_MIP) if mip else (N_VALUE_PIXEL, N_VALUE_BLEND)
+    if kind is not None:
+        assert not mip
+        pixel, blend = N_VALUE_PIXEL_W[kind], N_VALUE_BLEND_W[kind]
     return max(pixel + 4 * C, blend + 2 * C * trips) + 6 + 1
+
+
+# The weighted call.  Where rho's scale is S_d^2 (robust_ref's docstring), not the 2 |d| S_d a product carries, what d has lost counts TWICE:
+# |rho'| <= 2 |d| <= 2 S_d for every kind (where it is 2 |d| S_d it counts once: the count below holds for both), and d = dd is 27 operations
+# down the path above (dn, of a blended pixel: 32).  Behind d, relative to
+# |rho| <= d^2 <= S_d^2 and by robust_ref's rules (a product n_a + n_b + 1, a sum max + 1, a product with 2 exact, d itself counted already):
+#     L2              d d 1
+#     Charbonnier     z 1, t = z z 3, 1 + t 4, the root 5, 1 + h 6; 2 (d d) 1; the quotient 1 + 6 + 1 = 8
+#     Geman-McClure   z 1, t 3, k = 1 + t 4; d d 1; the quotient 1 + 4 + 1 = 6
+# then the weight's two operations (wm, wm * face weight) and its product with rho, 3, and the subtraction of w0 rho(d0) (a shorter path), 1:
+# 2 * 27 + 4 + rho's.  A blended pixel: 2 * 32 + 4 + rho's, and the subtraction of the plain term, 1.  The accumulations are n_value's.
+N_RHO = {'l2': 1, 'charbonnier': 8, 'geman_mcclure': 6}
+N_VALUE_PIXEL_W = {k: 2 * 27 + 4 + n for k, n in N_RHO.items()}
+N_VALUE_BLEND_W = {k: 2 * 32 + 5 + n for k, n in N_RHO.items()}
 
 
 def _coef(x):
@@ -484,6 +525,43 @@ class _State:
     pass
 
 
+class _Weights:
+    """The weights of a weighted call per pixel, in `dtype`, by robust_ref.weights (mask_weight, face_weight; k_fix forms them by the same
+    expressions): w [P] (covered pixels: wm * face weight; 0 elsewhere), w0 [P] (ALL pixels: wm * w_outside), and rho / psi of a residual Q
+    (rho_psi) with the scales of the module docstring."""
+
+    def __init__(self, inp, dtype):
+        wt = inp['weights']
+        assert inp.get('mip_levels') is None, "the mip call has no weighted form"
+        self.kind, self.dtype = wt['kind'], dtype
+        assert self.kind in RB.KINDS
+        self.inv_c = RB.inv_scale(wt['c']) if self.kind != 'l2' else 0.0
+        ids = inp['ids'].detach().cpu().long()
+        sat = int(wt.get('saturation', 0))
+        if MUTANT == 'saturation_as_greater' and sat > 0:
+            sat += 1
+        rast_w = ids.float()
+        if MUTANT == 'face_weight_of_id':
+            rast_w = torch.where(ids > 0, ids + 1, ids).float()
+        kw = dict(mask=wt.get('mask'), w_outside=float(wt.get('weight_outside', 1.0)), sat=sat, dtype=dtype)
+        w, cov = RB.weights(rast_w, inp['ref_u8'], face_w=wt.get('face_weights'), **kw)
+        w0, _ = RB.weights(torch.zeros_like(rast_w), inp['ref_u8'], face_w=None, **kw)
+        self.w0 = w0.reshape(-1)
+        self.w = torch.where(cov, w, torch.zeros((), dtype=dtype)).reshape(-1)
+        if MUTANT == 'w0_for_a_covered_pixel':
+            self.w = torch.where(cov.reshape(-1), self.w0, self.w)
+
+    def rho(self, d):
+        v = RB.rho_psi(d.v, self.kind, self.inv_c, RB.sqrt_rounded)[0]      # (the device's sqrtf is correctly rounded; torch's float32 root is not)
+        if MUTANT == 'charbonnier_rho_without_2' and self.kind == 'charbonnier':
+            v = v * 0.5
+        return Q(v, torch.minimum(d.S * d.S, 2.0 * d.v.abs() * d.S))      # (module docstring: S_rho)
+
+    def psi(self, d):
+        v = d.v if MUTANT == 'psi_without_s' else RB.rho_psi(d.v, self.kind, self.inv_c, RB.sqrt_rounded)[1]
+        return Q(v, d.S)
+
+
 def _tex_coord(px, inp, dtype):
     uvt = inp['uv'].detach().to('cpu', dtype)[inp['uv_tri'].detach().cpu().long()[px.t]]      # [n,3,2]
     q = [[_inp(uvt[:, k, c]) for c in range(2)] for k in range(3)]
@@ -546,7 +624,7 @@ def choices(inp):
     clamp states and tap cells per axis), taps0 (the lookup at uv = (0, 0)), rast (z/w as k_shade stores it, ids), adj, D
     (antialias_ref.decisions).  Cached for a case's inputs: treat as read-only."""
     if _case_cache.get(inp.get('name')) is inp:
-        return _choices_cached(inp['name'])
+        return _choices_cached(inp.get('base', inp['name']))      # (with_weights: the weights add no choice, the case's own serve)
     ch = {}
     _forward(inp, torch.float32, ch)
     return ch
@@ -555,7 +633,8 @@ def choices(inp):
 def evaluate(inp, dtype=torch.float64):
     """The statement on the choices of choices(inp) -> dict: 'value' (value, S) scalars, 'g_pos' (value, S) [B,V,4], 'g_tex' (value, S)
     [Ht,Wt,C], and what the tests look at: 'st' (the forward), 'D', 'E', 'hit' / 'hit2' (flat pixel indices of the blended covered pixels /
-    of the pixels k_fix<1> visits), 'gq' [n,C] values, 'dd' [n,C] values, 'esum' (C values), 'n_esum' entries, 'terms' per texel."""
+    of the pixels k_fix<1> visits), 'gq' [n,C] values, 'dd' [n,C] values, 'esum' (C values), 'n_esum' entries, 'terms' per texel.  The weighted call
+    (inp['weights']) adds 'wsum' (value, S) and 'w', 'w0' [n], the covered pixels' weights."""
     ch = choices(inp)
     st = _forward(inp, dtype, ch)
     px, lk, lk0, D = st.px, st.lk, st.lk0, ch['D']
@@ -572,7 +651,13 @@ def evaluate(inp, dtype=torch.float64):
     rf = _inp(rf_all[pix])
     d0 = rf - Q(bgs.expand(n), bgs.abs().expand(n))
     dd = [rf - lk.col[c] * CS_SCALE for c in range(C)]
-    gq = [Kq * dd[c] for c in range(C)]
+    wg = _Weights(inp, dtype) if inp.get('weights') is not None else None
+    if wg is None:
+        gq = [Kq * dd[c] for c in range(C)]
+    else:      # the weights of the covered pixels as coefficients; what every covered pixel's background term weighed
+        w, w0 = _coef(wg.w[pix]), _coef(wg.w0[pix])
+        w0rho = w0 * wg.rho(d0)
+        gq = [Kq * (w * wg.psi(dd[c])) for c in range(C)]
     mip = st.mip is not None
     if mip:      # one gradient per level of the chain, folded into level 0's at the end (_fold_mip_grads)
         L_tex = [torch.zeros(h * w * C, dtype=dtype) for h, w in lk.dims]
@@ -620,6 +705,12 @@ def evaluate(inp, dtype=torch.float64):
     hit = torch.unique(er[rc])
     hrow = rowof[hit]
     dn, gaa = [], []
+    if wg is not None:
+        wh = _at(w, hrow)
+        if MUTANT == 'partner_weight_in_k_fix0':      # the weight of (one of) the receiver's partners, an empty one's being its w0
+            wp = torch.where(cov, wg.w, wg.w0)
+            wp[er[rc]] = torch.where(cov, wg.w, wg.w0)[eo[rc]]
+            wh = _coef(wp[hit])
     for c in range(C):
         delta = _at(amt, rc) * (_at(colP[c], eo[rc]) - _at(colP[c], er[rc]))
         av, aS = torch.zeros(P, dtype=dtype), torch.zeros(P, dtype=dtype)
@@ -629,7 +720,7 @@ def evaluate(inp, dtype=torch.float64):
         dn.append(_at(rf, hrow) - acc * CS_SCALE)
         gv_, gS_ = torch.zeros(P, dtype=dtype), torch.zeros(P, dtype=dtype)
         gv_[pix], gS_[pix] = gq[c].v, gq[c].S
-        g_hit = Kq * dn[c]
+        g_hit = Kq * dn[c] if wg is None else Kq * (wh * wg.psi(dn[c]))
         gv_[hit], gS_[hit] = g_hit.v, g_hit.S
         gaa.append(Q(gv_, gS_))
 
@@ -649,6 +740,8 @@ def evaluate(inp, dtype=torch.float64):
             goS.index_add_(0, eo[rc][o_cov], term.S[o_cov])
         go = Q(gov[hit2], goS[hit2]) + _at(gaa[c], hit2)
         d = go - _at(gq[c], h2row)
+        if MUTANT == 'unweighted_gq_taken_away_in_k_fix1' and wg is not None:
+            d = go - Kq * wg.psi(_at(dd[c], h2row))
         if MUTANT == 'difference_term_sign_flipped':
             d = -d
         if MUTANT == 'difference_term_dropped':
@@ -678,7 +771,16 @@ def evaluate(inp, dtype=torch.float64):
     # ---- the value ----
     tv_, tS_ = torch.zeros((), dtype=dtype), torch.zeros((), dtype=dtype)
     d0h = _at(d0, hrow)
-    for c in range(C):
+    for c in range(C if wg is not None else 0):      # the weighted call: the same two sums, every term with its weight
+        rho_dd = wg.rho(dd[c])
+        plain = w * rho_dd - w0rho
+        tv_ = tv_ + plain.v.sum()
+        tS_ = tS_ + (plain.S + (w * rho_dd).v.abs() + w0rho.v.abs()).sum()
+        w_h, w0rho_h, rho_ddh, rho_dn = _at(w, hrow), _at(w0rho, hrow), _at(rho_dd, hrow), wg.rho(dn[c])
+        corr = (w_h * rho_dn - w0rho_h) - (w_h * rho_ddh - w0rho_h)
+        tv_ = tv_ + corr.v.sum()
+        tS_ = tS_ + (corr.S + (w_h * rho_dn).v.abs() + (w_h * rho_ddh).v.abs() + 2.0 * w0rho_h.v.abs()).sum()
+    for c in range(C if wg is None else 0):
         plain = dd[c] * dd[c] if MUTANT == 'background_share_for_covered_pixels_too' else dd[c] * dd[c] - d0 * d0
         tv_ = tv_ + plain.v.sum()
         tS_ = tS_ + (plain.S + (dd[c].v * dd[c].v).abs() + d0.v * d0.v).sum()
@@ -690,9 +792,20 @@ def evaluate(inp, dtype=torch.float64):
         tS_ = tS_ + (corr.S + dn[c].v * dn[c].v + ddh.v * ddh.v + 2.0 * d0h.v * d0h.v).sum()
     b = float(np.float32(float(inp.get('background', BACKGROUND)) * 255.0))      # what reference_background_sumsq hands fpcdr_ref_bg_sumsq
     bg_v, bg_S = bg_sumsq(inp['ref_u8'], b, dtype)
+    extra = {}
+    if wg is not None:      # fpcdr_ref_bg_wsum: w0 rho(d0) and w0 over ALL pixels; the covered pixels' w - w0 from k_shade's wsum slots
+        d0_all = _inp(rf_all) - Q(torch.tensor(b, dtype=dtype).expand(P), torch.tensor(b, dtype=dtype).abs().expand(P))
+        w0_bg = wg.w0
+        if MUTANT == 'background_share_weighted_by_w':
+            w0_bg = torch.where(cov, wg.w, wg.w0)
+        share = _coef(w0_bg) * wg.rho(d0_all)
+        bg_v, bg_S = share.v.reshape(B, -1).sum(dim=1), share.S.reshape(B, -1).sum(dim=1)      # (per image, as bg_sumsq sums)
+        covered = w.v if MUTANT == 'wsum_without_minus_w0' else w.v - w0.v
+        extra = {'wsum': (float(C) * wg.w0.sum() + float(C) * covered.sum(), float(C) * wg.w0.sum() + float(C) * (w.v + w0.v).sum()),
+                 'w': w.v, 'w0': w0.v}
     value = (tv_ + float(C) * bg_v.sum()) / float(n_total)
     value_S = (tS_ + float(C) * bg_S.sum()) / float(n_total)
-    return {'value': (value, value_S), 'g_pos': (G_pos.reshape(B, px.V, 4), S_pos.reshape(B, px.V, 4)),
+    return {**extra, 'value': (value, value_S), 'g_pos': (G_pos.reshape(B, px.V, 4), S_pos.reshape(B, px.V, 4)),
             'g_tex': (G_tex.reshape(Ht, Wt, C), S_tex.reshape(Ht, Wt, C)), 'st': st, 'D': D, 'E': E, 'hit': hit, 'hit2': hit2, 'pix': pix,
             'cov': cov, 'rowof': rowof, 'gq': torch.stack([q.v for q in gq], 1), 'dd': torch.stack([q.v for q in dd], 1),
             'dn': torch.stack([q.v for q in dn], 1) if hit.numel() else torch.zeros(0, C, dtype=dtype), 'n_esum': n_esum, 'col': col_img,
@@ -737,22 +850,34 @@ def _structure(inp):
     cov = torch.zeros(B * H * W, dtype=torch.bool)
     cov[pix] = True
     level_count = None
+    rc = cov[D.er]
+    has = None
+    if inp.get('weights') is not None:
+        # the weighted call: entries with a weight-0 receiver have no term, and a pixel has one (`has`) when its weight is positive or it is
+        # the partner of an entry that has (module docstring); w > 0 is a matter of integers and of the face weights' zeros
+        wpos = _Weights(inp, torch.float32).w > 0
+        rc = rc & wpos[D.er]
+        has_all = wpos.clone()
+        has_all[D.eo[rc & cov[D.eo]]] = True
+        has = has_all[pix]
     if st.mip is None:
         count = torch.zeros(Ht * Wt, dtype=torch.int64)
         for k in range(4):
-            count.index_add_(0, lk.flat[k][lk.valid[k]], torch.ones(int(lk.valid[k].sum()), dtype=torch.int64))
+            ok = lk.valid[k] if has is None else lk.valid[k] & has
+            count.index_add_(0, lk.flat[k][ok], torch.ones(int(ok.sum()), dtype=torch.int64))
         anyv = lk.valid[0] | lk.valid[1] | lk.valid[2] | lk.valid[3]
     else:      # the taps of every level, folded: a coarse texel's terms reach its four fine ones
         level_count = lk.level_reach()
         count = fold_levels([c.reshape(h, w) for c, (h, w) in zip(level_count, lk.dims)], scale=None).reshape(-1)
         anyv = lk.any_valid()
-    rc = cov[D.er]
     n_esum = int((rc & ~cov[D.eo]).sum())
     reach = count > 0
     if n_esum:
         for k in range(4):
             reach[lk0.flat[k][lk0.valid[k]]] = True
     term = (ch['open0'] | ch['open1']) & ((lk.mu != 0) | (lk.mv != 0)) & anyv
+    if has is not None:
+        term = term & has
     off_centre = (px.fx.v != 0) | (px.fy.v != 0)      # (the w column's term is -fx g_x - fy g_y: none at the image's centre)
     if st.mip is not None:      # the footprint's gradient reaches x, y and w of all three vertices wherever the level's gate is open
         through_level = lk.passes & anyv
@@ -769,7 +894,7 @@ def _structure(inp):
     for r_ in (rows, rows_w):
         r_[(base + D.E['va'][D.ei, D.ee])[ent]] = True
         r_[(base + D.E['vb'][D.ei, D.ee])[ent]] = True
-    return dict(reach=reach, rows=rows, rows_w=rows_w, count=count, n_esum=n_esum, cov=cov, pix=pix, st=st, D=D, level_count=level_count)
+    return dict(reach=reach, rows=rows, rows_w=rows_w, count=count, n_esum=n_esum, cov=cov, pix=pix, st=st, D=D, level_count=level_count, has=has)
 
 
 def predicted_zeros(inp):
@@ -789,8 +914,24 @@ def predicted_zeros(inp):
 def float32_in_kernel_order(inp):
     """The per-pixel float32 statement, one rounding per operation, in the kernels' order -> dict: 'r' (evaluate(inp, float32)), 'texel'
     [m] flat indices of the texels that hold exactly one plain term, of a pixel outside every blend, and no share of the empty pixels, and
-    'g_tex' [m,C] the float32 product gq * w_k there; 'gq_w' [n,4,C] all the products."""
-    r = evaluate(inp, torch.float32)
+    'g_tex' [m,C] the float32 product gq * w_k there; 'gq_w' [n,4,C] all the products.  Cached for a case's inputs: treat as read-only."""
+    if _case_cache.get(inp.get('name')) is inp and MUTANT is None:
+        return (_kernel_order_cached_weighted if 'base' in inp else _kernel_order_cached)(inp['name'])
+    return _kernel_order(inp)
+
+
+@functools.lru_cache(maxsize=None)
+def _kernel_order_cached(name):
+    return _kernel_order(_case_cache[name])
+
+
+@functools.lru_cache(maxsize=4)      # (with_weights: see _reference_cached_weighted)
+def _kernel_order_cached_weighted(name):
+    return _kernel_order(_case_cache[name])
+
+
+def _kernel_order(inp):
+    r = reference(inp, torch.float32)
     if r['st'].mip is not None:      # (the mip call's one-term texels are held through `mip/magnified/C1/wrap`, on the non-mip statement)
         C = inp['tex'].shape[2]
         return {'r': r, 'texel': torch.zeros(0, dtype=torch.int64), 'g_tex': torch.zeros(0, C), 'gq_w': None}
@@ -807,6 +948,8 @@ def float32_in_kernel_order(inp):
     texel, val = [], []
     for k in range(4):
         ok = lk.valid[k] & single[lk.flat[k]] & ~in_blend
+        if s['has'] is not None:      # (the weighted call: the one term is a pixel's that has one -- gq = (-2 cs gs) (w psi) in float32)
+            ok = ok & s['has']
         texel.append(lk.flat[k][ok])
         val.append(prod[ok, k])
     return {'r': r, 'texel': torch.cat(texel), 'g_tex': torch.cat(val), 'gq_w': prod}
@@ -1013,7 +1156,14 @@ def plan(inp):
 
 def id_planes(inp):
     """The id planes the call leaves (include/fpcdr.h): (triangle + 1) | silhouette bits << 24 per pixel -> [B,H,W] int64."""
+    if _case_cache.get(inp.get('name')) is inp and 'base' in inp:      # (with_weights: the planes are the case's own)
+        return _id_planes_cached(inp['base'])
     return plan(inp)['code']
+
+
+@functools.lru_cache(maxsize=None)
+def _id_planes_cached(name):
+    return plan(_case_cache[name])['code']
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1344,15 +1494,96 @@ def with_mip(inp, max_mip_level=None):
     return _case_cache[name]
 
 
+# The weighted call (tests/test_gpu_objective_weighted_ref.py): seeded weights on the settled cases above.  The captures lie in 1 .. 140, so a
+# saturation level of 100 takes a good share of them.  Every case runs the five kinds and scales under the full option set, and each other
+# option set of tests/test_gpu_weighted_objective.py -- (w_outside, sat) = (0.25, 0), (0, 0), (0, 100) with mask and face weights, the mask
+# alone, the face weights alone -- under one kind other than L2.
+WEIGHTED_CASE_IDS = ['soup/C1/wrap/seam', 'soup/C3/clamp', 'soup/C4/zero', 'islands/wrap', 'islands/clamp', 'borders', 'mesh/B3', 'tiny/1x1',
+                     'magnified/C1/wrap']      # (the last for its thousands of one-term texels: the others have none to four)
+WEIGHT_SAT = 100
+# tag: (kind, c, mask, face weights, w_outside, sat)
+WEIGHT_SETS = {
+    'l2/all': ('l2', None, True, True, 0.25, WEIGHT_SAT),
+    'charbonnier2/all': ('charbonnier', 2.0, True, True, 0.25, WEIGHT_SAT),
+    'charbonnier20/all': ('charbonnier', 20.0, True, True, 0.25, WEIGHT_SAT),
+    'geman2/all': ('geman_mcclure', 2.0, True, True, 0.25, WEIGHT_SAT),
+    'geman20/all': ('geman_mcclure', 20.0, True, True, 0.25, WEIGHT_SAT),
+    'charbonnier2/w0.25': ('charbonnier', 2.0, True, True, 0.25, 0),
+    'geman20/w0': ('geman_mcclure', 20.0, True, True, 0.0, 0),
+    'charbonnier20/w0,sat': ('charbonnier', 20.0, True, True, 0.0, WEIGHT_SAT),
+    'geman2/mask': ('geman_mcclure', 2.0, True, False, 1.0, 0),
+    'charbonnier2/faces': ('charbonnier', 2.0, False, True, 1.0, 0),
+}
+WEIGHT_TAGS = list(WEIGHT_SETS)
+NEUTRAL = ('l2', None, False, False, 1.0, 0)      # tag 'neutral': the plain objective through the weighted statement
+
+
+def case_weights(inp):
+    """The case's own mask [B,H,W] uint8 -- random bytes with a block of 0 and a block of 255 (at 45 x 70: rows 5 .. 13, columns 8 .. 29 and rows
+    20 .. 39, columns 25 .. 59), the bytes 1 and 254 on two covered pixels outside the blocks (an image of one pixel: 254) -- and face weights
+    [T] float32: random below 1.5, a fifth of them exactly 0, face 0 at 0 and face 1 at 1.25.  Seeded by the case's name."""
+    B, (H, W), T = inp['pos'].shape[0], inp['res'], inp['tri'].shape[0]
+    g = torch.Generator().manual_seed(77 + sum(ord(ch) for ch in inp.get('base', inp['name'])))
+    mask = torch.randint(0, 256, (B, H, W), generator=g, dtype=torch.uint8)
+    block = torch.zeros(H, W, dtype=torch.bool)
+    mask[:, H * 5 // 45:H * 14 // 45, W * 8 // 70:W * 30 // 70] = 0
+    mask[:, H * 20 // 45:H * 40 // 45, W * 25 // 70:W * 60 // 70] = 255
+    block[H * 5 // 45:H * 14 // 45, W * 8 // 70:W * 30 // 70] = True
+    block[H * 20 // 45:H * 40 // 45, W * 25 // 70:W * 60 // 70] = True
+    free = torch.nonzero(((inp['ids'].detach().cpu() > 0) & ~block).reshape(-1), as_tuple=True)[0]
+    free = free[torch.randperm(free.numel(), generator=g)][:2]
+    for p, byte in zip(free.tolist(), (254, 1)):
+        mask.reshape(-1)[p] = byte
+    face_w = torch.rand(T, generator=g) * 1.5
+    face_w[torch.rand(T, generator=g) < 0.2] = 0.0
+    face_w[0] = 0.0
+    if T > 1:
+        face_w[1] = 1.25
+    return dict(mask=mask, face_weights=face_w)
+
+
+def with_weights(inp, tag):
+    """The inputs of a case for the weighted call under WEIGHT_SETS[tag] ('neutral': NEUTRAL), a copy under the name case | tag, cached like a
+    case; inp['base'] names the case, whose choices it shares."""
+    name = inp['name'] + '|' + tag
+    if name not in _case_cache:
+        kind, c, use_mask, use_faces, w_out, sat = NEUTRAL if tag == 'neutral' else WEIGHT_SETS[tag]
+        cw = case_weights(inp)
+        _case_cache[name] = dict(inp, name=name, base=inp['name'], tag=tag, weights=dict(
+            kind=kind, c=c, mask=cw['mask'] if use_mask else None, face_weights=cw['face_weights'] if use_faces else None, weight_outside=w_out,
+            saturation=sat))
+    return _case_cache[name]
+
+
+@functools.lru_cache(maxsize=None)
+def _max_deferred_cached(name):
+    return plan(_case_cache[name])['max_deferred']
+
+
+def value_count(inp):
+    """n_value of a call: its channels, the most deferred pixels of a bin (a matter of ids and silhouettes, the same with weights), its form."""
+    if _case_cache.get(inp.get('name')) is inp and 'base' in inp:
+        most = _max_deferred_cached(inp['base'])
+    else:
+        most = plan(inp)['max_deferred']
+    wt = inp.get('weights')
+    return n_value(inp['tex'].shape[2], most, inp.get('mip_levels') is not None, None if wt is None else wt['kind'])
+
+
 @functools.lru_cache(maxsize=None)
 def _reference_cached(name, dtype):
+    return evaluate(_case_cache[name], dtype)
+
+
+@functools.lru_cache(maxsize=8)      # (with_weights: ninety variants of a few cases, each used by one test at a time)
+def _reference_cached_weighted(name, dtype):
     return evaluate(_case_cache[name], dtype)
 
 
 def reference(inp, dtype=torch.float64):
     """evaluate() on a case's inputs.  Cached: treat as read-only."""
     if _case_cache.get(inp.get('name')) is inp and MUTANT is None:
-        return _reference_cached(inp['name'], dtype)
+        return (_reference_cached_weighted if 'base' in inp else _reference_cached)(inp['name'], dtype)
     return evaluate(inp, dtype)
 
 
@@ -1362,6 +1593,8 @@ def measure_rows(x, ref, name):
     x = x.detach().cpu()
     if name == 'g_tex':
         return [('g_tex', measure(x, r, S)[0])]
+    if name == 'wsum':      # (the weighted call's sum of all weights: one number)
+        return [('wsum', measure(x.reshape(()), r, S)[0])]
     xyz = [0, 1, 2]
     return [('g_pos', measure(x[..., xyz], r[..., xyz], S[..., xyz])[0]), ('g_pos.w', measure(x[..., 3], r[..., 3], S[..., 3])[0])]
 
@@ -1369,6 +1602,8 @@ def measure_rows(x, ref, name):
 def value_error(x, ref):
     """|x - r| / S of the value in units of u."""
     r, S = ref['value']
+    if float(S) == 0.0:      # (a weighted call whose every weight is 0: the value is the exact 0)
+        return 0.0 if float(x) == float(r) else float('inf')
     return abs(float(x) - float(r)) / float(S) / U
 
 
@@ -1387,9 +1622,16 @@ def failures(inp, ref, r32, got, k32=None):
         for (row, e), (_, e32) in zip(rows, rows32):
             if not e <= 8 * e32 + 4:
                 bad.append((row, 'bound', round(e, 2), round(8 * e32 + 4, 2)))
-    n = n_value(inp['tex'].shape[2], plan(inp)['max_deferred'], inp.get('mip_levels') is not None)
+    n = value_count(inp)
     if not value_error(got['value'], ref) <= n + 2:
         bad.append(('value', value_error(got['value'], ref), n + 2))
+    if 'wsum' in ref:      # the weighted call: the sum of all weights, by the long-sum bar
+        try:
+            e, e32 = measure_rows(got['wsum'], ref, 'wsum')[0][1], measure_rows(r32['wsum'][0], ref, 'wsum')[0][1]
+            if not e <= 8 * e32 + 4:
+                bad.append(('wsum', 'bound', round(e, 2), round(8 * e32 + 4, 2)))
+        except AssertionError:
+            bad.append(('wsum', 'a weight where there is none'))
     if k32 is not None and not torch.equal(got['g_tex'].reshape(-1, inp['tex'].shape[2])[k32['texel']].float(), k32['g_tex']):
         bad.append(('g_tex', 'a one-term texel is not gq * w bit for bit'))
     return bad

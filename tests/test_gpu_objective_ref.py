@@ -53,6 +53,14 @@ def _call(dr, inp, want=('pos', 'tex'), **kw):
     pos, tex = inp['pos'].to(dev).requires_grad_('pos' in want), inp['tex'].to(dev).requires_grad_('tex' in want)
     idp = torch.zeros(lib.fpcdr_idplane_bytes(B, H, W), dtype=torch.uint8, device=dev)
     flags = torch.zeros(lib.fpcdr_antialias_flags_bytes(B, H, W) // 8, dtype=torch.int64, device=dev)
+    wt, wsum = inp.get('weights'), None
+    if wt is not None:      # objective_ref.with_weights: the weighted call, its mask stored one byte off 16-byte alignment
+        from test_gpu_robust import _at
+        wsum = torch.zeros(1, dtype=torch.float64, device=dev)
+        mask = None if wt['mask'] is None else _at(wt['mask'], 1)
+        assert mask is None or mask.data_ptr() % 16 == 1
+        kw = dict(kw, robust=(wt['kind'], wt['c']), mask=mask, face_weights=None if wt['face_weights'] is None else wt['face_weights'].to(dev),
+                  weight_outside=wt['weight_outside'], saturation=wt['saturation'], wsum_out=wsum)
     val = dr.pixel_objective(ctx, pos, inp['tri'].to(dev), inp['uv'].to(dev), inp['uv_tri'].to(dev), tex, inp['ref_u8'].to(dev), (H, W),
                              boundary_mode=inp['boundary'], unit_upstream=True, id_plane_out=idp, aa_flags_out=flags, **kw)
     val.backward()
@@ -60,6 +68,8 @@ def _call(dr, inp, want=('pos', 'tex'), **kw):
     OY, OX = (H + 31) // 32, (W + 31) // 32
     planes = idp.cpu().view(torch.int32).reshape(B, OY, OX, 32, 32).permute(0, 1, 3, 2, 4).reshape(B, OY * 32, OX * 32)[:, :H, :W].long() & 0xffffffff
     got = {'value': val.detach().cpu(), 'ids': planes, 'flags': flags.cpu()}
+    if wsum is not None:
+        got['wsum'] = wsum.cpu()[0]
     if 'pos' in want:
         got['g_pos'] = pos.grad.cpu()
     if 'tex' in want:
@@ -79,8 +89,11 @@ def _hold(name, inp, got, tag, calls=1, word='OBJ'):
         if k in got:
             for (row, e), (_, e32) in zip(R.measure_rows(got[k], ref, k), R.measure_rows(r32[k][0], ref, k)):
                 print(f"{word} {name}{tag} {row} {calls} {e:.3f} {e32:.3f} {8 * e32 + 4:.2f}")
-    n = R.n_value(inp['tex'].shape[2], R.plan(inp)['max_deferred'], inp.get('mip_levels') is not None)
+    n = R.value_count(inp)
     print(f"{word} {name}{tag} value {calls} {R.value_error(got['value'], ref):.3f} {R.value_error(r32['value'][0], ref):.3f} {n + 2}")
+    if 'wsum' in ref:      # the weighted call: the sum of all weights
+        (_, e), (_, e32) = R.measure_rows(got['wsum'], ref, 'wsum')[0], R.measure_rows(r32['wsum'][0], ref, 'wsum')[0]
+        print(f"{word} {name}{tag} wsum {calls} {e:.3f} {e32:.3f} {8 * e32 + 4:.2f}")
     assert R.failures(inp, ref, r32, full, k32 if 'g_tex' in got else None) == [], (name, tag)
 
 

@@ -7,6 +7,10 @@ background sums are long sums, held by that file's bar e <= 8 * e32 + 4 in units
 Inputs: tests/objective_ref.case_inputs -- two images of 45 x 70 (partial bins on both axes), silhouettes that cross bin borders (the
 soups) and that lie against empty pixels (the islands).  The mask is random bytes with a block of 0 and a block of 255, stored one byte
 off alignment; a fifth of the face weights is exactly 0.  Every line below is printed by a test as "WOBJ ..." (pytest -s).
+These bars are relative over whole tensors: they see a wrong formula, not a wrong pixel.  The entry-by-entry bars against a float64 statement
+of the weighted call -- exact zeros, every entry in units of its own scale, the value by an operation count, wsum, one-term texels bit for
+bit, C = 4 -- live in tests/test_gpu_objective_weighted_ref.py (tests/objective_ref.py with inp['weights']); this file keeps the comparison
+with the operator path, the Fitter, the background sums and the argument checks.
 
 Measured on an MI355X at 17543e4 plus the change that adds this file (the largest over the cases of a row; 120 weighted calls against
 autograd: six cases x five kinds and scales x four option sets).  The whole file runs in 6.6 s there, 2.2 s of them the first Fitter test:
