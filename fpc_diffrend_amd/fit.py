@@ -22,6 +22,7 @@ Reference quirks are reproduced and flagged where they 
   Q7 the Laplacian term enters squared (fit.py:581).
 """
 import ctypes
+import gc
 import json
 import math
 import os
@@ -369,15 +370,32 @@ def pixel_term(cfg, i, weighted=False):
     return ('robust', 'l2', None) if weighted else None
 
 
+def step_path(cfg, term, mip, channels=1):
+    """Which of its four forms a step runs under FitConfig cfg when its pixel term is `term` (pixel_term's answer), the active level's
+    enable_mip is `mip` and the texture has `channels` ("Which pixel term an iteration runs") -> (form, weighted):
+      'one_pass'   ops.pixel_objective, value and gradient from one call: fused_objective, fused_render, fused_loss, texture shading with
+                   1, 3 or 4 channels, one_pass and sparse_objective, and no term of its own -- or, weighted = True, the robust term
+                   under cfg.weighted_one_pass on a level without mip ("Weighted objective rule"; a pyramid level under
+                   pyramid_mip, the cheap levels, stays on the operator path);
+      'two_call'   ops.pixel_objective's two-call form: the same flags without one_pass or without sparse_objective (mip needs the
+                   latter), and no term of its own: a windowed or weighted loss needs the image in memory;
+      'operators'  render_from_clip or render_vertex and the fused pixel term (pixel_term_loss): fused_loss otherwise;
+      'torch'      the reference's torch loss on the operators' image: fused_loss=False.
+    Needs no GPU."""
+    objective = bool(cfg.fused_objective and cfg.fused_render and cfg.fused_loss and cfg.shading == 'texture' and channels in (1, 3, 4))
+    if objective and cfg.one_pass and cfg.sparse_objective:
+        weighted = bool(cfg.weighted_one_pass and term is not None and term[0] == 'robust' and not mip)
+        if term is None or weighted:
+            return 'one_pass', weighted
+    elif objective and term is None and (not mip or cfg.sparse_objective):
+        return 'two_call', False
+    return ('operators' if cfg.fused_loss else 'torch'), False
+
+
 def weighted_one_pass_term(cfg, term, mip, channels=1):
-    """Whether an iteration whose pixel term is `term` (pixel_term's answer) runs the WEIGHTED one-pass objective ("Weighted
-    objective rule"; ops.pixel_objective with weights) instead of render_from_clip + pixel_loss_robust: cfg.weighted_one_pass is set, the
-    term is the robust one, every flag of the one-pass step is on (fused_objective, fused_render, fused_loss, one_pass, sparse_objective),
-    the shading is the texture's with 1, 3 or 4 `channels`, and the active level runs without mip (`mip`: the level's enable_mip -- a
-    pyramid level under pyramid_mip, the cheap levels, stays on the operator path).  Needs no GPU."""
-    return bool(cfg.weighted_one_pass and term is not None and term[0] == 'robust' and cfg.fused_objective and cfg.fused_render
-                and cfg.fused_loss and cfg.one_pass and cfg.sparse_objective and cfg.shading == 'texture' and channels in (1, 3, 4)
-                and not mip)
+    """Whether an iteration whose pixel term is `term` runs the WEIGHTED one-pass objective (ops.pixel_objective with weights) instead of
+    render_from_clip + pixel_loss_robust: step_path's second answer.  Needs no GPU."""
+    return step_path(cfg, term, mip, channels)[1]
 
 
 def pixel_term_loss(term, colour, rast_out, ref_u8, n_total, **weights):
@@ -1418,17 +1436,14 @@ class Fitter:
         self._skip_cur = None
         Fb, Nc = self._n(frame_ids), (len(self.cam_idxs) if view_ids is None else int(view_ids.shape[0]))
         C = self.tex_opt.shape[2]
-        # (the mip branch of the reference's render(), fit.py:153-155, runs inside the same kernels)
-        one_shot = (cfg.fused_objective and cfg.fused_render and cfg.fused_loss and C in (1, 3, 4) and cfg.shading == 'texture'
-                    and (not mip or cfg.sparse_objective))
-        term = pixel_term(cfg, i, self._weighted)      # a windowed loss needs the image in memory: the operator path; so does a weighted
-        robust = term is not None and term[0] == 'robust'      # one, unless the weighted one-pass objective takes it
-        weighted_shot = weighted_one_pass_term(cfg, term, mip, C)
-        one_shot = one_shot and (term is None or weighted_shot)
+        term = pixel_term(cfg, i, self._weighted)
+        robust = term is not None and term[0] == 'robust'
+        form, weighted_shot = step_path(cfg, term, mip, C)      # (the step's path, asked once)
+        one_pass, one_shot = form == 'one_pass', form in ('one_pass', 'two_call')
         # one flat buffer for the small accumulators of this step's backward kernels, zero-filled by the objective's first kernel; the
         # pool around it goes to the functions whose backward takes views of it
         zero_buf, pool = None, None
-        if one_shot and cfg.one_pass and cfg.sparse_objective:
+        if one_pass:
             n_pose = (self.q_opt.shape[0] + self.per_frame_q.shape[0]) if (view_ids is not None or torch.is_tensor(frame_ids)) else (Fb + Nc)
             zero_buf = torch.empty(Fb * Nc * 16 + 7 * n_pose + 64 + Fb * (self.datasets['local'].shape[1] + self.m3.shape[1]),
                                    dtype=torch.float32, device=self.device)
@@ -1477,7 +1492,7 @@ class Fitter:
             bg_sum = None
             if cfg.sparse_objective and not weighted_shot:
                 bg_sum = self._rows_sum('bg_sumsq', None, self.target_bg_sumsq.reshape(-1), rows)
-            self._skip_cur = self._skip_target() if (cfg.one_pass and cfg.sparse_objective) else None
+            self._skip_cur = self._skip_target() if one_pass else None
             wkw = {}
             if weighted_shot:      # the same weights pixel_loss_robust takes, and the level's all-background share of this term
                 mask = self._step_masks(rows)
@@ -1692,13 +1707,23 @@ class Fitter:
             one_graph = self.reduce_fn is None
             ga, gb = torch.cuda.CUDAGraph(), (None if one_graph else torch.cuda.CUDAGraph())
             self.optimizer.zero_grad(set_to_none=True)
-            with torch.cuda.graph(ga):
-                loss = self.loss_and_backward(frame_ids, view_ids, validate=False)
-                if one_graph:
-                    self._update(prepared=True)
-            if not one_graph:
-                with torch.cuda.graph(gb, pool=ga.pool()):
-                    self._update(prepared=True)
+            # no garbage collection inside a capture: a dead Fitter is CYCLIC garbage (the closures of its prior terms), so it is freed
+            # whenever the collector happens to run, and freeing its pinned buffers records events, which is not permitted while a stream
+            # captures -- the process aborts.  torch.cuda.graph() does not collect first: collect here, and keep the collector off
+            gc_was_on = gc.isenabled()
+            gc.collect()
+            gc.disable()
+            try:
+                with torch.cuda.graph(ga):
+                    loss = self.loss_and_backward(frame_ids, view_ids, validate=False)
+                    if one_graph:
+                        self._update(prepared=True)
+                if not one_graph:
+                    with torch.cuda.graph(gb, pool=ga.pool()):
+                        self._update(prepared=True)
+            finally:
+                if gc_was_on:
+                    gc.enable()
             self._graphs = (ga, gb, loss)      # capture does not execute: fall through to the first replay
         ga, gb, loss = self._graphs
         if cap_adam and not prepared:

@@ -22,7 +22,7 @@ libfpcdr.so; there is no CPU or eager-torch fallback.
 import ctypes
 import functools
 import weakref
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -376,6 +376,58 @@ class _MappedHints:
         self.seq = self.seq % 0x7ffffff0 + 1
         return self.seq
 
+    @staticmethod
+    def plan(hints, nbins, capturing, has_skip_out, record_slots, n_pixels):
+        """What a one-pass call on a batch of `nbins` bins and `n_pixels` pixels does with its launch sizes, its counters and its records
+        of DEFERRED pixels (a pixel pair at a silhouette; a few per cent of the covered pixels -- nothing else of the image ever exists in
+        HBM): a _CallPlan.  hints: the shape's record, or None (launch_hints=False, first use of a shape under capture) -- caps 0, nothing
+        reported, records as the caller says or by pixel.  capturing: a graph replays fixed launch sizes and cannot be waited for --
+        nothing is reported, a pending overflow stays pending, records by pixel.  Host logic only: no device, no stream."""
+        given = record_slots is not None
+        if hints is None:
+            return _CallPlan((0, 0, 0), None, False, int(record_slots) if given else 0, n_pixels)
+        # a batch of few bins -- one image of the reference's run shape has 1 900 -- is launched at its full size whatever the hint says: a
+        # sized launch has a strided sweep launched behind it (four per call, 4.6 us each), and the dead workgroups of a full launch cost less
+        caps = hints.poll()
+        if nbins <= SMALL_BATCH_BINS and not hints.frozen:
+            caps = (0, 0, 0)
+        seq = None if capturing else hints.next_seq()
+        if hints.overflowed is not None and not capturing:
+            # an earlier call on this shape ran out of record slots: its value was NaN and its gradients incomplete.  A caller that hands
+            # over skip_out had the device flag of that very call (Fitter: the update was skipped on the device) -- nothing to raise; the
+            # demand the call counted (it keeps counting beyond the pool) has sized this call.  Anybody else learns it here.
+            over, hints.overflowed = hints.overflowed, None
+            if not has_skip_out:
+                hints.sil_bins = -1      # (re-count in front of the next call)
+                raise RuntimeError(f"pixel_objective: a call on this batch shape (sequence number <= {over}) ran out of record slots (the "
+                                   "take's silhouette grew by more than half within one step); its value was NaN and its gradients "
+                                   "incomplete -- repeat the step, or pass skip_out= and skip the update as Fitter does")
+            hints.skipped_calls += 1
+        # large batches: COMPACT, a slot of 1 024 records for every bin that shows a silhouette triangle, sized from the last call on the
+        # batch shape (24 B per pixel of the batch otherwise: 14 GB at 288 full-HD images, for 0.2 % of them); the first call on a shape
+        # asks the rasteriser for the count (one extra rasterisation and a host wait, once per shape)
+        compact = not given and COMPACT_RECORDS and not capturing and nbins > SMALL_BATCH_BINS
+        count = compact and hints.sil_bins < 0 and not hints.frozen
+        slots = int(record_slots) if given else max(hints.slots, 1) if compact else 0
+        return _CallPlan(caps, seq, count, slots, n_pixels)
+
+    def counted(self, plan):
+        """The plan of the call proper once the count-only call `plan` asked for has landed (the caller has waited for the stream)."""
+        caps, seq = self.poll(), self.next_seq()
+        if self.sil_bins < 0:
+            raise RuntimeError("pixel_objective: the counting call reported nothing")
+        return _CallPlan(caps, seq, False, max(self.slots, 1), plan.n_pixels)
+
+
+class _CallPlan(namedtuple('_CallPlan', 'caps seq count slots n_pixels')):
+    """_MappedHints.plan's answer: caps (cap_bins, cap_occ, cap_def); seq, the counts_seq with which counts_out is handed over, or None:
+    nothing reported; count: a count-only call comes first, then _MappedHints.counted; slots: rec_slots, 0 = records by pixel."""
+    __slots__ = ()
+
+    @property
+    def n_records(self):
+        return self.slots * _lib.OCC_BIN * _lib.OCC_BIN if self.slots > 0 else self.n_pixels
+
 
 _list_hints = {}
 # Compact records (fpcdr_objective_params.rec_slots): a call gets 1.5 x the slots the last call on the batch shape used, at least this
@@ -407,12 +459,45 @@ def clear_hints():
     _list_hints.clear()
 
 
+_objective_options = namedtuple('_objective_options', 'H W n_total bg boundary ref_bg_sumsq use_hints want_grad mip_levels sparse queued_backward '
+                                'unit_upstream flags_out zero_extra bin_lists idp_out record_slots skip_out weights',
+                                defaults=(True, False, False, None, None, True, None, None, None, None))
+_objective_options.__doc__ = """What pixel_objective hands to either form's apply() beside its tensors, as ONE argument (nothing in it gets
+a gradient).  Both forms read the first nine; sparse and queued_backward are the two-call form's, the rest the one-pass form's."""
+
+
+def _background_share(ref, bg, ref_bg_sumsq, dev):
+    """The plain objective's share of an all-background image, f64 []: the caller's ref_bg_sumsq, or computed here (it depends on ref alone)."""
+    return (reference_background_sumsq(ref, bg).sum() if ref_bg_sumsq is None
+            else torch.as_tensor(ref_bg_sumsq, device=dev)).to(torch.float64).contiguous()
+
+
+def _wire_plan(p, hints, plan):
+    """A _CallPlan's launch sizes and, when the call reports its counters, where to and under which number, into the struct p."""
+    p.cap_bins, p.cap_occ, p.cap_def = plan.caps      # (live bins, occupied bins, bins with a deferred pixel)
+    if plan.seq is not None:
+        p.counts_out, p.counts_seq = hints.host.data_ptr(), plan.seq
+
+
+def _mip_chain(p, tex, mip_levels, want_grad=False):
+    """mip_levels = n: the reference's enable_mip branch inside the objective's kernels -- levels 1..n of tex [Ht,Wt,C] (built here, box
+    filter as texture()) and, with want_grad, the buffers of their gradients, wired into the parameter struct p.  None: ([], [])."""
+    if mip_levels is None:
+        return [], []
+    chain = _build_mips(tex[None], mip_levels)[1:]
+    g_chain = [torch.empty_like(t) for t in chain] if want_grad else []
+    _wire_mips(p, chain, g_chain)
+    return chain, g_chain
+
+
 class _pixel_objective_func(torch.autograd.Function):
-    """mean over n_total of (ref - 255 * where(covered, antialias(render(pos, tex)), bg))^2 as three kernels."""
+    """The two-call form: mean over n_total of (ref - 255 * where(covered, antialias(render(pos, tex)), bg))^2 as three kernels."""
 
     @staticmethod
-    def forward(ctx, pos, tex, tri, adj, uv, uv_tri, ref, H, W, n_total, bg, boundary, sparse, ref_bg_sumsq, use_hints,
-                queued_backward, mip_levels=None, grad_enabled=True):
+    def forward(ctx, pos, tex, *const):
+        tri, adj, uv, uv_tri, ref, opt = const
+        H, W, n_total, bg, boundary, sparse, mip_levels = opt.H, opt.W, opt.n_total, opt.bg, opt.boundary, opt.sparse, opt.mip_levels
+        ctx.n_const = len(const)
         lib = _lib.load_twocall()      # (the two-call form: include/fpcdr_twocall.h, libfpcdr_twocall.so)
         B, V, _ = pos.shape
         T = tri.shape[0]
@@ -429,10 +514,7 @@ class _pixel_objective_func(torch.autograd.Function):
         p = _lib.RenderFwd(pos=_ptr(pos), tri=_ptr(tri), B=B, V=V, T=T, H=H, W=W, scratch=_ptr(scratch), uv=_ptr(uv),
                            uv_tri=_ptr(uv_tri), Vt=uv.shape[0], tex=_ptr(tex), Ht=Ht, Wt=Wt, C=C, boundary_mode=boundary,
                            rast=_ptr(rast), color=_ptr(color), tri_uv=_ptr(tri_uv), occ=_ptr(occ), empty_color=_ptr(ecol))
-        # mip_levels = n: the reference's enable_mip branch inside the same kernels (the chain is built here, box filter as texture())
-        chain = _build_mips(tex[None], mip_levels)[1:] if mip_levels is not None else []
-        if mip_levels is not None:
-            _wire_mips(p, chain)
+        chain, _ = _mip_chain(p, tex, mip_levels)
         g_aa = torch.empty_like(color)
         sil = torch.empty(B, T, dtype=torch.uint8, device=dev)
         nflag = lib.fpcdr_antialias_flags_bytes(B, H, W) // 8
@@ -446,7 +528,7 @@ class _pixel_objective_func(torch.autograd.Function):
         if sparse:
             # one call: the rasteriser settles every pixel antialiasing cannot touch, a second kernel the candidates it marks
             cmask = torch.empty(lib.fpcdr_cmask_bytes(B, H, W), dtype=torch.uint8, device=dev)
-            hints = _hints_for((dev.index, B, V, T, H, W), _ListHints) if use_hints else None
+            hints = _hints_for((dev.index, B, V, T, H, W), _ListHints) if opt.use_hints else None
             if hints is not None:
                 q.cap_bins, q.cap_fix, ctx.cap_bwd = hints.poll()
             _lib.call("fpcdr_render_loss_fwd", ctypes.byref(p), ctypes.byref(q), _ptr(cmask), _stream())
@@ -465,18 +547,15 @@ class _pixel_objective_func(torch.autograd.Function):
         # the one-call sparse forward leaves the list of bins the backward visits in `occ`; measured at cfg3 the backward gains
         # nothing from it (2.69 vs 2.64 ms: its dead workgroups' dispatch hides behind the live ones' work), so the grid form is
         # the default and the list form stays selectable
-        ctx.queued = 1 if (sparse and queued_backward) else 0
-        # (sparse => the one-call forward, which also leaves the per-bin summary of the antialias flags in `occ`)
-        bg_sum = None
-        if sparse:
-            # the kernel summed only the difference to an all-background image; the rest depends on ref alone
-            bg_sum = (reference_background_sumsq(ref, bg).sum() if ref_bg_sumsq is None
-                      else torch.as_tensor(ref_bg_sumsq, device=dev)).to(torch.float64).contiguous()
+        ctx.queued = 1 if (sparse and opt.queued_backward) else 0
+        # (sparse => the one-call forward, which also leaves the per-bin summary of the antialias flags in `occ`); its kernel summed only
+        # the difference to an all-background image: the rest depends on ref alone
+        bg_sum = _background_share(ref, bg, opt.ref_bg_sumsq, dev) if sparse else None
         out = torch.empty((), dtype=torch.float32, device=dev)
         _lib.call("fpcdr_objective_value", _ptr(acc), _lib.LOSS_SLOTS, _ptr(bg_sum), float(C), float(n_total), _ptr(out), _stream())
         # forward only (no input wants a gradient, or the caller runs under no_grad -- needs_input_grad stays True there): read the
         # counts back now; otherwise after the backward call has been enqueued
-        if not (grad_enabled and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])) and ctx.hint_update is not None:
+        if not (opt.want_grad and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])) and ctx.hint_update is not None:
             ctx.hint_update[0].update(ctx.hint_update[1])
             ctx.hint_update = None
         return out
@@ -508,7 +587,7 @@ class _pixel_objective_func(torch.autograd.Function):
             ctx.hint_update = None
         if not ctx.needs_input_grad[0]:
             g_pos = None
-        return (g_pos, g_tex) + (None,) * 16
+        return (g_pos, g_tex) + (None,) * ctx.n_const
 
 
 class _pixel_objective_onepass(torch.autograd.Function):
@@ -517,24 +596,23 @@ class _pixel_objective_onepass(torch.autograd.Function):
     barycentrics, taps, texels and vertices are in registers, and backward() only multiplies by what autograd hands over."""
 
     @staticmethod
-    def forward(ctx, pos, tex, tri, adj, uv, uv_tri, ref, H, W, n_total, bg, boundary, ref_bg_sumsq, use_hints, want_grad, unit_upstream,
-                flags_out=None, mip_levels=None, zero_extra=None, bin_lists=True, idp_out=None, record_slots=None,
-                skip_out=None, weights=None):
+    def forward(ctx, pos, tex, *const):
+        tri, adj, uv, uv_tri, ref, opt = const
+        H, W, weights, skip_out = opt.H, opt.W, opt.weights, opt.skip_out
+        ctx.n_const = len(const)
         lib = _lib.load()
         B, V, _ = pos.shape
         T = tri.shape[0]
         Ht, Wt, C = tex.shape
         dev = pos.device
-        want_pos = bool(want_grad and ctx.needs_input_grad[0])
-        want_tex = bool(want_grad and ctx.needs_input_grad[1])
+        want_pos = bool(opt.want_grad and ctx.needs_input_grad[0])
+        want_tex = bool(opt.want_grad and ctx.needs_input_grad[1])
+        # buffers
         u8 = lambda n: torch.empty(n, dtype=torch.uint8, device=dev)
         scratch = u8(lib.fpcdr_rasterize_scratch_bytes(B, T))
         sil = u8(B * T)
-        if idp_out is not None:      # (tests / diagnostics: the caller keeps the id planes)
-            if idp_out.numel() * idp_out.element_size() != lib.fpcdr_idplane_bytes(B, H, W) or not idp_out.is_contiguous() or idp_out.device != dev:
-                raise ValueError("id_plane_out must be a contiguous device tensor of fpcdr_idplane_bytes(B, H, W) bytes")
-        idp = idp_out if idp_out is not None else u8(lib.fpcdr_idplane_bytes(B, H, W))
-        binlist = u8(lib.fpcdr_binlist_bytes(B, H, W)) if bin_lists else None      # per-bin triangle lists (set-up kernel -> rasteriser)
+        idp = opt.idp_out if opt.idp_out is not None else u8(lib.fpcdr_idplane_bytes(B, H, W))      # (tests / diagnostics: the caller keeps the id planes)
+        binlist = u8(lib.fpcdr_binlist_bytes(B, H, W)) if opt.bin_lists else None      # per-bin triangle lists (set-up kernel -> rasteriser)
         occ, cmask = u8(lib.fpcdr_occ_bytes(B, H, W)), u8(lib.fpcdr_objective_cmask_bytes(B, H, W))
         ecol = torch.empty(4, dtype=torch.float32, device=dev)
         # (zero_outputs: the call's first kernel zero-fills its accumulators)
@@ -544,78 +622,39 @@ class _pixel_objective_onepass(torch.autograd.Function):
         tri_uv = _cached_tri_uv(uv, uv_tri)
         p = _lib.Objective(pos=_ptr(pos), tri=_ptr(tri), adj=_ptr(adj), B=B, V=V, T=T, H=H, W=W, scratch=_ptr(scratch), uv=_ptr(uv),
                            uv_tri=_ptr(uv_tri), Vt=uv.shape[0], tri_uv=_ptr(tri_uv), tex=_ptr(tex), Ht=Ht, Wt=Wt, C=C,
-                           boundary_mode=boundary, ref=_ptr(ref), bg=bg, color_scale=255.0, grad_scale=1.0 / n_total, sil=_ptr(sil),
+                           boundary_mode=opt.boundary, ref=_ptr(ref), bg=opt.bg, color_scale=255.0, grad_scale=1.0 / opt.n_total, sil=_ptr(sil),
                            idp=_ptr(idp), occ=_ptr(occ), cmask=_ptr(cmask),
-                           empty_color=_ptr(ecol), loss_sum=_ptr(acc), grad_pos=_ptr(g_pos), grad_tex=_ptr(g_tex), flags=_ptr(flags_out),
+                           empty_color=_ptr(ecol), loss_sum=_ptr(acc), grad_pos=_ptr(g_pos), grad_tex=_ptr(g_tex), flags=_ptr(opt.flags_out),
                            binlist=_ptr(binlist), zero_outputs=1, skip_out=_ptr(skip_out))
-        # mip_levels = n: the reference's enable_mip branch inside the same kernels (the chain is built here, box filter as texture())
-        chain = _build_mips(tex[None], mip_levels)[1:] if mip_levels is not None else []
-        g_chain = [torch.empty_like(t) for t in chain] if want_tex else []
-        if mip_levels is not None:
-            _wire_mips(p, chain, g_chain)
-        capturing = torch.cuda.is_current_stream_capturing()
-        hints = _hints_for(('onepass', dev.index, B, V, T, H, W), _MappedHints) if use_hints else None
+        chain, g_chain = _mip_chain(p, tex, opt.mip_levels, want_tex)
+        # plan (_MappedHints.plan: launch sizes, counters, records), and the count-only call when it asks for one
+        hints = _hints_for(('onepass', dev.index, B, V, T, H, W), _MappedHints) if opt.use_hints else None
         nbins = _n_bins(B, H, W)
-        if hints is not None:
-            p.cap_bins, p.cap_occ, p.cap_def = hints.poll()      # (live bins, occupied bins, bins with a deferred pixel)
-            # a batch of few bins -- one image of the reference's run shape has 1 900 -- is launched at its full size whatever the
-            # hint says: a sized launch has a strided sweep launched behind it (four per call, 4.6 us each), and the dead workgroups
-            # of a full launch cost less than that
-            if nbins <= SMALL_BATCH_BINS and not hints.frozen:
-                p.cap_bins, p.cap_occ, p.cap_def = 0, 0, 0
-            if not capturing:      # (a graph replays fixed launch sizes: nothing to report)
-                p.counts_out, p.counts_seq = hints.host.data_ptr(), hints.next_seq()
-        # records of the DEFERRED pixels (a pixel pair at a silhouette; a few per cent of the covered pixels -- nothing else of the image
-        # ever exists in HBM).  Large batches: COMPACT, a slot of 1 024 records for every bin that shows a silhouette triangle, sized from
-        # the last call on the batch shape (24 B per pixel of the batch otherwise: 14 GB at 288 full-HD images, for 0.2 % of them).  The
-        # first call on a shape asks the rasteriser for the count (one extra rasterisation and a host wait, once per shape).  Small
-        # batches, captured calls and calls without hints address the records by pixel.
-        slots = 0
-        if hints is not None and hints.overflowed is not None and not capturing:
-            # an earlier call on this shape ran out of record slots: its value was NaN and its gradients incomplete.  A caller that hands
-            # over skip_out had the device flag of that very call (Fitter: the update was skipped on the device) -- nothing to raise; the
-            # demand the call counted (it keeps counting beyond the pool) has sized this call.  Anybody else learns it here.
-            seq, hints.overflowed = hints.overflowed, None
-            if skip_out is not None:
-                hints.skipped_calls += 1
-            else:
-                hints.sil_bins = -1      # (re-count in front of the next call)
-                raise RuntimeError(f"pixel_objective: a call on this batch shape (sequence number <= {seq}) ran out of record slots (the "
-                                   "take's silhouette grew by more than half within one step); its value was NaN and its gradients "
-                                   "incomplete -- repeat the step, or pass skip_out= and skip the update as Fitter does")
-        if record_slots is not None:
-            slots = int(record_slots)
-        elif COMPACT_RECORDS and hints is not None and not capturing and nbins > SMALL_BATCH_BINS:
-            if hints.sil_bins < 0 and not hints.frozen:
-                p.count_only = 1
-                _lib.call("fpcdr_objective_fwd", ctypes.byref(p), _stream())
-                p.count_only = 0
-                torch.cuda.current_stream(dev).synchronize()
-                p.cap_bins, p.cap_occ, p.cap_def = hints.poll()
-                p.counts_seq = hints.next_seq()
-                if hints.sil_bins < 0:
-                    raise RuntimeError("pixel_objective: the counting call reported nothing")
-            slots = max(hints.slots, 1)
-        if slots > 0:
-            n_rec = slots * _lib.OCC_BIN * _lib.OCC_BIN
+        plan = _MappedHints.plan(hints, nbins, torch.cuda.is_current_stream_capturing(), skip_out is not None, opt.record_slots, B * H * W)
+        _wire_plan(p, hints, plan)
+        if plan.count:
+            p.count_only = 1
+            _lib.call("fpcdr_objective_fwd", ctypes.byref(p), _stream())
+            p.count_only = 0
+            torch.cuda.current_stream(dev).synchronize()
+            plan = hints.counted(plan)
+            _wire_plan(p, hints, plan)
+        # records of the deferred pixels: in slots, or by pixel
+        if plan.slots > 0:
             slot_map = torch.empty(nbins, dtype=torch.int32, device=dev)
-            p.rec_slots, p.slot_map = slots, _ptr(slot_map)
-        else:
-            n_rec = B * H * W
-        rec = torch.empty(n_rec, 4, dtype=torch.float32, device=dev)
-        color = torch.empty(n_rec, C, dtype=torch.float32, device=dev)
-        g_aa = torch.empty(n_rec, C, dtype=torch.float32, device=dev)
+            p.rec_slots, p.slot_map = plan.slots, _ptr(slot_map)
+        rec = torch.empty(plan.n_records, 4, dtype=torch.float32, device=dev)
+        color = torch.empty(plan.n_records, C, dtype=torch.float32, device=dev)
+        g_aa = torch.empty(plan.n_records, C, dtype=torch.float32, device=dev)
         p.rec, p.color, p.grad_aa = _ptr(rec), _ptr(color), _ptr(g_aa)
-        # the value from the call's last kernel: (loss slots + C * background share) / n_total
-        if weights is None:
-            bg_sum = (reference_background_sumsq(ref, bg).sum() if ref_bg_sumsq is None
-                      else torch.as_tensor(ref_bg_sumsq, device=dev)).to(torch.float64).contiguous()
-        else:      # (the weighted background share: [2] = sum of w0 * rho(d0), sum of w0 over the call's images; the kernel reads [0])
-            bg_sum = weights['bg']
+        # the value from the call's last kernel: (loss slots + C * background share) / n_total.  The weighted background share is [2] =
+        # sum of w0 * rho(d0), sum of w0 over the call's images; the kernel reads [0]
+        bg_sum = _background_share(ref, opt.bg, opt.ref_bg_sumsq, dev) if weights is None else weights['bg']
         out = torch.empty((), dtype=torch.float32, device=dev)
-        p.bg_sumsq, p.bg_coeff, p.n_total, p.value_out = _ptr(bg_sum), float(C), float(n_total), _ptr(out)
-        if zero_extra is not None:      # (a caller's own small accumulators, zero-filled by the call's first kernel)
-            p.zero_extra, p.zero_extra_bytes = _ptr(zero_extra), zero_extra.numel() * zero_extra.element_size()
+        p.bg_sumsq, p.bg_coeff, p.n_total, p.value_out = _ptr(bg_sum), float(C), float(opt.n_total), _ptr(out)
+        if opt.zero_extra is not None:      # (a caller's own small accumulators, zero-filled by the call's first kernel)
+            p.zero_extra, p.zero_extra_bytes = _ptr(opt.zero_extra), opt.zero_extra.numel() * opt.zero_extra.element_size()
+        # launch, fold
         if weights is None:
             _lib.call("fpcdr_objective_fwd", ctypes.byref(p), _stream())
         else:
@@ -632,7 +671,7 @@ class _pixel_objective_onepass(torch.autograd.Function):
             _fold_mip_grads([g_tex[None]] + g_chain)
         ctx.save_for_backward(*(t for t in (g_pos, g_tex) if t is not None))
         ctx.have = (want_pos, want_tex)
-        ctx.unit = bool(unit_upstream)
+        ctx.unit = bool(opt.unit_upstream)
         return out
 
     @staticmethod
@@ -646,7 +685,7 @@ class _pixel_objective_onepass(torch.autograd.Function):
             g = g.to(torch.float32)
             g_pos = g_pos * g if g_pos is not None else None
             g_tex = g_tex * g if g_tex is not None else None
-        return (g_pos if ctx.needs_input_grad[0] else None, g_tex if ctx.needs_input_grad[1] else None) + (None,) * 22
+        return (g_pos if ctx.needs_input_grad[0] else None, g_tex if ctx.needs_input_grad[1] else None) + (None,) * ctx.n_const
 
 
 def reference_background_sumsq(ref_u8, background=45.0 / 255.0):
@@ -835,6 +874,39 @@ def _weight_tensors(ref_u8, mask, face_weights, check_weights, device=None, n_tr
         if check_weights and not bool((torch.isfinite(face_weights) & (face_weights >= 0)).all()):
             raise ValueError("face_weights must be finite and not negative")
     return mask, face_weights
+
+
+def _objective_weights(ref_u8, device, n_tri, background, plain_form, ref_bg_sumsq, robust, mask, face_weights, weight_outside, saturation,
+                       ref_bg_wsum, wsum_out, check_weights):
+    """pixel_objective's weighted keywords, checked -> what the weighted one-pass call reads (kind, inv_c, w_outside, sat, mask, face_w,
+    bg: the background share f64 [2], wsum_out), or None when none of them is given: the plain call.  ref_u8 contiguous; device, n_tri:
+    of pos and tri; plain_form: the call is not the one-pass sparse form without mip, which alone takes weights.  ValueError otherwise."""
+    if (robust is None and mask is None and face_weights is None and float(weight_outside) == 1.0 and saturation == 0
+            and ref_bg_wsum is None and wsum_out is None):
+        return None
+    if plain_form:
+        raise ValueError("pixel_objective: robust / mask / face_weights / weight_outside / saturation / ref_bg_wsum / wsum_out belong to "
+                         "the one-pass sparse form without mip (use the separate operators and robust_pixel_loss otherwise)")
+    if ref_bg_sumsq is not None:
+        raise ValueError("pixel_objective: a weighted call takes ref_bg_wsum (reference_background_weighted), not ref_bg_sumsq")
+    if robust is not None and not (isinstance(robust, (tuple, list)) and len(robust) == 2):
+        raise ValueError(f"robust must be (kind, scale) (got {robust!r})")
+    kind, scale = robust if robust is not None else ('l2', None)
+    kind_no, inv_c, weight_outside, saturation = robust_args(kind, scale, weight_outside, saturation)
+    mask, face_weights = _weight_tensors(ref_u8, mask, face_weights, check_weights, device=device, n_tri=n_tri)
+    if wsum_out is not None and not (torch.is_tensor(wsum_out) and wsum_out.dtype == torch.float64 and wsum_out.device == device
+                                     and wsum_out.numel() >= 1 and wsum_out.is_contiguous()):
+        raise ValueError("wsum_out must be a contiguous float64 tensor of at least one element on the device of pos")
+    if ref_bg_wsum is None:
+        bgw = reference_background_weighted(ref_u8, mask, kind, scale, weight_outside, saturation, background).sum(0)
+    else:
+        bgw = torch.as_tensor(ref_bg_wsum, device=device).to(torch.float64)
+        if bgw.dim() == 2:
+            bgw = bgw.sum(0)
+        if tuple(bgw.shape) != (2,):
+            raise ValueError(f"ref_bg_wsum must be [2] or [B,2] (got {tuple(bgw.shape)})")
+    return dict(kind=kind_no, inv_c=inv_c, w_outside=weight_outside, sat=saturation, mask=mask, face_w=face_weights, bg=bgw.contiguous(),
+                wsum_out=wsum_out)
 
 
 def robust_loss_call(colour, rast, ref_u8, kind, scale, grad_scale, mask=None, face_weights=None, weight_outside=1.0, saturation=0,
@@ -1215,22 +1287,23 @@ def pixel_objective(glctx, pos, tri, uv, uv_tri, tex, ref_u8, resolution, n_tota
                     enable_mip=False, max_mip_level=None, one_pass=True, unit_upstream=False, aa_flags_out=None, zero_extra=None,
                     id_plane_out=None, record_slots=None, skip_out=None, robust=None, mask=None, face_weights=None, weight_outside=1.0,
                     saturation=0, ref_bg_wsum=None, wsum_out=None, check_weights=True):
-    """The whole pixel term of the reference's loss (fit.py:151-161 + the first term of :579) for a minibatch,
-    as three kernels:  mean((ref - 255 * where(rast.w > 0, antialias(texture(interpolate(rasterize(pos)))), bg))^2)
-    over n_total elements (default: all of this call's).  pos [B,V,4], tex [Ht,Wt,C] (C in 1,3,4), ref_u8 [B,H,W] uint8.
-    Differentiable w.r.t. pos and tex; equals the chain of separate operators + pixel loss.
-    sparse=True: 32x32-pixel bins that no triangle's bounding box touches are skipped by all three kernels (they can only
+    """The whole pixel term of the reference's loss (fit.py:151-161 + the first term of :579) for a minibatch:
+    mean((ref - 255 * where(rast.w > 0, antialias(texture(interpolate(rasterize(pos)))), bg))^2) over n_total elements (default: all of
+    this call's).  pos [B,V,4], tex [Ht,Wt,C] (C in 1,3,4), ref_u8 [B,H,W] uint8.  Differentiable w.r.t. pos and tex; equals the chain of
+    separate operators + pixel loss.
+    By default (one_pass and sparse) VALUE AND GRADIENT come from ONE call, fpcdr_objective_fwd: the kernel that shades a pixel also
+    chains its gradient back; backward() multiplies by the upstream scalar, or returns the buffers as they are with unit_upstream=True
+    (the caller guarantees d loss / d objective = 1).  The alternative, one_pass=False or sparse=False, is the two-call form: a forward
+    call of three kernels that keeps the image, and a backward call.
+    sparse=True: 32x32-pixel bins that no triangle's bounding box touches are skipped by every kernel (they can only
     contribute (ref - 255 bg)^2 to the loss, which is added from ref_bg_sumsq: a scalar f64 tensor, the sum of
     reference_background_sumsq(ref_u8, background) over this call's images; computed here when None); same result.
     launch_hints: size the sparse kernels' launches from the bin counts of the previous call on the same batch shape
-    (read back asynchronously, never waited for; the result does not depend on them).  queued_backward: the backward
+    (never waited for; the result does not depend on them).  queued_backward (two-call form): the backward
     kernel also runs over the compact list of occupied bins instead of one workgroup per bin (same result).
-    enable_mip (sparse mode): the reference's other branch (fit.py:153-155) -- interpolate with the rasteriser's
-    screen-space derivatives and texture 'linear-mipmap-linear' with max_mip_level -- inside the same three kernels; equals the
+    enable_mip (sparse mode, either form): the reference's other branch (fit.py:153-155) -- interpolate with the rasteriser's
+    screen-space derivatives and texture 'linear-mipmap-linear' with max_mip_level -- inside the same kernels; equals the
     chain rasterize(output_db) -> interpolate(diff_attrs='all') -> texture(texd) -> antialias + pixel loss.
-    one_pass (sparse mode, with or without mip; the default): value and gradient from ONE call -- the kernel that shades a pixel also chains
-    its gradient back (fpcdr_objective_fwd); backward() multiplies by the upstream scalar, or returns the buffers as they are with
-    unit_upstream=True (the caller guarantees d loss / d objective = 1).  one_pass=False: the two-call form.
     aa_flags_out (one_pass; tests / diagnostics): a zero-filled int64 tensor of fpcdr_antialias_flags_bytes(B,H,W) / 8 words that
     receives the antialias flag planes (which pixel pairs were blended).  zero_extra (one_pass): a contiguous float32 / int32 tensor of the
     caller's that the call's first kernel zero-fills along with its own buffers (a fit step's small gradient accumulators).
@@ -1265,9 +1338,10 @@ def pixel_objective(glctx, pos, tri, uv, uv_tri, tex, ref_u8, resolution, n_tota
         raise ValueError("ref_u8 must have shape [B,H,W]")
     if boundary_mode not in _lib.BOUNDARY:
         raise ValueError(f"unknown boundary_mode '{boundary_mode}'")
-    tri = tri.contiguous()
+    tri, ref_u8 = tri.contiguous(), ref_u8.contiguous()
     adj = _cached_topology(tri)
     n_total = n_total or pos.shape[0] * H * W * tex.shape[2]
+    one_pass = bool(one_pass and sparse)
     mip_levels = None
     if enable_mip:
         if not sparse:
@@ -1280,50 +1354,25 @@ def pixel_objective(glctx, pos, tri, uv, uv_tri, tex, ref_u8, resolution, n_tota
         # (the kernel zero-fills numel * itemsize bytes from data_ptr(): a view with gaps would have other storage overwritten)
         if not (zero_extra.is_contiguous() and zero_extra.dtype in (torch.float32, torch.int32) and zero_extra.device == pos.device):
             raise ValueError("zero_extra must be a contiguous float32 / int32 tensor on the device of pos")
-        if not (one_pass and sparse):
+        if not one_pass:
             zero_extra.zero_()
-    weighted = (robust is not None or mask is not None or face_weights is not None or float(weight_outside) != 1.0 or saturation != 0
-                or ref_bg_wsum is not None or wsum_out is not None)
-    weights = None
-    if weighted:
-        if not (one_pass and sparse) or enable_mip:
-            raise ValueError("pixel_objective: robust / mask / face_weights / weight_outside / saturation / ref_bg_wsum / wsum_out belong to "
-                             "the one-pass sparse form without mip (use the separate operators and robust_pixel_loss otherwise)")
-        if ref_bg_sumsq is not None:
-            raise ValueError("pixel_objective: a weighted call takes ref_bg_wsum (reference_background_weighted), not ref_bg_sumsq")
-        if robust is not None and not (isinstance(robust, (tuple, list)) and len(robust) == 2):
-            raise ValueError(f"robust must be (kind, scale) (got {robust!r})")
-        kind, scale = robust if robust is not None else ('l2', None)
-        kind_no, inv_c, weight_outside, saturation = robust_args(kind, scale, weight_outside, saturation)
-        ref_u8 = ref_u8.contiguous()
-        mask, face_weights = _weight_tensors(ref_u8, mask, face_weights, check_weights, device=pos.device, n_tri=int(tri.shape[0]))
-        if wsum_out is not None and not (torch.is_tensor(wsum_out) and wsum_out.dtype == torch.float64 and wsum_out.device == pos.device
-                                         and wsum_out.numel() >= 1 and wsum_out.is_contiguous()):
-            raise ValueError("wsum_out must be a contiguous float64 tensor of at least one element on the device of pos")
-        if ref_bg_wsum is None:
-            bgw = reference_background_weighted(ref_u8, mask, kind, scale, weight_outside, saturation, background).sum(0)
-        else:
-            bgw = torch.as_tensor(ref_bg_wsum, device=pos.device).to(torch.float64)
-            if bgw.dim() == 2:
-                bgw = bgw.sum(0)
-            if tuple(bgw.shape) != (2,):
-                raise ValueError(f"ref_bg_wsum must be [2] or [B,2] (got {tuple(bgw.shape)})")
-        weights = dict(kind=kind_no, inv_c=inv_c, w_outside=weight_outside, sat=saturation, mask=mask, face_w=face_weights,
-                       bg=bgw.contiguous(), wsum_out=wsum_out)
-    if one_pass and sparse:
-        return _pixel_objective_onepass.apply(pos.contiguous(), tex.contiguous(), tri, adj, uv.contiguous(), uv_tri.contiguous(),
-                                              ref_u8.contiguous(), H, W, n_total, background, _lib.BOUNDARY[boundary_mode], ref_bg_sumsq,
-                                              bool(launch_hints), torch.is_grad_enabled(), bool(unit_upstream), aa_flags_out, mip_levels, zero_extra,
-                                              True, id_plane_out, record_slots, skip_out, weights)
-    if skip_out is not None:
+    weights = _objective_weights(ref_u8, pos.device, int(tri.shape[0]), background, not one_pass or enable_mip, ref_bg_sumsq, robust, mask,
+                                 face_weights, weight_outside, saturation, ref_bg_wsum, wsum_out, check_weights)
+    if not one_pass and skip_out is not None:      # (what else belongs to the one-pass form alone)
         raise ValueError("skip_out belongs to the one-pass form")
-    if record_slots is not None:
+    if not one_pass and record_slots is not None:
         raise ValueError("record_slots belongs to the one-pass form")
-    if id_plane_out is not None:
+    if not one_pass and id_plane_out is not None:
         raise ValueError("id_plane_out is an output of the one-pass form")
-    return _pixel_objective_func.apply(pos.contiguous(), tex.contiguous(), tri, adj, uv.contiguous(), uv_tri.contiguous(),
-                                       ref_u8.contiguous(), H, W, n_total, background, _lib.BOUNDARY[boundary_mode], bool(sparse), ref_bg_sumsq,
-                                       bool(launch_hints), bool(queued_backward), mip_levels, torch.is_grad_enabled())
+    if id_plane_out is not None and (id_plane_out.numel() * id_plane_out.element_size() != _lib.load().fpcdr_idplane_bytes(pos.shape[0], H, W)
+                                     or not id_plane_out.is_contiguous() or id_plane_out.device != pos.device):
+        raise ValueError("id_plane_out must be a contiguous device tensor of fpcdr_idplane_bytes(B, H, W) bytes")
+    opt = _objective_options(H, W, n_total, background, _lib.BOUNDARY[boundary_mode], ref_bg_sumsq, bool(launch_hints), torch.is_grad_enabled(),
+                             mip_levels, sparse=bool(sparse), queued_backward=bool(queued_backward), unit_upstream=bool(unit_upstream),
+                             flags_out=aa_flags_out, zero_extra=zero_extra, idp_out=id_plane_out, record_slots=record_slots, skip_out=skip_out,
+                             weights=weights)
+    form = _pixel_objective_onepass if one_pass else _pixel_objective_func
+    return form.apply(pos.contiguous(), tex.contiguous(), tri, adj, uv.contiguous(), uv_tri.contiguous(), ref_u8, opt)
 
 
 # ----------------------------------------------------------------------------------------------
