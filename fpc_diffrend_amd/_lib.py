@@ -285,9 +285,14 @@ def load():
 
 
 def load_twocall():
-    """libfpcdr_twocall.so: the superseded two-call form of the pixel objective and the fused render pair (include/fpcdr_twocall.h).
-    A complete library of its own -- every symbol of fpcdr.h plus SYMBOLS_TWOCALL -- loaded only when one of those entry points is
-    asked for (ops.pixel_objective(one_pass=False), ops.render_textured); the fit loop never does."""
+    """libfpcdr_twocall.so: the superseded two-call form of the pixel objective, and the fused render pair fpcdr_render_fwd / _bwd, which
+    is in use (include/fpcdr_twocall.h).  A complete library of its own -- every symbol of fpcdr.h plus SYMBOLS_TWOCALL -- loaded when one
+    of those entry points is asked for: ops.pixel_objective(one_pass=False), and ops.render_textured.  The fit loop asks for the latter
+    on every step that fit.step_path sends down the 'operators' or 'torch' path with fused_render (the default) and without mip
+    (fit.render_from_clip): a blurred or locally normalised term (blur_sigma > 0, the blur levels of the coarse-to-fine pyramid,
+    norm_sigma > 0), a robust, masked or face-weighted term without weighted_one_pass (off by default), fused_loss=False, and a texture
+    of 2 or more than 4 channels.  Their gradients come through k_render_bwd (tests/test_gpu_render.py).  Only a fit whose every step
+    is a one-shot objective never loads it."""
     global _lib_twocall
     if _lib_twocall is not None:
         return _lib_twocall

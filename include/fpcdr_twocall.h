@@ -1,9 +1,11 @@
 /*
- * fpcdr_twocall.h -- the TWO-CALL form of the pixel objective and the fused render pair: rounds 1-3 of this build, superseded in the fit loop
- * by fpcdr_objective_fwd (fpcdr.h) and kept as its parity partner, for the dense (non-sparse) mode and for ops.render_textured.
+ * fpcdr_twocall.h -- the TWO-CALL form of the pixel objective and the fused render pair: rounds 1-3 of this build.  The two-call objective
+ * is superseded in the fit loop by fpcdr_objective_fwd (fpcdr.h) and kept as its parity partner and for the dense (non-sparse) mode.  The
+ * render pair fpcdr_render_fwd / _bwd is in use: ops.render_textured, which the fit loop calls on every step that is not a one-shot
+ * objective.
  *
  * These entry points are NOT exported by libfpcdr.so.  They live in libfpcdr_twocall.so (csrc/Makefile) -- a complete library: every
- * symbol of fpcdr.h plus the ones below -- which fpc_diffrend_amd/_lib.py loads only when one of them is asked for.
+ * symbol of fpcdr.h plus the ones below -- which fpc_diffrend_amd/_lib.py loads when one of them is asked for.
  */
 #ifndef FPCDR_TWOCALL_H
 #define FPCDR_TWOCALL_H
