@@ -35,6 +35,8 @@ import torch
 
 from . import _lib, camera
 from . import ops as dr
+from .landmarks import (LandmarkSet, check_landmark_options, landmark_incidence, landmark_inv_scale, landmark_penalty, landmark_tables,
+                        project_landmarks, read_landmarks, write_landmarks)
 from .mesh_reg import (MeshTopology, RestShape, _check_item_weights, _uniform_laplacian, bend_penalty, check_motion_options,
                        hinge_incidence, hinge_rest_cs, hinge_vertices, laplacian_penalty, mesh_edge_loss, mesh_laplacian_smoothing,
                        mesh_normal_consistency, motion_inv_scale, motion_penalty, rest_edge_lengths, stretch_penalty)
@@ -692,6 +694,18 @@ class FitConfig:
                                     # supplied texture.  0 = off: nothing changes
     tex_anchor_weights: object = None            # as tex_smooth_weights, per texel.  None: 1 -- or, with init_texture='bake', the bake's
                                     # `filled` map: only the texels a capture reached are held
+    weight_landmark: float = 0.0    # > 0: named points of the mesh are held to their detected 2D positions in the captures (DESIGN.md 3,
+                                    # "Landmark rule"; Scene.landmark_points / Scene.landmarks, scene.from_take(landmarkpath=...)): the
+                                    # reprojection error in full-resolution pixels, value and the gradients for the vertices AND the poses
+                                    # from one call in front of the objective, the same term at every pyramid level.  0 = off: nothing is
+                                    # built, allocated or launched.  > 0 on a Scene without landmarks is a ValueError
+    landmark_scale: Optional[float] = None       # the Charbonnier scale c in pixels, finite and > 0: quadratic below c, linear above it, so
+                                    # a wrong detection does not outweigh the others.  None: plain squares.  No default value -- nobody has
+                                    # measured one
+    landmark_iters: int = 0         # 0 = the term is on for every iteration; n = for iterations i < n, then the run continues without it
+    landmark_weights: object = None              # one weight per landmark, finite and >= 0, in place of the points' own 'weight': an
+                                    # array-like [L] or the path of a text file with one number per landmark
+    use_landmarks: bool = True      # False: a Scene's landmarks are ignored, whatever weight_landmark says
     cam_idxs: Sequence[int] = (0, 1, 2, 3, 4, 5, 6, 7, 8)
     mode: str = "prior"
     regularize_correctives: bool = False
@@ -795,6 +809,7 @@ class FitConfig:
                              "or norm_sigma > 0: weighting the windowed losses is a different rule")
         check_motion_options(self)
         check_tex_prior_options(self)
+        check_landmark_options(self)
 
     def weights_configured(self):
         """Whether the options alone (without a Scene's masks) put iterations on the weighted robust pixel term."""
@@ -991,6 +1006,7 @@ class Fitter:
         if cfg.init_texture == 'bake':
             _, baked = self.bake_texture()
         self._build_prior_terms(motion, baked)
+        self._build_landmarks()
         if self._levels is not None:
             self._set_level(self.pyramid_factor())
 
@@ -1037,6 +1053,70 @@ class Fitter:
                  (self._tex_prior_on, texture_prior, on_texture, [cfg.weight_tex_smooth, cfg.weight_tex_anchor], ["TEXS", "TEXA"], {})]
         self._reg_terms = [PriorTerm(fn, inputs, weights, keys, self.world, eager_grad=True, unit_upstream=True, acc=self._reg_acc, **step)
                            for on, fn, inputs, weights, keys, step in table if on]
+
+    def _build_landmarks(self):
+        """The landmark term's tables on the device ("Landmark rule"), or ValueError: the LandmarkSet, this rank's
+        observations [F_local * n_cam, L, 3] laid out as the targets are, and the scratch of the points' gradients for the most images a
+        step takes.  weight_landmark = 0 or use_landmarks = False: nothing is built.  The term is not one of _reg_terms: it reads the
+        matrices and the step's rows too, so loss_and_backward evaluates it itself (_landmark_term) and hands it over with them."""
+        cfg, sc, dev = self.cfg, self.sc, self.device
+        self._lmk, self._lmk_obs, self._lmk_scratch = None, None, None
+        if not cfg.weight_landmark or not cfg.use_landmarks:
+            return
+        if sc.landmarks is None or not sc.landmark_points:
+            raise ValueError("FitConfig.weight_landmark > 0 needs a Scene with landmarks (Scene.landmark_points and Scene.landmarks; "
+                             "scene.from_take(landmarkpath=...)), or use_landmarks=False")
+        lms = LandmarkSet(sc.landmark_points, sc.n_vertices, sc.pos_idx, dev)
+        if cfg.landmark_weights is not None:
+            lms = lms.with_weights(_load_weights(cfg.landmark_weights, lms.n, 'landmark_weights', 'landmark'))
+        obs = np.asarray(sc.landmarks)
+        if obs.shape != (self.n_frames, len(sc.cams), lms.n, 3):
+            raise ValueError(f"Scene.landmarks must be [{self.n_frames},{len(sc.cams)},{lms.n},3] (got {tuple(obs.shape)})")
+        obs = np.ascontiguousarray(obs[self.frame_lo:self.frame_hi][:, self.cam_idxs], dtype=np.float32)
+        if not (np.isfinite(obs[..., 2]).all() and (obs[..., 2] >= 0).all()):
+            raise ValueError("Scene.landmarks: the confidences must be finite and not negative (0: not observed)")
+        obs[..., :2] = np.where(obs[..., 2:] > 0, obs[..., :2], 0.0)      # (what nobody observed is not read; keep it finite)
+        if not np.isfinite(obs).all():
+            raise ValueError("Scene.landmarks: the position of an observed landmark is not finite")
+        # the pixel grid of the observations: the captures as read (a take fitted at a fixed reduced size keeps its landmarks' own grid:
+        # the projection chain is pure NDC), which is full_resolution everywhere else
+        self._lmk_res = tuple(sc.images.shape[2:]) if sc.images is not None else tuple(self.full_resolution)
+        self._lmk, self._lmk_obs = lms, torch.from_numpy(obs.reshape(-1, lms.n, 3)).to(dev)
+        self._lmk_scratch = torch.empty(self._lmk_obs.shape[0] * lms.n * 3, dtype=torch.float32, device=dev)
+
+    def landmark_on(self, i=None):
+        """Whether iteration i (default: the current one) runs the landmark term (FitConfig.weight_landmark, landmark_iters)."""
+        i = self.iteration if i is None else i
+        return self._lmk is not None and (not self.cfg.landmark_iters or i < self.cfg.landmark_iters)
+
+    def _landmark_term(self, vtx, mvp, rows, step=True, residuals=None):
+        """The landmark term on the step's meshes vtx [Fb,V,3], matrices mvp [Fb*Nc,4,4] and rows (_target_rows) of the observation table.
+        step: the step's form -- the weight / world, the shared accumulator, the gradients made with the value for a unit upstream; else
+        the log's: the full weight, a fresh accumulator."""
+        cfg = self.cfg
+        obs = self._take(self._lmk_obs, 0, rows)
+        kw = dict(eager_grad=True, unit_upstream=True, acc=self._reg_acc, scratch=self._lmk_scratch) if step else {}
+        return landmark_penalty(vtx, mvp, self._lmk, obs, cfg.weight_landmark / self.world if step else cfg.weight_landmark, self._lmk_res,
+                                scale=cfg.landmark_scale, residuals=residuals, validate=False, **kw)
+
+    @torch.no_grad()
+    def landmark_residuals(self, frame_ids=None, view_ids=None):
+        """(u - u*, v - v*) of every landmark at the current parameters, [Fb,Nc,L,2] in full-resolution pixels, NaN where the entry does
+        not count (not observed, a landmark of weight 0, a point behind its camera): the number to look at to judge an alignment.
+        frame_ids: frames of this rank's shard (None: all of them), a slice or an integer tensor; view_ids: positions in cam_idxs."""
+        if self._lmk is None:
+            raise ValueError("Fitter.landmark_residuals needs FitConfig.weight_landmark > 0 on a Scene with landmarks")
+        frames = slice(self.frame_lo, self.frame_hi) if frame_ids is None else frame_ids
+        if torch.is_tensor(frames):
+            frames = frames.to(self.device, torch.long)
+        if view_ids is not None:
+            view_ids = torch.as_tensor(view_ids, dtype=torch.long, device=self.device)
+        self.check_indices(frames, view_ids)
+        Fb, Nc = self._n(frames), (len(self.cam_idxs) if view_ids is None else int(view_ids.shape[0]))
+        vtx = self.vertices(frames, validate=False).reshape(Fb, -1, 3)
+        res = torch.empty(Fb * Nc, self._lmk.n, 2, dtype=torch.float32, device=self.device)
+        self._landmark_term(vtx, self.mvp(frames, view_ids, validate=False), self._target_rows(frames, view_ids), step=False, residuals=res)
+        return res.reshape(Fb, Nc, self._lmk.n, 2)
 
     def texture_chart(self):
         """fit.chart_map of this Fitter's UV mesh at its texture's resolution, float32 [Ht,Wt], built on the first call and kept."""
@@ -1487,6 +1567,8 @@ class Fitter:
         # numbers to hand over), an index tensor names them
         step_ids = frame_ids if torch.is_tensor(frame_ids) else None
         terms = [reg_term(vtx_pos_split, step_ids) for reg_term in self._reg_terms]
+        if self.landmark_on(i):      # (on the step's matrices too: both gradients come with the value)
+            terms.append(self._landmark_term(vtx_pos_split, mvp, rows))
         self.optimizer.zero_grad(set_to_none=True)
         if one_shot:
             bg_sum = None
@@ -1666,6 +1748,8 @@ class Fitter:
                 rec["MNC"] = float(cfg.weight_normalconsistency * mesh_normal_consistency(v, self.topo))
                 for reg_term in self._reg_terms:
                     rec.update(reg_term.log(v, frame_ids if torch.is_tensor(frame_ids) else None))
+                if self.landmark_on(i):      # (the term at its full weight, over every camera of the step's frames)
+                    rec["LMK"] = float(self._landmark_term(v, self.mvp(frame_ids, validate=False), self._target_rows(frame_ids), step=False))
         if rec is None:
             return
         line = json.dumps(rec)
@@ -1692,7 +1776,7 @@ class Fitter:
         Adam + quaternion renormalisation; the gradient all-reduce runs between them, outside any graph.  The set of
         trainable tensors is part of the key: 'combined' mode switches the free-form basis on half way (fit.py:603-608)."""
         switch = self.cfg.mode == 'combined' and (self.iteration - 1) > self.cfg.max_iter / 2
-        key = (switch, tuple(p.requires_grad for p in self.params))
+        key = (switch, tuple(p.requires_grad for p in self.params), self.landmark_on())
         if self._graph_key != key:
             # new set of trainable tensors: one eager step first, so that Adam creates their state outside a capture
             self._graph_key, self._graphs = key, None

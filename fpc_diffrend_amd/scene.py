@@ -43,6 +43,11 @@ class Scene:
     frames: int = 0                          # number of frames when there is no ground truth to count
     masks: Optional[np.ndarray] = None       # [F,Ncam,H,W] uint8, row 0 = bottom: 255 = trust this pixel of the capture, 0 = ignore it
                                              # (the robust pixel loss, DESIGN.md 3 "Robust loss rule"); None = no masks
+    landmark_points: Optional[list] = None   # the landmarks as points of the mesh (landmarks.landmark_tables: {'vertex': i} or
+                                             # {'face': t, 'bary': (b0, b1, b2)}, optional 'name' and 'weight'); None = no landmarks
+    landmarks: Optional[np.ndarray] = None   # [F,Ncam,L,3] float32 = (u, v, confidence) of every landmark in every image, in RASTER pixels of
+                                             # the full-resolution captures (pixel centres at integers, row 0 = bottom); confidence 0 = not
+                                             # observed (the landmark term, DESIGN.md 3 "Landmark rule")
 
     @property
     def n_vertices(self):
@@ -236,7 +241,7 @@ def load_masks(maskdir, cams, n_frames, digits, resolution):
 
 
 def from_take(basemeshpath, localblpath, calibpath, imdir, texpath="", texshape=(1024, 1024, 1), seed=0, undistort=False, device='cuda',
-              maskdir=''):
+              maskdir='', landmarkpath=''):
     """A take on disk in the reference's layout -> Scene (reference fit.py:415-439, 461, 514-533):
 
       basemeshpath  base mesh .obj (v / vt / f v/vt triangles)                       fit.py:424-432, data.py:7-39
@@ -258,7 +263,13 @@ def from_take(basemeshpath, localblpath, calibpath, imdir, texpath="", texshape=
 
     maskdir: a directory laid out like imdir (the same camera directories and file names) of 8-bit single-channel masks, 255 = trust
     this pixel, 0 = ignore it (load_masks): flipped like the images, never clipped, kept in Scene.masks for the robust pixel loss.  They
-    belong to the images as they are read: with undistort=True supply masks of the undistorted views."""
+    belong to the images as they are read: with undistort=True supply masks of the undistorted views.
+
+    landmarkpath: one JSON file {"points": [...], "observations": {camera name: [[[x, y, conf] x L] x F]}} (landmarks.read_landmarks):
+    the landmarks as points of the mesh, and per camera directory (or calibration key), frame and landmark its detected position in pixels
+    of the images as read -- x right, y down, the top-left pixel's centre at (0, 0) -- with the detector's confidence; a null entry or an
+    absent camera is "not observed".  Kept in Scene.landmark_points and, flipped like the images (v = H - 1 - y), in Scene.landmarks.  As
+    for masks: with undistort=True supply landmarks of the undistorted views."""
     cams = sorted(os.listdir(imdir))
     n_frames, digits = data.assert_num_frames(cams, imdir)
     base = data.MeshData(basemeshpath)
@@ -287,8 +298,13 @@ def from_take(basemeshpath, localblpath, calibpath, imdir, texpath="", texshape=
         tex = np.random.default_rng(seed).uniform(low=0.0, high=1.0, size=texshape)   # fit.py:438 (seeded here)
     blend = data.load_blendshape_deltas(localblpath, base.vertices)
     masks = load_masks(maskdir, cams, n_frames, digits, (H, W)) if maskdir else None
+    points, landmarks = None, None
+    if landmarkpath:
+        from .landmarks import read_landmarks
+        points, landmarks = read_landmarks(landmarkpath, cams, n_frames, H)
     return Scene(v_base=base.vertices, pos_idx=base.faces, uv=base.uv, uv_idx=base.fuv, blendshapes=blend,
-                 texture=np.ascontiguousarray(tex, dtype=np.float32), cams=lookup, resolution=(H, W), images=images, masks=masks)
+                 texture=np.ascontiguousarray(tex, dtype=np.float32), cams=lookup, resolution=(H, W), images=images, masks=masks,
+                 landmark_points=points, landmarks=landmarks)
 
 
 def undistort_take(imdir, calibpath, out_dir, device='cuda'):
@@ -307,13 +323,15 @@ def undistort_take(imdir, calibpath, out_dir, device='cuda'):
     return out_dir
 
 
-def write_take(sc, directory, images, cam_idxs=None, blendshape_scale=1.0, distortion=None, masks=None):
+def write_take(sc, directory, images, cam_idxs=None, blendshape_scale=1.0, distortion=None, masks=None, landmarks=None):
     """Write a Scene + reference images [F,Nc,H,W] uint8 (row 0 = bottom) to `directory` in the layout `from_take`
     reads (the reference's, fit.py:415-432, 514-533): basemesh.obj, blendshapes/*.obj, calibration.json,
     images/cam_<name>/cam_<name>_<frame>.tif.  Returns the four paths.  (Test / example helper: the reference ships
     no data.)  distortion: optional [Nc,5] (k1, k2, p1, p2, k3), one row per camera of cam_idxs, written as each camera's
     `distortion`; None writes zeros.  masks: optional [F,Nc,H,W] uint8 (row 0 = bottom), written to <directory>/masks under the
-    images' camera directories and file names -- the `maskdir` of from_take; the four returned paths stay what they were."""
+    images' camera directories and file names -- the `maskdir` of from_take; the four returned paths stay what they were.
+    landmarks: optional [F,Nc,L,3] float32 in raster coordinates, one column per camera of cam_idxs, for the points sc.landmark_points,
+    written to <directory>/landmarks.json -- the `landmarkpath` of from_take (landmarks.write_landmarks)."""
     import json
     from PIL import Image
     cam_idxs = list(range(len(sc.cams))) if cam_idxs is None else list(cam_idxs)
@@ -363,6 +381,11 @@ def write_take(sc, directory, images, cam_idxs=None, blendshape_scale=1.0, disto
             os.makedirs(os.path.join(directory, "masks", name), exist_ok=True)
             for fr in range(F):
                 Image.fromarray(np.flip(masks[fr, j], 0)).save(os.path.join(directory, "masks", name, f"{name}_{fr:0{digits}d}.tif"))
+    if landmarks is not None:
+        from .landmarks import write_landmarks
+        assert sc.landmark_points, "write_take(landmarks=...) needs the points they belong to in sc.landmark_points"
+        write_landmarks(os.path.join(directory, "landmarks.json"), sc.landmark_points, landmarks,
+                        [f"cam_{sc.cams[c]['cam']}" for c in cam_idxs], int(np.asarray(images).shape[2]))
     return base, bldir, calibpath, imdir
 
 

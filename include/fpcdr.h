@@ -450,6 +450,29 @@ int fpcdr_motion_penalty(const float *x, const int64_t *frame_t /* [F] or NULL *
                          void *acc /* F+1 doubles, zero in, zero out */, float *per, float *out, float weight, int32_t F, int32_t V,
                          void *stream);
 
+/* Named points of the mesh held to their detected 2D positions ("Landmark rule"), value and both gradients in one call
+ * (three launches).  Landmark l is the point q = sum_k lm_bary[k][l] * x[f][lm_vtx[k][l]] (k = 0..2); image n = f * Nc + c (frame-major):
+ *   p = mvp[n] . (q, 1),   u = (p.x / p.w * 0.5 + 0.5) * width - 0.5,   v = (p.y / p.w * 0.5 + 0.5) * height - 0.5   (raster pixels of
+ *   the width x height capture: pixel centres at integers, row 0 at the bottom),   s = (u - u*)^2 + (v - v*)^2,
+ *   rho(s) = s  (inv_c = 0: L2)   or   2 c^2 (sqrt(1 + s / c^2) - 1),  c = 1 / inv_c in pixels  (Charbonnier, as fpcdr_motion_penalty)
+ *   per[f] = 1 / (Nc L) * sum_c sum_l lm_w[l] kappa[n][l] rho(s),   out[0] = weight / F * sum_f per[f]   (divided by the number of
+ *   entries, not by the sum of the confidences).
+ * An entry counts when kappa > 0, lm_w[l] > 0 and p.w > 1e-6; any other contributes exactly 0 to the value and to every gradient.
+ * lm_vtx [3,L] int32 and lm_bary [3,L] float32, corner-major (a landmark at a vertex: (v, v, v) with (1, 0, 0)); lm_w [L] float32 >= 0 or
+ * NULL: 1; obs [F*Nc,L,3] float32 = (u*, v*, kappa >= 0).  lm_inc [K,V] int32, slot-major: the landmark corners 3 l + k at every vertex,
+ * ascending, pads -1 trailing.  The vertex ids are NOT checked on the device.
+ * grad_x [F,V,3] and grad_mvp [F*Nc,4,4] = d out / d x and d out / d mvp for a unit upstream (overwritten, every entry: a vertex without
+ * a landmark gets 0, row z of a matrix gets 0), NULL together: value only (scratch and lm_inc may then be NULL).  scratch: caller-owned,
+ * F * Nc * L * 3 floats, left filled with d out / d q.  No float atomics: every output is bit-identical from run to run.
+ * res_out [F*Nc,L,2] or NULL: (u - u*, v - v*), NaN where the entry does not count.  A negative or non-finite inv_c is an error.
+ * acc: (F + 1) * 8 bytes, 8-byte aligned, ZERO on entry; the call leaves it zero again.                                         */
+int fpcdr_landmark_penalty(const float *x, const float *mvp, const int32_t *lm_vtx, const float *lm_bary, const float *lm_w /* [L] or NULL */,
+                           const int32_t *lm_inc, const float *obs, float inv_c /* 0: L2 */, int32_t width, int32_t height,
+                           float *scratch /* F*Nc*L*3 floats */, float *grad_x /* [F,V,3] or NULL: value only */,
+                           float *grad_mvp /* [F*Nc,4,4], NULL with grad_x */, float *res_out /* [F*Nc,L,2] or NULL */,
+                           void *acc /* F+1 doubles, zero in, zero out */, float *per, float *out, float weight, int32_t F, int32_t Nc,
+                           int32_t V, int32_t L, int32_t K, void *stream);
+
 /* The texture's prior ("Texture prior rule"), value and gradient in one call (two launches): smoothness over the pairs of
  * horizontally and vertically neighbouring texels -- none across the border -- and a hold to an anchor texture.
  *   s_pq = || t_p - t_q ||^2 over the C channels,   rho(s) = s  (inv_c = 0: L2)   or   2 s / (1 + sqrt(1 + s / c^2)),  c = 1 / inv_c
