@@ -65,6 +65,27 @@ __global__ void __launch_bounds__(256) k_adam_step(fpcdr_adam_params P) {
         }
         return;
     }
+    if (t.renorm == 2) {
+        // quaternions normalised one by one ("Quaternion normalisation"): one lane updates one row of four and divides it
+        // by its own norm
+        const long long rows = n / 4;
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < rows; i += (long long)gridDim.x * 256) {
+            float p0 = t.param[4 * i], p1 = t.param[4 * i + 1], p2 = t.param[4 * i + 2], p3 = t.param[4 * i + 3];
+            if (t.grad) {
+                float m0 = t.exp_avg[4 * i], m1 = t.exp_avg[4 * i + 1], m2 = t.exp_avg[4 * i + 2], m3 = t.exp_avg[4 * i + 3];
+                float v0 = t.exp_avg_sq[4 * i], v1 = t.exp_avg_sq[4 * i + 1], v2 = t.exp_avg_sq[4 * i + 2], v3 = t.exp_avg_sq[4 * i + 3];
+                adam_one(p0, t.grad[4 * i], m0, v0, P.one_minus_beta1, P.beta2, P.one_minus_beta2, P.eps, step_size, t.bc2_sqrt);
+                adam_one(p1, t.grad[4 * i + 1], m1, v1, P.one_minus_beta1, P.beta2, P.one_minus_beta2, P.eps, step_size, t.bc2_sqrt);
+                adam_one(p2, t.grad[4 * i + 2], m2, v2, P.one_minus_beta1, P.beta2, P.one_minus_beta2, P.eps, step_size, t.bc2_sqrt);
+                adam_one(p3, t.grad[4 * i + 3], m3, v3, P.one_minus_beta1, P.beta2, P.one_minus_beta2, P.eps, step_size, t.bc2_sqrt);
+                t.exp_avg[4 * i] = m0; t.exp_avg[4 * i + 1] = m1; t.exp_avg[4 * i + 2] = m2; t.exp_avg[4 * i + 3] = m3;
+                t.exp_avg_sq[4 * i] = v0; t.exp_avg_sq[4 * i + 1] = v1; t.exp_avg_sq[4 * i + 2] = v2; t.exp_avg_sq[4 * i + 3] = v3;
+            }
+            const float norm = sqrtf((p0 * p0 + p1 * p1) + (p2 * p2 + p3 * p3));
+            t.param[4 * i] = p0 / norm; t.param[4 * i + 1] = p1 / norm; t.param[4 * i + 2] = p2 / norm; t.param[4 * i + 3] = p3 / norm;
+        }
+        return;
+    }
     // a quaternion tensor (quirk Q3: divided by the norm of the WHOLE tensor, fit.py:616-618): one block updates it, reduces
     // the sum of squares of the updated values and divides.  These tensors hold 36 and 4 F floats.
     if (blockIdx.x != 0) return;
@@ -104,6 +125,8 @@ extern "C" int fpcdr_adam_step(const fpcdr_adam_params *p, void *stream) {
         FPCDR_REQUIRE(t.param != nullptr && t.n > 0, "null parameter tensor");
         FPCDR_REQUIRE(t.grad == nullptr || (t.exp_avg && t.exp_avg_sq), "a tensor with a gradient needs its two moment buffers");
         FPCDR_REQUIRE(t.grad != nullptr || t.renorm, "a tensor without a gradient has nothing to do");
+        FPCDR_REQUIRE(t.renorm >= 0 && t.renorm <= 2, "renorm is 0 (none), 1 (the whole tensor) or 2 (every row of four)");
+        FPCDR_REQUIRE(t.renorm != 2 || (t.n & 3) == 0, "renorm = 2: the tensor holds quaternions, n must be a multiple of 4");
         FPCDR_REQUIRE(t.grad == nullptr || p->step_table || t.bc2_sqrt > 0.0f, "the bias correction must be positive");
         if (p->step_table || p->skipped) {
             FPCDR_REQUIRE(t.table_row >= 0 && t.table_row < FPCDR_ADAM_MAX_TENSORS, "table_row outside the table");

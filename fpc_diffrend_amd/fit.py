@@ -35,8 +35,8 @@ import torch
 
 from . import _lib, camera
 from . import ops as dr
-from .landmarks import (LandmarkSet, check_landmark_options, landmark_incidence, landmark_inv_scale, landmark_penalty, landmark_tables,
-                        project_landmarks, read_landmarks, write_landmarks)
+from .landmarks import (LandmarkSet, check_landmark_options, check_pose_options, landmark_incidence, landmark_inv_scale, landmark_penalty,
+                        landmark_tables, project_landmarks, read_landmarks, solve_pose, write_landmarks)
 from .mesh_reg import (MeshTopology, RestShape, _check_item_weights, _uniform_laplacian, bend_penalty, check_motion_options,
                        hinge_incidence, hinge_rest_cs, hinge_vertices, laplacian_penalty, mesh_edge_loss, mesh_laplacian_smoothing,
                        mesh_normal_consistency, motion_inv_scale, motion_penalty, rest_edge_lengths, stretch_penalty)
@@ -491,11 +491,14 @@ class GroupedAdam(torch.optim.Optimizer):
     step.  State layout and names are torch.optim.Adam's ('step', 'exp_avg', 'exp_avg_sq'), so LambdaLR, state_dict() and
     checkpoints work unchanged (the update is the same formula evaluated in a slightly different order -- step_size * (m / denom) --
     so a run with grouped_adam on and one with it off agree to a few ulps per step, not bit for bit).  `renorm` = the parameters
-    divided by their whole-tensor norm after every step."""
+    divided by their whole-tensor norm after every step; renorm_rows: every row of four of them by its own norm instead
+    (fpcdr_adam_tensor.renorm = 2; FitConfig.quat_renorm='rows')."""
 
-    def __init__(self, groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, renorm=(), capturable=False):
+    def __init__(self, groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, renorm=(), capturable=False, renorm_rows=False):
         super().__init__(groups, dict(lr=lr, betas=betas, eps=eps))
         self._renorm = {id(p) for p in renorm}
+        self._renorm_kind = 2 if renorm_rows else 1
+        assert not renorm_rows or all(p.numel() % 4 == 0 for p in renorm), "renorm_rows: the tensors hold quaternions"
         n = sum(len(g['params']) for g in self.param_groups)
         assert n <= _lib.ADAM_MAX_TENSORS, "more parameter tensors than one fpcdr_adam_step call takes"
         # capturable: the launch may be captured in a HIP graph.  Its per-tensor (step_size, bc2_sqrt) then come from a device table
@@ -624,7 +627,7 @@ class GroupedAdam(torch.optim.Optimizer):
                     continue
                 assert p.is_contiguous() and p.dtype == torch.float32
                 t = P.t[k]
-                t.param, t.n, t.renorm, t.table_row = p.data_ptr(), p.numel(), 1 if ren else 0, row
+                t.param, t.n, t.renorm, t.table_row = p.data_ptr(), p.numel(), self._renorm_kind if ren else 0, row
                 t.step_size, t.bc2_sqrt = 0.0, 1.0
                 if p.grad is not None:
                     st = self._state_of(p)
@@ -706,6 +709,13 @@ class FitConfig:
     landmark_weights: object = None              # one weight per landmark, finite and >= 0, in place of the points' own 'weight': an
                                     # array-like [L] or the path of a text file with one number per landmark
     use_landmarks: bool = True      # False: a Scene's landmarks are ignored, whatever weight_landmark says
+    init_pose: str = "keep"         # 'keep' | 'landmarks': every frame's rigid pose is solved from its landmarks at the end of construction
+                                    # (Fitter.align_to_landmarks; DESIGN.md 3, "Pose solve rule"), before init_texture='bake' reads the pose.
+                                    # Needs a Scene with landmarks and use_landmarks, not weight_landmark > 0
+    init_pose_iters: int = 20       # the trials of that solve
+    init_pose_rotation: bool = True             # False: the translation alone (the only form quat_renorm='tensor' keeps on several frames)
+    quat_renorm: str = "tensor"     # 'tensor': the reference's division of q_opt and per_frame_q by the norm of the WHOLE tensor after every
+                                    # step (quirk Q3) | 'rows': every quaternion divided by its own norm, so that a rotation survives the loop
     cam_idxs: Sequence[int] = (0, 1, 2, 3, 4, 5, 6, 7, 8)
     mode: str = "prior"
     regularize_correctives: bool = False
@@ -810,6 +820,7 @@ class FitConfig:
         check_motion_options(self)
         check_tex_prior_options(self)
         check_landmark_options(self)
+        check_pose_options(self)
 
     def weights_configured(self):
         """Whether the options alone (without a Scene's masks) put iterations on the weighted robust pixel term."""
@@ -918,17 +929,18 @@ class Fitter:
                                              self.resolution)
         else:
             self.use_graph = bool(cfg.hip_graph)
+        rows = cfg.quat_renorm == 'rows'
         if self.use_graph and cfg.grouped_adam:
             # a replayed update reads its learning rates and bias corrections from a device table (GroupedAdam.prepare): ONE launch in the
             # graph.  (torch.optim.Adam(capturable=True) is ~13 multi-tensor launches per parameter group: 140 of the 190 dispatches of a
             # replayed one-image step, 0.6 ms of 4.5 us nodes)
-            self.optimizer = GroupedAdam(groups, lr=cfg.lr_base, renorm=(self.q_opt, self.per_frame_q), capturable=True)
+            self.optimizer = GroupedAdam(groups, lr=cfg.lr_base, renorm=(self.q_opt, self.per_frame_q), capturable=True, renorm_rows=rows)
         elif self.use_graph:      # replayed updates read the learning rates from device memory
             for g in groups:
                 g['lr'] = torch.tensor(float(g['lr']), dtype=torch.float32, device=dev)
             self.optimizer = torch.optim.Adam(groups, lr=torch.tensor(cfg.lr_base, dtype=torch.float32, device=dev), capturable=True)
         else:
-            self.optimizer = GroupedAdam(groups, lr=cfg.lr_base, renorm=(self.q_opt, self.per_frame_q)) if cfg.grouped_adam \
+            self.optimizer = GroupedAdam(groups, lr=cfg.lr_base, renorm=(self.q_opt, self.per_frame_q), renorm_rows=rows) if cfg.grouped_adam \
                 else torch.optim.Adam(groups, lr=cfg.lr_base, fused=True)
         # a step whose pixel objective ran out of record slots (ops.pixel_objective, skip_out) is skipped ON THE DEVICE: the call's last
         # kernel writes the flag, the gradient bucket carries it over the ranks, the Adam launch reads it -- no host read-back, no
@@ -1002,6 +1014,10 @@ class Fitter:
                 lres = (self.resolution[0] // s, self.resolution[1] // s)
                 lm = dr.downsample_images(self.full_masks, s) if self.full_masks is not None else None
                 self._levels[s] = (lt, lres, dr.reference_background_sumsq(lt.reshape(-1, *lres), BACKGROUND).reshape(lt.shape[:2]), lm)
+        self._pose_tables = None     # (the landmark tables of align_to_landmarks where the landmark term has not built its own)
+        self._lmk = None
+        if cfg.init_pose == 'landmarks':      # (in front of the bake, which reads the pose)
+            self.align_to_landmarks(iters=cfg.init_pose_iters, rotation=cfg.init_pose_rotation)
         baked = None
         if cfg.init_texture == 'bake':
             _, baked = self.bake_texture()
@@ -1059,12 +1075,24 @@ class Fitter:
         observations [F_local * n_cam, L, 3] laid out as the targets are, and the scratch of the points' gradients for the most images a
         step takes.  weight_landmark = 0 or use_landmarks = False: nothing is built.  The term is not one of _reg_terms: it reads the
         matrices and the step's rows too, so loss_and_backward evaluates it itself (_landmark_term) and hands it over with them."""
-        cfg, sc, dev = self.cfg, self.sc, self.device
+        cfg = self.cfg
         self._lmk, self._lmk_obs, self._lmk_scratch = None, None, None
         if not cfg.weight_landmark or not cfg.use_landmarks:
             return
+        self._lmk, self._lmk_obs, self._lmk_res = self._landmark_tables("FitConfig.weight_landmark > 0")
+        self._lmk_scratch = torch.empty(self._lmk_obs.shape[0] * self._lmk.n * 3, dtype=torch.float32, device=self.device)
+
+    def _landmark_tables(self, who):
+        """(the LandmarkSet with the configured weights, this rank's observations [F_local * n_cam, L, 3], the observations' pixel grid) on
+        the device, or ValueError in the name of `who`: the landmark term's own if it has built them, else built on first use and kept
+        (Fitter.align_to_landmarks needs them without weight_landmark > 0)."""
+        cfg, sc, dev = self.cfg, self.sc, self.device
+        if self._lmk is not None:
+            return self._lmk, self._lmk_obs, self._lmk_res
+        if getattr(self, "_pose_tables", None) is not None:
+            return self._pose_tables
         if sc.landmarks is None or not sc.landmark_points:
-            raise ValueError("FitConfig.weight_landmark > 0 needs a Scene with landmarks (Scene.landmark_points and Scene.landmarks; "
+            raise ValueError(f"{who} needs a Scene with landmarks (Scene.landmark_points and Scene.landmarks; "
                              "scene.from_take(landmarkpath=...)), or use_landmarks=False")
         lms = LandmarkSet(sc.landmark_points, sc.n_vertices, sc.pos_idx, dev)
         if cfg.landmark_weights is not None:
@@ -1080,9 +1108,81 @@ class Fitter:
             raise ValueError("Scene.landmarks: the position of an observed landmark is not finite")
         # the pixel grid of the observations: the captures as read (a take fitted at a fixed reduced size keeps its landmarks' own grid:
         # the projection chain is pure NDC), which is full_resolution everywhere else
-        self._lmk_res = tuple(sc.images.shape[2:]) if sc.images is not None else tuple(self.full_resolution)
-        self._lmk, self._lmk_obs = lms, torch.from_numpy(obs.reshape(-1, lms.n, 3)).to(dev)
-        self._lmk_scratch = torch.empty(self._lmk_obs.shape[0] * lms.n * 3, dtype=torch.float32, device=dev)
+        res = tuple(sc.images.shape[2:]) if sc.images is not None else tuple(self.full_resolution)
+        self._pose_tables = (lms, torch.from_numpy(obs.reshape(-1, lms.n, 3)).to(dev), res)
+        return self._pose_tables
+
+    @torch.no_grad()
+    def align_to_landmarks(self, frame_ids=None, iters=20, rotation=True, reduce=None):
+        """Solve every frame's rigid pose from its landmarks ("Pose solve rule"; fit.solve_pose), in ONE launch, at the
+        current meshes (Fitter.vertices) and camera poses: the first stage of a landmark-driven fit, for a take whose head is not where
+        the calibration puts it -- Adam at lr_t = 1e-5 cannot travel there.  Every camera of cam_idxs, the configured landmark_scale and
+        landmark_weights.  Needs a Scene with landmarks and use_landmarks, NOT weight_landmark > 0: a fit may use its landmarks for the
+        start only; the tables are built on first use.
+
+          frame_ids  frames of this rank's shard (None: all of them), a sequence or an integer tensor
+          iters      trials of the damped Gauss-Newton solve
+          rotation   False: the translation alone.  True on more than one frame needs quat_renorm='rows': the whole-tensor division
+                     (quirk Q3) scales every row to 1 / sqrt(F), and rigid() applies q as it stands, R(q / sqrt(F)) = I + (R(q) - I) / F
+          reduce     reduce(delta) -> delta sums the float32 [F,7] table of (q, t) changes, zero outside this rank's frames, over the ranks
+                     (bake_texture's convention); None: one all_reduce(SUM) when world > 1 and torch.distributed is initialised.  The
+                     replicated parameters stay identical on every rank
+
+        per_frame_q / per_frame_t are written in place (a captured graph replays with them); Adam's moments stay as they are: call it
+        before the first step.  Returns {'before', 'after'}: the mean live |residual| in pixels over the solved frames, and 'info'
+        [Fb,4] = (cost before, cost after, live entries, accepted trials) per frame."""
+        cfg, dev = self.cfg, self.device
+        if not cfg.use_landmarks:
+            raise ValueError("Fitter.align_to_landmarks needs FitConfig.use_landmarks")
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
+            raise ValueError(f"Fitter.align_to_landmarks: iters must be an integer >= 0 (got {iters!r})")
+        if rotation and cfg.quat_renorm == 'tensor' and self.n_frames > 1:
+            raise ValueError("Fitter.align_to_landmarks(rotation=True) on more than one frame needs FitConfig.quat_renorm='rows': under "
+                             "'tensor' every step divides per_frame_q by the norm of the WHOLE tensor, each row comes out at 1 / sqrt(F), "
+                             "and the solved rotation is turned back to almost none (use rotation=False, or quat_renorm='rows')")
+        lms, obs_all, res = self._landmark_tables("Fitter.align_to_landmarks")
+        if frame_ids is None:
+            frames = torch.arange(self.frame_lo, self.frame_hi, device=dev)
+        else:
+            frames = torch.as_tensor(frame_ids).to(dev).reshape(-1)
+        self.check_indices(frames)
+        frames = frames.long()
+        Fb, Nc = int(frames.shape[0]), len(self.cam_idxs)
+        verts = self.vertices(frames, validate=False).reshape(Fb, -1, 3).contiguous()
+        # base[c] = Rt(q_c, t_c) . MV_c . T(0,170,0), the float32 product k_mvp_fwd forms: its own launch with the frame at the identity and
+        # the identity for the projection (a product with the identity is exact)
+        eye_q = torch.tensor([[0.0, 0.0, 0.0, 1.0]], dtype=torch.float32, device=dev)
+        all_cams = self.cam_idxs == list(range(self.q_opt.shape[0]))
+        q_c, t_c = (self.q_opt, self.t_opt) if all_cams else (self.q_opt[self.cam_sel], self.t_opt[self.cam_sel])
+        base = _mvp_func.apply(q_c.detach(), t_c.detach(), eye_q, torch.zeros(1, 3, dtype=torch.float32, device=dev),
+                               torch.eye(4, dtype=torch.float32, device=dev).expand(Nc, 4, 4).contiguous(), self.t_mv,
+                               None, None, None, None, None, None)
+        obs = obs_all.index_select(0, self._target_rows(frames))
+        q, t = self.per_frame_q.detach().index_select(0, frames).contiguous(), self.per_frame_t.detach().index_select(0, frames).contiguous()
+        q0, t0 = q.clone(), t.clone()
+        kw = dict(scale=cfg.landmark_scale, rotation=bool(rotation))
+
+        def mean_residual():
+            rr = torch.empty(Fb * Nc, lms.n, 2, dtype=torch.float32, device=dev)
+            landmark_penalty(verts, self.mvp(frames, validate=False), lms, obs, 1.0, res, scale=cfg.landmark_scale, residuals=rr, validate=False)
+            live = ~torch.isnan(rr[..., 0])
+            return float(rr[live].double().norm(dim=1).mean()) if bool(live.any()) else float('nan')
+
+        before = mean_residual()
+        info = solve_pose(verts, self.proj, base, lms, obs, q, t, res, iters=int(iters), **kw)
+        delta = torch.zeros(self.n_frames, 7, dtype=torch.float32, device=dev)
+        delta.index_copy_(0, frames, torch.cat([q - q0, t - t0], dim=1))
+        if reduce is not None:
+            delta = reduce(delta)
+        elif self.world > 1:
+            import torch.distributed as tdist
+            if tdist.is_available() and tdist.is_initialized():
+                tdist.all_reduce(delta, op=tdist.ReduceOp.SUM)
+        # (every rank applies the same sum to the same table, its own rows included: a row nobody solved adds an exact 0, a solved row
+        #  is its old value plus the rounded difference -- the solved value itself from the identity start, within an ulp of it otherwise)
+        self.per_frame_q.add_(delta[:, :4])
+        self.per_frame_t.add_(delta[:, 4:])
+        return {'before': before, 'after': mean_residual(), 'info': info}
 
     def landmark_on(self, i=None):
         """Whether iteration i (default: the current one) runs the landmark term (FitConfig.weight_landmark, landmark_iters)."""
@@ -1104,8 +1204,10 @@ class Fitter:
         """(u - u*, v - v*) of every landmark at the current parameters, [Fb,Nc,L,2] in full-resolution pixels, NaN where the entry does
         not count (not observed, a landmark of weight 0, a point behind its camera): the number to look at to judge an alignment.
         frame_ids: frames of this rank's shard (None: all of them), a slice or an integer tensor; view_ids: positions in cam_idxs."""
-        if self._lmk is None:
+        tables = (self._lmk, self._lmk_obs, self._lmk_res) if self._lmk is not None else self._pose_tables
+        if tables is None:      # (neither the term nor align_to_landmarks has built them)
             raise ValueError("Fitter.landmark_residuals needs FitConfig.weight_landmark > 0 on a Scene with landmarks")
+        lms, obs_all, lres = tables
         frames = slice(self.frame_lo, self.frame_hi) if frame_ids is None else frame_ids
         if torch.is_tensor(frames):
             frames = frames.to(self.device, torch.long)
@@ -1114,9 +1216,10 @@ class Fitter:
         self.check_indices(frames, view_ids)
         Fb, Nc = self._n(frames), (len(self.cam_idxs) if view_ids is None else int(view_ids.shape[0]))
         vtx = self.vertices(frames, validate=False).reshape(Fb, -1, 3)
-        res = torch.empty(Fb * Nc, self._lmk.n, 2, dtype=torch.float32, device=self.device)
-        self._landmark_term(vtx, self.mvp(frames, view_ids, validate=False), self._target_rows(frames, view_ids), step=False, residuals=res)
-        return res.reshape(Fb, Nc, self._lmk.n, 2)
+        res = torch.empty(Fb * Nc, lms.n, 2, dtype=torch.float32, device=self.device)
+        landmark_penalty(vtx, self.mvp(frames, view_ids, validate=False), lms, self._take(obs_all, 0, self._target_rows(frames, view_ids)),
+                         self.cfg.weight_landmark, lres, scale=self.cfg.landmark_scale, residuals=res, validate=False)
+        return res.reshape(Fb, Nc, lms.n, 2)
 
     def texture_chart(self):
         """fit.chart_map of this Fitter's UV mesh at its texture's resolution, float32 [Ht,Wt], built on the first call and kept."""
@@ -1675,6 +1778,10 @@ class Fitter:
         if not self._grouped:
             self.optimizer.step()
             with torch.no_grad():   # fit.py:616-618 (Q3: whole-tensor norm)
+                if self.cfg.quat_renorm == 'rows':      # (every quaternion by its own norm, summed as the kernel sums it)
+                    for q in (self.q_opt, self.per_frame_q):
+                        q /= torch.sqrt((q[:, 0:1] * q[:, 0:1] + q[:, 1:2] * q[:, 1:2]) + (q[:, 2:3] * q[:, 2:3] + q[:, 3:4] * q[:, 3:4]))
+                    return
                 self.q_opt /= torch.sum(self.q_opt ** 2) ** 0.5
                 self.per_frame_q /= torch.sum(self.per_frame_q ** 2) ** 0.5
             return

@@ -188,6 +188,81 @@ def landmark_penalty(verts, mvp, lms, obs, weight, resolution, scale=None, eager
                                    bool(eager_grad and unit_upstream), acc, scratch, residuals)
 
 
+def check_pose_options(cfg):
+    """What FitConfig's init_pose / quat_renorm fields ask (FitConfig.__post_init__), or ValueError.  Needs no GPU and no Scene."""
+    if cfg.init_pose not in ('keep', 'landmarks'):
+        raise ValueError(f"FitConfig.init_pose must be 'keep' or 'landmarks' (got {cfg.init_pose!r})")
+    if cfg.quat_renorm not in ('tensor', 'rows'):
+        raise ValueError(f"FitConfig.quat_renorm must be 'tensor' or 'rows' (got {cfg.quat_renorm!r})")
+    n = cfg.init_pose_iters
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+        raise ValueError(f"FitConfig.init_pose_iters must be an integer >= 0 (got {n!r})")
+    if not isinstance(cfg.init_pose_rotation, bool):
+        raise ValueError(f"FitConfig.init_pose_rotation must be True or False (got {cfg.init_pose_rotation!r})")
+
+
+def solve_pose(verts, proj, base, lms, obs, q, t, resolution, scale=None, iters=20, rotation=True, damping=1e-3, normal_out=None):
+    """Every frame's rigid pose (q [F,4] XYZW, t [F,3], float32, written IN PLACE) solved from its landmarks by damped Gauss-Newton on the
+    Landmark rule's cost, one launch for all frames ("Pose solve rule"; fpcdr_landmark_pose): the chain is
+    proj[c] . Rt(q_f / |q_f|, t_f) . base[c] on the meshes verts [F,V,3], proj and base [Nc,4,4] float32 (base = Rt(q_c, t_c) . MV_c .
+    T(0,170,0)), lms a LandmarkSet, obs [F*Nc,L,3] = (u*, v*, kappa) in raster pixels of a resolution = (H, W) capture, scale the
+    Charbonnier scale in pixels (None: L2).  iters trials from the damping `damping`; a trial is kept when it has at least as many live
+    entries and a smaller cost.  rotation=False: the translation alone, q is not written.  A frame with fewer than 3 live entries stays
+    bit for bit as it was.  normal_out: a contiguous float32 tensor [F,28] that receives A's upper triangle (21), b (6) and the cost at
+    the INPUT pose (iters=0: nothing else happens).  -> info [F,4] float32 = (cost at the input pose, cost at the returned pose, live
+    entries at the returned pose, accepted trials).  ValueError names what does not fit."""
+    inv_c = landmark_inv_scale(scale)
+    if not isinstance(lms, LandmarkSet):
+        raise ValueError(f"solve_pose: lms must be a LandmarkSet (got {type(lms).__name__})")
+    if not torch.is_tensor(verts) or verts.dim() != 3 or verts.shape[2] != 3 or verts.dtype != torch.float32:
+        raise ValueError(f"solve_pose: verts must be float32 [F,V,3] (got {getattr(verts, 'dtype', None)} {tuple(getattr(verts, 'shape', ()))})")
+    F, V = int(verts.shape[0]), int(verts.shape[1])
+    if F < 1 or V != lms.n_vertices:
+        raise ValueError(f"solve_pose: verts must hold at least one mesh of the landmark set's {lms.n_vertices} vertices (got {tuple(verts.shape)})")
+    dev = verts.device
+    for name, m in (('proj', proj), ('base', base)):
+        if not torch.is_tensor(m) or m.dim() != 3 or tuple(m.shape[1:]) != (4, 4) or m.dtype != torch.float32 or m.shape[0] < 1 or m.device != dev:
+            raise ValueError(f"solve_pose: {name} must be float32 [Nc,4,4] on the device of verts (got {tuple(getattr(m, 'shape', ()))})")
+    Nc = int(proj.shape[0])
+    if int(base.shape[0]) != Nc:
+        raise ValueError(f"solve_pose: proj and base must hold the same cameras (got {Nc} and {int(base.shape[0])})")
+    if not torch.is_tensor(obs) or obs.dtype != torch.float32 or tuple(obs.shape) != (F * Nc, lms.n, 3) or obs.device != dev:
+        raise ValueError(f"solve_pose: obs must be a float32 tensor [{F * Nc},{lms.n},3] on the device of verts")
+    for name, p, k in (('q', q, 4), ('t', t, 3)):
+        if not torch.is_tensor(p) or p.dtype != torch.float32 or tuple(p.shape) != (F, k) or p.device != dev or not p.is_contiguous():
+            raise ValueError(f"solve_pose: {name} must be a contiguous float32 tensor [{F},{k}] on the device of verts "
+                             f"(got {tuple(getattr(p, 'shape', ()))})")
+    try:
+        H, W = (int(v) for v in resolution)
+    except (TypeError, ValueError):
+        raise ValueError(f"solve_pose: resolution must be (H, W) (got {resolution!r})")
+    if H < 1 or W < 1:
+        raise ValueError(f"solve_pose: resolution must be (H, W), both positive (got {resolution!r})")
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
+        raise ValueError(f"solve_pose: iters must be an integer >= 0 (got {iters!r})")
+    if isinstance(damping, bool) or not isinstance(damping, (int, float)) or not np.isfinite(damping) or not damping > 0:
+        raise ValueError(f"solve_pose: damping must be finite and positive (got {damping!r})")
+    if lms.vtx.device != dev:
+        raise ValueError(f"solve_pose: the landmark set must be on the device of verts ({dev})")
+    if normal_out is not None and (not torch.is_tensor(normal_out) or normal_out.dtype != torch.float32 or tuple(normal_out.shape) != (F, 28)
+                                   or normal_out.device != dev or not normal_out.is_contiguous()):
+        raise ValueError(f"solve_pose: normal_out must be a contiguous float32 tensor [{F},28] on the device of verts")
+    if not (verts.is_cuda and torch.cuda.is_current_stream_capturing()):
+        k = obs[..., 2]
+        if not bool((torch.isfinite(k) & (k >= 0)).all()):
+            raise ValueError("solve_pose: the confidences obs[..., 2] must be finite and not negative")
+        qn = q.detach().double().norm(dim=1)
+        if not bool((torch.isfinite(qn) & (qn > 0)).all()):
+            bad = int(torch.nonzero(~(torch.isfinite(qn) & (qn > 0)))[0])
+            raise ValueError(f"solve_pose: the norm of q[{bad}] must be finite and positive (got {q[bad].tolist()})")
+    info = torch.empty(F, 4, dtype=torch.float32, device=dev)
+    x, pj, bs, ob = verts.detach().contiguous(), proj.detach().contiguous(), base.detach().contiguous(), obs.contiguous()
+    _lib.call("fpcdr_landmark_pose", _ptr(x), _ptr(pj), _ptr(bs), _ptr(lms.vtx), _ptr(lms.bary), _ptr(lms.w), _ptr(ob), _ptr(q.detach()),
+              _ptr(t.detach()), float(inv_c), W, H, int(iters), 1 if rotation else 0, float(damping), _ptr(info), _ptr(normal_out), F, Nc, V,
+              lms.n, _stream())
+    return info
+
+
 def project_landmarks(sc, lms_points, cam_idxs=None):
     """The landmarks of a synthetic Scene at its hidden ground truth, float64 numpy through camera.py's own chain (fit.py:541-553 of the
     reference: P . Rt(q_f, t_f) . MV_c . T(0, 170, 0)): [F,Ncam,L,3] = (u, v, kappa) in raster pixels of sc.resolution, kappa = 1 (0 for a

@@ -473,6 +473,31 @@ int fpcdr_landmark_penalty(const float *x, const float *mvp, const int32_t *lm_v
                            void *acc /* F+1 doubles, zero in, zero out */, float *per, float *out, float weight, int32_t F, int32_t Nc,
                            int32_t V, int32_t L, int32_t K, void *stream);
 
+/* Every frame's rigid pose solved from its landmarks ("Pose solve rule"), ONE launch for all F frames, every trial inside it.
+ * A pure addition: FPCDR_ABI_VERSION stays 16.  The chain is the fit's, mvp[f,c] = proj[c] . Rt(q_f, t_f) . base[c] with
+ * base[c] = Rt(q_c, t_c) . MV_c . T(0,170,0) as fpcdr_mvp_fwd forms it in float32; for frame f, image c and landmark l (the tables and obs
+ * of fpcdr_landmark_penalty):
+ *   y = base[c] (q_l, 1) (three rows),  a = R(q_f / |q_f|) y,  z = a + t_f,  p = proj[c] (z, 1) (rows x, y, w),  u, v, live, the residual
+ *   r, s = |r|^2, rho and d = rho'(s) exactly as fpcdr_landmark_penalty has them;  E_f = sum over the live entries of lm_w kappa rho(s).
+ *   g_u = (width / 2) / p.w * (proj_x[0:3] - (p.x / p.w) proj_w[0:3]), g_v with height and proj_y;  J_u = (a x g_u, g_u), J_v alike: the
+ *   residual's Jacobian for a left-multiplied rotation increment and a translation increment;  with w = lm_w kappa d:
+ *   A = sum w (J_u^T J_u + J_v^T J_v),  b = sum w (J_u r_u + J_v r_v), summed over the frame's Nc L entries in a fixed order (no float
+ *   atomics: bit-identical from run to run).
+ * A trial solves (A + lambda diag A) delta = -b in float64 by Cholesky (a pivot that is not positive: a rejected trial), forms
+ * q' = normalise(exp(delta_omega / 2) (x) q / |q|) and t' = t + delta_t, rounded to float32, and is accepted iff it has at least as many
+ * live entries and a smaller E; then lambda <- max(lambda / 10, 1e-9), otherwise lambda <- min(10 lambda, 1e9).  `iters` trials, lambda
+ * starting at lambda0.  rotation = 0: the translation block alone; q is not written.  A frame with fewer than 3 live entries at its
+ * input pose, or without an accepted trial, keeps q and t bit for bit.
+ * q [F,4] (XYZW) and t [F,3]: in and out.  info [F,4] = (E at the input pose, E at the returned pose, live entries at the returned pose,
+ * accepted trials).  normal_out [F,28] or NULL: A's upper triangle row-major (21), b (6) and E at the INPUT pose; iters = 0 returns only
+ * this (and info).  The vertex ids are NOT checked on the device.  A negative or non-finite inv_c, a lambda0 that is not finite and
+ * positive, Nc * L > 2^24 are errors.                                                                                                */
+int fpcdr_landmark_pose(const float *x /* [F,V,3] */, const float *proj /* [Nc,4,4] */, const float *base /* [Nc,4,4] */,
+                        const int32_t *lm_vtx, const float *lm_bary, const float *lm_w /* [L] or NULL */, const float *obs /* [F*Nc,L,3] */,
+                        float *q /* [F,4] */, float *t /* [F,3] */, float inv_c /* 0: L2 */, int32_t width, int32_t height, int32_t iters,
+                        int32_t rotation, float lambda0, float *info /* [F,4] */, float *normal_out /* [F,28] or NULL */, int32_t F,
+                        int32_t Nc, int32_t V, int32_t L, void *stream);
+
 /* The texture's prior ("Texture prior rule"), value and gradient in one call (two launches): smoothness over the pairs of
  * horizontally and vertically neighbouring texels -- none across the border -- and a hold to an anchor texture.
  *   s_pq = || t_p - t_q ||^2 over the C channels,   rho(s) = s  (inv_c = 0: L2)   or   2 s / (1 + sqrt(1 + s / c^2)),  c = 1 / inv_c
@@ -559,8 +584,9 @@ typedef struct {
     float step_size;       /* lr / (1 - beta1^step): the group's learning rate of this step (schedule applied by the caller) over
                               the first bias correction, divided in double precision as torch does */
     float bc2_sqrt;        /* sqrt(1 - beta2^step) */
-    int32_t renorm;
-    int32_t table_row;     /* ABI v10, with fpcdr_adam_params.step_table: this tensor's row of the table (step_size / bc2_sqrt above unused);
+    int32_t renorm;        /* 0: none; 1: divided by the norm of the WHOLE tensor (above); 2 (a pure addition): every row of four divided by
+                              its own norm, one lane a row -- n % 4 == 0 ("Quaternion normalisation") */
+    int32_t table_row;    /* ABI v10, with fpcdr_adam_params.step_table: this tensor's row of the table (step_size / bc2_sqrt above unused);
                               ABI v12, with fpcdr_adam_params.skipped: its entry of skipped_per_tensor */
     /* ABI v11, with fpcdr_adam_params.skipped: what step_size / bc2_sqrt were formed from -- the tensor's step count (this step included)
      * and its learning rate --, so that the kernel can re-form them for the steps that were not skipped */
