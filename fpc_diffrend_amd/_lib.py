@@ -236,6 +236,8 @@ SYMBOLS = {
     "fpcdr_bake_resolve": (_int, [_p, _p, _p, _i, _i, ctypes.c_double, ctypes.c_uint64, _p]),
     "fpcdr_bake_dilate": (_int, [_p, _p, _p, _p, _i, _i, _p]),
     "fpcdr_downsample_u8": (_int, [_p, _p, ctypes.c_int64, _i, _i, _i, _p]),
+    "fpcdr_exposure_sums": (_int, [_p, _p, _p, _p, _p, _i, _i, _i, ctypes.c_int64, _i, _i, _i, _p, _p]),
+    "fpcdr_apply_lut_u8": (_int, [_p, _p, _p, _i, ctypes.c_int64, ctypes.c_int64, _p]),
 }
 
 # the two-call form of the pixel objective + the fused render pair (include/fpcdr_twocall.h): exported by libfpcdr_twocall.so only

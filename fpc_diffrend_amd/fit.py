@@ -35,6 +35,7 @@ import torch
 
 from . import _lib, camera
 from . import ops as dr
+from .exposure import check_exposure_options, compose, fit_gains, identity_lut, is_identity
 from .landmarks import (LandmarkSet, check_landmark_options, check_pose_options, landmark_incidence, landmark_inv_scale, landmark_penalty,
                         landmark_tables, project_landmarks, read_landmarks, solve_pose, write_landmarks)
 from .mesh_reg import (MeshTopology, RestShape, _check_item_weights, _uniform_laplacian, bend_penalty, check_motion_options,
@@ -796,6 +797,17 @@ class FitConfig:
                                     # shading, a level without mip (fit.weighted_one_pass_term) -- and the operator path elsewhere: the same
                                     # term, the image never in memory.  False: the operator path everywhere, as it was.  hip_graph with
                                     # weights keeps raising
+    equalise_exposure_at: Sequence[int] = ()  # iterations at whose START step() calls Fitter.equalise_exposure() ("Exposure
+                                    # rule"): every camera's gain and offset are fitted against the fit's own render, and this rank's
+                                    # captures are mapped onto one common level, once, in place -- plain 8-bit targets again, so every fast
+                                    # path runs on as it stands and nothing is paid per step.  Meant for one or two entries, once the
+                                    # geometry is roughly right (after the norm_sigma or landmark iterations).  () = off: nothing is built,
+                                    # allocated, cloned or launched, and a step is exactly the path it was
+    equalise_method: str = 'regression'       # 'regression' | 'moments' (exposure.fit_gains)
+    equalise_anchor_camera: Optional[int] = None   # a value of cam_idxs: that camera's captures stay as they are, bit for bit, and the
+                                    # others are mapped onto its level.  None: onto the mean level of the usable cameras
+    equalise_max_gain: float = 4.0  # > 1: a camera whose gain ratio lies outside [1 / max_gain, max_gain] is left alone.  A cap, not a
+                                    # measurement: beyond two stops 8-bit data has nothing left to map
     log_interval: int = 0           # every n steps one JSON line {it, loss, lr, frames_per_s} (reference print, fit.py:621-623); an
                                     # iteration on the robust term adds "wsum", the sum of its weights over rank 0's batch
     reg_log_interval: int = 500     # every n steps the regulariser breakdown MEL / LAP / MNC (reference fit.py:597-601)
@@ -821,6 +833,7 @@ class FitConfig:
         check_tex_prior_options(self)
         check_landmark_options(self)
         check_pose_options(self)
+        check_exposure_options(self)
 
     def weights_configured(self):
         """Whether the options alone (without a Scene's masks) put iterations on the weighted robust pixel term."""
@@ -977,8 +990,15 @@ class Fitter:
         self.iteration = 0
         self._log_file, self._log_t, self._log_it = None, None, 0
         # ---- reference images, resident in HBM as 8 bit [F_local, n_cam, H, W] (fit.py:529-533) ----
+        # exposure ("Exposure rule"): the composite table applied to this rank's captures so far (None: the identity), the last
+        # fit, and whether the targets are the Fitter's own -- a tensor it was handed is never written into
+        self._exposure_total, self._exposure_fit = None, None
+        self._equalise_at = frozenset(int(i) for i in cfg.equalise_exposure_at)
+        self._targets_own = targets is None
         if targets is not None:
             self.targets = targets
+            if self._equalise_at:      # (cloned once, here; without the option: at the first call of equalise_exposure)
+                self.targets, self._targets_own = targets.clone(), True
         elif sc.images is not None:      # a take from disk: this rank's frames x the selected cameras
             self.targets = torch.from_numpy(np.ascontiguousarray(sc.images[self.frame_lo:self.frame_hi][:, self.cam_idxs])).to(dev)
             if tuple(sc.images.shape[2:]) != self.resolution:      # a fixed reduced size: the captures box-reduced once
@@ -1482,6 +1502,131 @@ class Fitter:
             self.tex_opt.copy_(tex)
         return tex, filled
 
+    def render_full(self, glctx, frame_ids):
+        """(colour [Fb*Nc,H,W,C], rast) of the frames `frame_ids` (an index tensor) x every camera of cam_idxs at full resolution and the
+        current parameters, through the path a step's operator render takes: render_from_clip with cfg.enable_mip, or render_vertex
+        under vertex shading.  glctx: a context with output_db when cfg.enable_mip."""
+        cfg = self.cfg
+        H, W = self.full_resolution
+        verts = self.vertices(frame_ids, validate=False).reshape(int(frame_ids.shape[0]), -1, 3)
+        pos_clip = transform_clip_batched(self.mvp(frame_ids, validate=False), verts)
+        if cfg.shading == 'vertex':
+            return self.render_vertex(glctx, pos_clip, (H, W))
+        return render_from_clip(glctx, pos_clip, self.pos_idx, self.uv, self.uv_idx, self.tex_opt, (H, W), bool(cfg.enable_mip),
+                                cfg.max_mip_level, cfg.fused_render)
+
+    def exposure_range(self):
+        """(lo, hi, keep_from) of the Exposure rule for this Fitter: captures at or above cfg.saturation (> 0) mean "saturated", stay that
+        byte and count nothing; 0 and 255 (clipped black, clipped white) count nothing either."""
+        keep_from = int(self.cfg.saturation) if self.cfg.saturation > 0 else 256
+        return 1, min(keep_from, 255) - 1, keep_from
+
+    @torch.no_grad()
+    def equalise_exposure(self, frame_ids=None, method=None, anchor_camera=None, max_gain=None, reduce=None, chunk=4, apply=True):
+        """Fit every camera's gain and offset against the fit's OWN render at the current parameters and map this rank's captures onto one
+        common level, in place ("Exposure rule"): the step a take with unequal cameras needs before the plain pixel term --
+        one-pass objective, weighted one-pass, pyramid, hip_graph -- can fit it.  Call it once the geometry is roughly right (after the
+        norm_sigma or landmark iterations), once or twice per fit: every application rounds again.
+
+          frame_ids      frames of this rank's shard whose renders are compared (None: all of them), a sequence or an integer tensor
+          method         'regression' | 'moments' (None: cfg.equalise_method)
+          anchor_camera  a value of cam_idxs whose captures stay as they are (None: cfg.equalise_anchor_camera; without either the
+                         common level is the mean over the usable cameras)
+          max_gain       None: cfg.equalise_max_gain
+          reduce         reduce(sums) -> sums adds the int64 [Nc,6] table over the ranks (bake_texture's convention); None: one
+                         all_reduce(SUM) when world > 1 and torch.distributed is initialised.  Integer sums: every rank fits the same
+                         tables, whatever the sharding
+          chunk          frames rendered at a time
+          apply          False: fit and report only; the captures, the composite table and the captured graphs stay as they are
+
+        With the Scene's masks (use_masks), cfg.face_weights and the range of exposure_range().  ALL of this rank's full_targets are mapped,
+        then everything derived from them is made again in place -- every pyramid level's targets (from the full-size ones) and
+        target_bg_sumsq, the float copy of the torch loss, the cached sums; tensors a captured graph reads keep their addresses.  Targets
+        handed in through targets= are cloned first (once), which discards a captured graph.  Returns exposure.fit_gains' dict plus
+        'composite': the uint8 [Nc,256] table of everything applied to this rank's captures so far."""
+        cfg, dev = self.cfg, self.device
+        H, W = self.full_resolution
+        Nc = len(self.cam_idxs)
+        method = cfg.equalise_method if method is None else method
+        max_gain = cfg.equalise_max_gain if max_gain is None else max_gain
+        anchor_camera = cfg.equalise_anchor_camera if anchor_camera is None else anchor_camera
+        anchor = None
+        if anchor_camera is not None:
+            if isinstance(anchor_camera, bool) or anchor_camera not in self.cam_idxs:
+                raise ValueError(f"Fitter.equalise_exposure: anchor_camera must be one of cam_idxs {tuple(self.cam_idxs)} (got {anchor_camera!r})")
+            anchor = self.cam_idxs.index(anchor_camera)
+        if frame_ids is None:
+            frames = torch.arange(self.frame_lo, self.frame_hi, device=dev)
+        else:
+            frames = torch.as_tensor(frame_ids).to(dev).reshape(-1)
+        self.check_indices(frames)
+        frames = frames.long()
+        lo, hi, keep_from = self.exposure_range()
+        glctx = dr.RasterizeGLContext(output_db=bool(cfg.enable_mip), device=dev)
+        targets = self.full_targets.reshape(-1, H, W)
+        masks = self.full_masks.reshape(-1, H, W) if self.full_masks is not None else None
+        table = torch.zeros(Nc, 6, dtype=torch.int64, device=dev)
+        for c0 in range(0, int(frames.shape[0]), max(1, int(chunk))):
+            ids = frames[c0:c0 + max(1, int(chunk))].contiguous()
+            colour, rast = self.render_full(glctx, ids)
+            rows = self._target_rows(ids)
+            sums = dr.exposure_sums(colour.contiguous(), rast, targets.index_select(0, rows), mask=None if masks is None else masks.index_select(0, rows),
+                                    face_weights=self.face_w, lo=lo, hi=hi)
+            table += sums.reshape(int(ids.shape[0]), Nc, 6).sum(0)
+        if reduce is not None:
+            table = reduce(table)
+        elif self.world > 1:
+            import torch.distributed as tdist
+            if tdist.is_available() and tdist.is_initialized():
+                tdist.all_reduce(table, op=tdist.ReduceOp.SUM)
+        out = fit_gains(table, method=method, anchor=anchor, max_gain=max_gain, keep_from=keep_from)
+        if apply:
+            self._apply_exposure(out['lut'])
+            self._exposure_fit = out
+        out['composite'] = identity_lut(Nc) if self._exposure_total is None else self._exposure_total.copy()
+        return out
+
+    @torch.no_grad()
+    def _apply_exposure(self, lut):
+        """Map this rank's full_targets through lut uint8 [Nc,256] in place, fold it into the composite table, and make everything
+        derived from the targets again, in place (equalise_exposure).  An identity table changes nothing and launches nothing."""
+        if is_identity(lut):
+            return
+        H, W = self.full_resolution
+        Nc = len(self.cam_idxs)
+        if not self._targets_own:      # the caller's tensor: cloned once; a captured graph reads the old one
+            own = self.full_targets.clone()
+            if self.targets is self.full_targets:
+                self.targets = own
+            if self._levels is not None:
+                self._levels[1] = (own,) + tuple(self._levels[1][1:])
+            self.full_targets, self._targets_own = own, True
+            self._graphs, self._graph_key = None, None
+        full = self.full_targets
+        n_img = full.numel() // (H * W)
+        cams = (torch.arange(n_img, device=self.device) % Nc).to(torch.int32)
+        dr.apply_lut_u8(full.reshape(n_img, H * W), torch.from_numpy(np.ascontiguousarray(lut)).to(self.device), cams)
+        bg = lambda t, res: dr.reference_background_sumsq(t.reshape(-1, *res), BACKGROUND).reshape(t.shape[:2])
+        if self._levels is None:
+            self.target_bg_sumsq.copy_(bg(full, (H, W)))
+        else:      # every level from the full-size captures, never a cascade
+            for s, (lt, lres, lbg, _) in self._levels.items():
+                if s > 1:
+                    lt.copy_(dr.downsample_images(full, s))
+                lbg.copy_(bg(lt, lres))
+        if self._targets_f32 is not None:
+            self._targets_f32.copy_(self.targets.to(torch.float32))
+        self._bg_wsum = {}
+        for name in list(self._shard_sums):      # the cached sums over the shard: a captured graph reads the plain term's
+            key, val = self._shard_sums[name]
+            if name == 'bg_sumsq':
+                val.copy_(self.target_bg_sumsq.reshape(-1)[key[1]:key[2]].sum(0))
+            else:
+                del self._shard_sums[name]
+        total = identity_lut(Nc) if self._exposure_total is None else self._exposure_total
+        total = compose(total, lut)
+        self._exposure_total = None if is_identity(total) else total
+
     @torch.no_grad()
     def render_targets(self, chunk=4):
         """Synthetic reference images: the hidden ground truth (weights, pose, texture) rendered through the
@@ -1810,6 +1955,8 @@ class Fitter:
     def step(self):
         """One Adam step (fit.py:524-618): forward, backward, gradient all-reduce, update, schedule, renormalise."""
         prepared = False
+        if self._equalise_at and self.iteration in self._equalise_at:
+            self.equalise_exposure()
         if self._levels is not None:
             self._set_level(self.pyramid_factor())
         self._mode_switch()      # (before the optimiser's table of this step is written: a parameter that turns trainable now counts this step)
@@ -1948,7 +2095,10 @@ class Fitter:
         """Everything a resumed run needs to continue bit-identically (the reference has no checkpointing, SURVEY.md
         section 5): parameters, Adam moments, schedule position, iteration, minibatch RNG and the result buffer."""
         names = ("m1", "m2", "m3", "maps_local", "maps_intermediate_local", "t_opt", "q_opt", "per_frame_t", "per_frame_q", "tex_opt")
-        return {"params": {n: p.detach().clone() for n, p in zip(names, self.params)},
+        # (the composite exposure table, present only when this rank's captures have been mapped: today's key sets stay as they are)
+        exposure = {} if self._exposure_total is None else {"exposure_lut": torch.from_numpy(self._exposure_total.copy())}
+        return {**exposure,
+                "params": {n: p.detach().clone() for n, p in zip(names, self.params)},
                 "requires_grad": [bool(p.requires_grad) for p in self.params],
                 "optimizer": self.optimizer.state_dict(), "scheduler": self.scheduler.state_dict(),
                 "iteration": self.iteration, "rng": self.rng.bit_generator.state,
@@ -1986,6 +2136,18 @@ class Fitter:
         self.result.copy_(state["result"].to(self.result.device))
         if self._tex_anchor is not None and state.get("tex_anchor") is not None:      # (without the key the anchor stays as constructed)
             self.set_texture_anchor(state["tex_anchor"], state.get("tex_anchor_weights"))
+        if state.get("exposure_lut") is not None:      # the checkpoint's captures were mapped: map these the same way, once
+            lut = np.ascontiguousarray(torch.as_tensor(state["exposure_lut"]).cpu().numpy())
+            if lut.dtype != np.uint8 or lut.shape != (len(self.cam_idxs), 256):
+                raise ValueError(f"load_state_dict: exposure_lut must be uint8 [{len(self.cam_idxs)},256] (got {lut.dtype} {lut.shape})")
+            if self._exposure_total is None:
+                self._apply_exposure(lut)
+            elif not np.array_equal(self._exposure_total, lut):
+                raise ValueError("load_state_dict: the checkpoint's exposure table differs from the one already applied to this Fitter's "
+                                 "captures; load it into a Fitter whose captures are as read")
+        elif self._exposure_total is not None:      # (a checkpoint without the key: its captures were as read, these are mapped)
+            raise ValueError("load_state_dict: the checkpoint carries no exposure table, but this Fitter's captures have been mapped; load "
+                             "it into a Fitter whose captures are as read")
         self._graphs, self._graph_key = None, None
         if self._levels is not None:
             self._set_level(self.pyramid_factor())
@@ -2064,6 +2226,28 @@ class Fitter:
             return
         write_result(directory, result.cpu().numpy(), self.uv.cpu().numpy(), face_lines(self.sc.pos_idx, self.sc.uv_idx),
                      self.tex_opt.detach().cpu().numpy(), self.per_frame_t.detach().cpu().tolist(), self.per_frame_q.detach().cpu().tolist())
+        if self._exposure_total is not None:      # (only then: the files of a fit that never equalised stay byte for byte what they were)
+            self.save_exposure(directory)
+
+    def save_exposure(self, directory):
+        """<directory>/exposure.json: per camera name the composite table 'lut' (256 bytes: capture byte -> the byte the fit saw) and, of the
+        last equalise_exposure call, 'gain' = g, 'offset' = b_common - g b (new byte ~ gain * byte + offset) and 'rho'; null where this
+        Fitter made no fit of its own (a table loaded from a checkpoint) or the camera was not usable."""
+        total = identity_lut(len(self.cam_idxs)) if self._exposure_total is None else self._exposure_total
+        fitted = self._exposure_fit
+        num = lambda v: float(v) if np.isfinite(v) else None
+        rec = {}
+        for j, c in enumerate(self.cam_idxs):
+            gain = offset = rho = None
+            if fitted is not None:
+                rho = num(fitted['rho'][j])
+                if fitted['usable'][j]:
+                    gain = num(fitted['g'][j])
+                    offset = num(fitted['b_common'] - fitted['g'][j] * fitted['b'][j])
+            rec[str(self.sc.cams[c].get('cam', c))] = {'gain': gain, 'offset': offset, 'rho': rho, 'lut': [int(v) for v in total[j]]}
+        os.makedirs(directory, exist_ok=True)
+        with open(os.path.join(directory, "exposure.json"), "w", encoding="utf-8") as f:
+            json.dump(rec, f, sort_keys=True, indent=1)
 
 
 def face_lines(pos_idx, uv_idx):

@@ -31,7 +31,8 @@ from . import _lib
 
 __all__ = ['RasterizeGLContext', 'RasterizeCudaContext', 'RasterizeHipContext', 'rasterize', 'interpolate', 'texture',
            'texture_construct_mip', 'antialias', 'antialias_construct_topology_hash', 'render_textured', 'pixel_objective', 'undistort_images', 'compare_images',
-           'gaussian_taps', 'blurred_pixel_loss', 'normalised_pixel_loss', 'robust_pixel_loss', 'bake_accumulate', 'bake_resolve', 'downsample_images']
+           'gaussian_taps', 'blurred_pixel_loss', 'normalised_pixel_loss', 'robust_pixel_loss', 'bake_accumulate', 'bake_resolve', 'downsample_images',
+           'exposure_sums', 'apply_lut_u8']
 
 
 def _stream():
@@ -1280,6 +1281,101 @@ def downsample_images(images, factor):
     with torch.cuda.device(images.device):
         _lib.call("fpcdr_downsample_u8", _ptr(images), _ptr(out), images.numel() // (H * W), H, W, factor, _stream())
     return out
+
+
+def exposure_sums(colour, rast, ref_u8, sums=None, mask=None, face_weights=None, lo=1, hi=254):
+    """The integer moments of render byte against capture byte over the interior covered pixels of every image, by the rule of DESIGN.md
+    3 "Exposure rule" (fpcdr_exposure_sums): what exposure.fit_gains fits a camera's gain and offset from.
+
+      colour        float32 GPU tensor [N,H,W,C], C in 1..4: the render, r = its byte at scale 255 (the Comparison rule's quantisation)
+      rast          float32 [N,H,W,4], only .w is read (> 0: covered; the triangle id + 1 for face_weights)
+      ref_u8        uint8 [N,H,W], t; row i belongs to raster row i
+      sums          int64 [N,6] = (n, sum r, sum t, sum r^2, sum t^2, sum r t) per image, ADDED to; None: a new table of zeros
+      mask          uint8 [N,H,W] or None: a pixel counts only where its byte is >= 128
+      face_weights  float32 [T] or None: a pixel counts only where its triangle's weight is > 0 (an id past the table does not count)
+      lo, hi        0 <= lo <= hi <= 255: a pixel counts only where lo <= t <= hi
+
+    A pixel with an uncovered neighbour (up, down, left, right) inside the image does not count: silhouette pixels hold blended
+    background.  All contiguous, on one device.  Integer sums: the result does not depend on the order of the calls or on how the images
+    are shared out over calls and ranks.  Returns sums."""
+    tensors = [('colour', colour, torch.float32), ('rast', rast, torch.float32), ('ref_u8', ref_u8, torch.uint8)]
+    if sums is not None:
+        tensors.append(('sums', sums, torch.int64))
+    if mask is not None:
+        tensors.append(('mask', mask, torch.uint8))
+    if face_weights is not None:
+        tensors.append(('face_weights', face_weights, torch.float32))
+    for name, t, _ in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    for name, t, dtype in tensors:
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a GPU tensor (got {t.device}); the exposure sums have no CPU path")
+        if t.device != colour.device:
+            raise ValueError(f"colour and {name} are on different devices ({colour.device}, {t.device})")
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must be {dtype} (got {t.dtype})")
+    for name, v in (('lo', lo), ('hi', hi)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer (got {v!r})")
+    if not 0 <= lo <= hi <= 255:
+        raise ValueError(f"0 <= lo <= hi <= 255 is required (got lo = {lo}, hi = {hi})")
+    if colour.dim() != 4 or not 1 <= colour.shape[3] <= 4:
+        raise ValueError(f"colour must be [N,H,W,C] with C in 1..4 (got shape {tuple(colour.shape)})")
+    N, H, W, C = colour.shape
+    if tuple(rast.shape) != (N, H, W, 4):
+        raise ValueError(f"rast must be {(N, H, W, 4)} (got {tuple(rast.shape)})")
+    if tuple(ref_u8.shape) != (N, H, W):
+        raise ValueError(f"ref_u8 must be {(N, H, W)} (got {tuple(ref_u8.shape)})")
+    if mask is not None and tuple(mask.shape) != (N, H, W):
+        raise ValueError(f"mask must be {(N, H, W)} (got {tuple(mask.shape)})")
+    if face_weights is not None and (face_weights.dim() != 1 or face_weights.numel() == 0):
+        raise ValueError(f"face_weights must be [T] and not empty (got shape {tuple(face_weights.shape)})")
+    if colour.numel() == 0:
+        raise ValueError("empty input")
+    if sums is None:
+        sums = torch.zeros(N, 6, dtype=torch.int64, device=colour.device)
+    elif tuple(sums.shape) != (N, 6):
+        raise ValueError(f"sums must be {(N, 6)} (got {tuple(sums.shape)})")
+    if not all(t.is_contiguous() for _, t, _ in tensors) or not sums.is_contiguous():
+        raise ValueError("colour, rast, ref_u8, sums, mask and face_weights must be contiguous")
+    with torch.cuda.device(colour.device):
+        _lib.call("fpcdr_exposure_sums", _ptr(colour), _ptr(rast), _ptr(ref_u8), _ptr(mask), _ptr(face_weights),
+                  0 if face_weights is None else int(face_weights.numel()), int(lo), int(hi), N, H, W, C, _ptr(sums), _stream())
+    return sums
+
+
+def apply_lut_u8(images, lut, cam_of_image):
+    """images[b] <- lut[cam_of_image[b]][images[b]], IN PLACE (DESIGN.md 3 "Exposure rule": fpcdr_apply_lut_u8): a camera's 256-entry
+    table applied to each of its 8-bit images, e.g. exposure.fit_gains' or a Fitter's composite table on captures read anew.
+
+      images        uint8 GPU tensor [B, ...], contiguous (every trailing dimension is one image's bytes)
+      lut           uint8 [Nl,256], contiguous, same device
+      cam_of_image  int32 [B], same device: the table of each image
+
+    An entry of cam_of_image outside [0, Nl) raises RuntimeError after the other images have been mapped; that image is left as it is.
+    The call reads cam_of_image back first, so it waits for the stream and cannot be captured into a graph.  Returns images."""
+    for name, t, dtype in (('images', images, torch.uint8), ('lut', lut, torch.uint8), ('cam_of_image', cam_of_image, torch.int32)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a GPU tensor (got {t.device}); apply_lut_u8 has no CPU path")
+        if t.device != images.device:
+            raise ValueError(f"images and {name} are on different devices ({images.device}, {t.device})")
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must be {dtype} (got {t.dtype})")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous (the images are written in place)")
+    if images.dim() < 2 or images.numel() == 0:
+        raise ValueError(f"images must be [B, ...] and not empty (got shape {tuple(images.shape)})")
+    if lut.dim() != 2 or lut.shape[1] != 256 or lut.shape[0] == 0:
+        raise ValueError(f"lut must be [Nl,256] (got shape {tuple(lut.shape)})")
+    B = int(images.shape[0])
+    if tuple(cam_of_image.shape) != (B,):
+        raise ValueError(f"cam_of_image must be {(B,)} (got {tuple(cam_of_image.shape)})")
+    with torch.cuda.device(images.device):
+        _lib.call("fpcdr_apply_lut_u8", _ptr(images), _ptr(lut), _ptr(cam_of_image), int(lut.shape[0]), B, images.numel() // B, _stream())
+    return images
 
 
 def pixel_objective(glctx, pos, tri, uv, uv_tri, tex, ref_u8, resolution, n_total=None, background=45.0 / 255.0,

@@ -762,6 +762,36 @@ int fpcdr_bake_dilate(const float *tex_in, const uint8_t *filled_in, float *tex_
  * overlap.  n_images == 0 is success without a launch.  src and dst may sit at any address (wider accesses are used where it allows). */
 int fpcdr_downsample_u8(const uint8_t *src, uint8_t *dst, int64_t n_images, int H, int W, int s, void *stream);
 
+/* Per-camera exposure from the fit's own render: the integer moments the gains are fitted from, and the 256-entry tables applied to the
+ * captures in place.  Pure additions: FPCDR_ABI_VERSION stays 16, no existing entry or struct changes.  DESIGN.md 3, "Exposure rule".
+ *
+ * fpcdr_exposure_sums:
+ *   colour [n_images, H, W, C] float32, C in 1..4;  rast [n_images, H, W, 4] float32, only .w is read;  ref [n_images, H, W] uint8
+ *   mask   [n_images, H, W] uint8 or NULL;  face_w [T] float32 or NULL (then T is not read)
+ *   sums   [n_images, 6] signed 64-bit (n, sum r, sum t, sum r^2, sum t^2, sum r t) per image, ACCUMULATED: the caller zero-fills it
+ * For the pixel at row i, column j of image n (target row i is raster row i: nothing is flipped):
+ *   cov(i, j) = rast[n, i, j, 3] > 0  (a NaN is not covered);  t = ref[n, i, j]
+ *   the pixel counts iff cov(i, j), cov holds at each of (i +- 1, j), (i, j +- 1) that lies inside the image (fpcdr_bake_accumulate_u8's
+ *   interior_only), mask[n, i, j] >= 128 (with a mask), face_w[id - 1] > 0 for id = (int)rast[n, i, j, 3] (with face weights; an id
+ *   outside 1..T does not count and reads nothing), and lo <= t <= hi
+ *   for every channel k of a pixel that counts:  r = the Comparison rule's byte of colour[n, i, j, k] * 255 (float32 product, NaN -> 0,
+ *   round half to even, clip to 0..255);  sums[n] += (1, r, t, r r, t t, r t)
+ * Integer atomics, one per sum and workgroup: the sums do not depend on the order of the adds, of the calls or of the images.
+ * Errors, before any launch: a NULL colour / rast / ref / sums, sizes <= 0, C outside 1..4, lo / hi outside 0 <= lo <= hi <= 255, face_w
+ * with T <= 0, sums not 8-byte aligned or overlapping an input.  colour, rast and face_w may sit at any 4-byte aligned address, ref and
+ * mask at any address (wider accesses are used where the addresses allow).
+ *
+ * fpcdr_apply_lut_u8:  images[b, p] = lut[cam_of_image[b], images[b, p]] for 0 <= p < HW, in place
+ *   images [n_images, HW] uint8;  lut [Nl, 256] uint8;  cam_of_image [n_images] int32 -- all DEVICE memory
+ *   An image whose cam_of_image lies outside [0, Nl) is left as it is and every other image is mapped; the entry then returns
+ *   FPCDR_EINVAL (it reads cam_of_image back first, so it waits for the stream and cannot be captured into a graph).
+ * Errors, before any launch: a NULL pointer, HW or Nl <= 0, n_images < 0, images overlapping lut or cam_of_image.  n_images == 0 is
+ * success without a launch.  images and lut may sit at any address. */
+int fpcdr_exposure_sums(const float *colour, const float *rast, const uint8_t *ref, const uint8_t *mask, const float *face_w, int T,
+                        int lo, int hi, int64_t n_images, int H, int W, int C, int64_t *sums, void *stream);
+int fpcdr_apply_lut_u8(uint8_t *images, const uint8_t *lut, const int32_t *cam_of_image, int Nl, int64_t n_images, int64_t HW,
+                       void *stream);
+
 /* Locally normalised pixel loss: a pixel term that does not see a camera's exposure, gain or black level (the reference carries
  * whiten / normalize_highlights in utils.py and builds torch.nn.LocalResponseNorm(2) at src/torch/fit.py:510, but wires none of it
  * into its loss).  A pure addition: FPCDR_ABI_VERSION stays 16.  DESIGN.md 3, "Normalised loss rule"; taps, reflected borders and
