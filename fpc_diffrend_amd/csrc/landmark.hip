@@ -5,19 +5,19 @@
 //   k_landmark_gather   one lane per (frame, vertex) over ALL vertices: the vertex's landmark corners summed over the frame's images in a
 //                       fixed order -- no float atomics; a vertex without a landmark writes 0, so the kernel is also the fill of grad_x
 //   k_penalty_finish<false> with divisor Nc L (penalty_finish.h): per_f, the value, the accumulators zeroed again
+#include "landmark_entry.h"
 #include "penalty_finish.h"
 
 #include <cmath>
 
 namespace {
 
-// lm_vtx [3,L] int32 and lm_bary [3,L] float32, corner-major: landmark l is the point sum_k lm_bary[k][l] x[lm_vtx[k][l]]; lm_w [L] or
-// null: 1.  obs [F Nc,L,3] = (u*, v*, kappa) in raster pixels of the W x H capture.  An entry is live when kappa > 0, omega > 0 and
-// p.w > 1e-6; what is not live is switched off by SELECTS, not by a product with 0, so that a NaN in an observation nobody made, or the
-// quotient of a point behind the camera, stays where it is.  coef = weight / (F Nc L).  g_q (may be null: value only) [F Nc,L,3];
-// g_mvp (null with it) [F Nc,4,4]: the twelve entries of the rows x, y, w summed over the workgroup -- DPP within a wave, the four waves'
-// partials through LDS in wave order -- and stored whole, row z as 0.  res_out (may be null) [F Nc,L,2] = (u - u*, v - v*), NaN where
-// the entry is not live.  Constant indices only: no private segment.
+// The tables lm_vtx, lm_bary, lm_w and an entry's read and residual: landmark_entry.h.  obs [F Nc,L,3] = (u*, v*, kappa) in raster pixels of
+// the W x H capture.  An entry is live when kappa > 0, omega > 0 and p.w > 1e-6; what is not live is switched off by SELECTS, so that a NaN in
+// an observation nobody made, or the quotient of a point behind the camera, stays where it is.  coef = weight / (F Nc L).  g_q (may be
+// null: value only) [F Nc,L,3]; g_mvp (null with it) [F Nc,4,4]: the twelve entries of the rows x, y, w summed over the workgroup -- DPP
+// within a wave, the four waves' partials through LDS in wave order -- and stored whole, row z as 0.  res_out (may be null) [F Nc,L,2] =
+// (u - u*, v - v*), NaN where the entry is not live.  Constant indices only: no private segment.
 __global__ void __launch_bounds__(256) k_landmark_points(const float *__restrict__ x, const float *__restrict__ mvp,
                                                          const int32_t *__restrict__ lm_vtx, const float *__restrict__ lm_bary,
                                                          const float *__restrict__ lm_w, const float *__restrict__ obs, float ic, float half_w,
@@ -36,36 +36,22 @@ __global__ void __launch_bounds__(256) k_landmark_points(const float *__restrict
 #pragma unroll
     for (int i = 0; i < 12; ++i) gm[i] = 0.0f;
     for (int l = threadIdx.x; l < L; l += blockDim.x) {
-        const int i0 = lm_vtx[l], i1 = lm_vtx[(size_t)L + l], i2 = lm_vtx[2 * (size_t)L + l];
-        const float b0 = lm_bary[l], b1 = lm_bary[(size_t)L + l], b2 = lm_bary[2 * (size_t)L + l];
-        const float omega = lm_w ? lm_w[l] : 1.0f;
-        const float *o = obs + ((size_t)n * L + l) * 3;
-        const float us = o[0], vs = o[1], kappa = o[2];
-        float q[4];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) q[i] = (b0 * xf[3 * (size_t)i0 + i] + b1 * xf[3 * (size_t)i1 + i]) + b2 * xf[3 * (size_t)i2 + i];
-        q[3] = 1.0f;
+        float p[3];
+        LandmarkEntry e;
+        landmark_entry(xf, lm_vtx, lm_bary, lm_w, obs + ((size_t)n * L + l) * 3, L, l, p, e);
+        const float q[4] = {p[0], p[1], p[2], 1.0f};
         const float px = ((mx[0] * q[0] + mx[1] * q[1]) + mx[2] * q[2]) + mx[3];
         const float py = ((my[0] * q[0] + my[1] * q[1]) + my[2] * q[2]) + my[3];
         const float pw = ((mw[0] * q[0] + mw[1] * q[1]) + mw[2] * q[2]) + mw[3];
-        const bool live = kappa > 0.0f && omega > 0.0f && pw > 1e-6f;
-        const float sw = live ? pw : 1.0f;
-        const float ru = ((px / sw * 0.5f + 0.5f) * (2.0f * half_w) - 0.5f) - us;
-        const float rv = ((py / sw * 0.5f + 0.5f) * (2.0f * half_h) - 0.5f) - vs;
-        const float s = ru * ru + rv * rv;
-        float rho = s, d = 1.0f;
-        if (ic > 0.0f) {      // the Charbonnier form without the cancellation, as the motion term has it
-            const float zu = ru * ic, zv = rv * ic;
-            const float h = sqrtf(1.0f + (zu * zu + zv * zv));
-            rho = (2.0f * s) / (1.0f + h);
-            d = 1.0f / h;
-        }
-        const float wk = omega * kappa;
-        if (live) value += wk * rho;
+        LandmarkResidual r;
+        landmark_residual(px, py, pw, e, half_w, half_h, ic, r);
+        const bool live = r.live;
+        const float sw = r.sw, ru = r.ru, rv = r.rv, d = r.d, wk = e.wk;
+        if (live) value += wk * r.rho;
         if (res_out) {
-            float *r = res_out + ((size_t)n * L + l) * 2;
-            r[0] = live ? ru : __builtin_nanf("");
-            r[1] = live ? rv : __builtin_nanf("");
+            float *ro = res_out + ((size_t)n * L + l) * 2;
+            ro[0] = live ? ru : __builtin_nanf("");
+            ro[1] = live ? rv : __builtin_nanf("");
         }
         if (g_q) {
             const float k2 = (coef * wk) * (d * 2.0f);

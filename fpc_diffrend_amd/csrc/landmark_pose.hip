@@ -6,7 +6,7 @@
 //                     a trial's evaluation is also the next trial's linearisation, so a trial is one pass.  Lane 0 solves the damped 6 x 6
 //                     system in float64 (Cholesky, unrolled, constant indices: no private segment), publishes the trial pose through LDS
 //                     and keeps or rejects it.  No float atomics, a fixed order: bit-identical from run to run.
-#include "common.h"
+#include "landmark_entry.h"
 
 #include <cmath>
 
@@ -14,7 +14,7 @@ namespace {
 
 constexpr int POSE_N = 29;      // A (21, upper triangle, row-major), b (6), E, the number of live entries
 
-// the partial sums of one pass at the pose s_pose = (q [4] as stored, t [3]) -> s_new[POSE_N]; ends behind a barrier
+// the partial sums of one pass at the pose s_pose = (q [4] as stored, t [3]) -> s_new[POSE_N]; ends behind a barrier (an entry: landmark_entry.h)
 __device__ __forceinline__ void pose_pass(const float *__restrict__ xf, const float *__restrict__ proj, const float *__restrict__ base,
                                           const int32_t *__restrict__ lm_vtx, const float *__restrict__ lm_bary,
                                           const float *__restrict__ lm_w, const float *__restrict__ obs_f, float ic, float half_w, float half_h,
@@ -37,15 +37,10 @@ __device__ __forceinline__ void pose_pass(const float *__restrict__ xf, const fl
     const int n = Nc * L;
     for (int e = threadIdx.x; e < n; e += 256) {
         const int c = e / L, l = e - c * L;
-        const int i0 = lm_vtx[l], i1 = lm_vtx[(size_t)L + l], i2 = lm_vtx[2 * (size_t)L + l];
-        const float b0 = lm_bary[l], b1 = lm_bary[(size_t)L + l], b2 = lm_bary[2 * (size_t)L + l];
-        const float omega = lm_w ? lm_w[l] : 1.0f;
-        const float *o = obs_f + (size_t)e * 3;
-        const float us = o[0], vs = o[1], kappa = o[2];
         const float *B = base + (size_t)c * 16, *P = proj + (size_t)c * 16;
         float p[3], yb[3], a[3], zz[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) p[i] = (b0 * xf[3 * (size_t)i0 + i] + b1 * xf[3 * (size_t)i1 + i]) + b2 * xf[3 * (size_t)i2 + i];
+        LandmarkEntry en;
+        landmark_entry(xf, lm_vtx, lm_bary, lm_w, obs_f + (size_t)e * 3, L, l, p, en);
 #pragma unroll
         for (int i = 0; i < 3; ++i) yb[i] = ((B[4 * i] * p[0] + B[4 * i + 1] * p[1]) + B[4 * i + 2] * p[2]) + B[4 * i + 3];
         a[0] = (r00 * yb[0] + r01 * yb[1]) + r02 * yb[2];
@@ -55,21 +50,11 @@ __device__ __forceinline__ void pose_pass(const float *__restrict__ xf, const fl
         const float px = ((P[0] * zz[0] + P[1] * zz[1]) + P[2] * zz[2]) + P[3];
         const float py = ((P[4] * zz[0] + P[5] * zz[1]) + P[6] * zz[2]) + P[7];
         const float pw = ((P[12] * zz[0] + P[13] * zz[1]) + P[14] * zz[2]) + P[15];
-        const bool live = kappa > 0.0f && omega > 0.0f && pw > 1e-6f;
-        const float sw = live ? pw : 1.0f;
-        const float nx = px / sw, ny = py / sw;
-        const float ru = ((nx * 0.5f + 0.5f) * (2.0f * half_w) - 0.5f) - us;
-        const float rv = ((ny * 0.5f + 0.5f) * (2.0f * half_h) - 0.5f) - vs;
-        const float s = ru * ru + rv * rv;
-        float rho = s, d = 1.0f;
-        if (ic > 0.0f) {      // the Charbonnier form without the cancellation, as the landmark term has it
-            const float zu = ru * ic, zv = rv * ic;
-            const float h = sqrtf(1.0f + (zu * zu + zv * zv));
-            rho = (2.0f * s) / (1.0f + h);
-            d = 1.0f / h;
-        }
-        const float wk = omega * kappa;
-        const float wd = wk * d;
+        LandmarkResidual r;
+        landmark_residual(px, py, pw, en, half_w, half_h, ic, r);
+        const bool live = r.live;
+        const float sw = r.sw, nx = r.nx, ny = r.ny, ru = r.ru, rv = r.rv, wk = en.wk;
+        const float wd = wk * r.d;
         const float ku = half_w / sw, kv = half_h / sw;
         float ju[6], jv[6];      // the residual's Jacobian: (a x g, g)
 #pragma unroll
@@ -92,7 +77,7 @@ __device__ __forceinline__ void pose_pass(const float *__restrict__ xf, const fl
             const float term = wd * (ju[i] * ru + jv[i] * rv);
             acc[21 + i] += live ? term : 0.0f;
         }
-        const float term = wk * rho;
+        const float term = wk * r.rho;
         acc[27] += live ? term : 0.0f;
         acc[28] += live ? 1.0f : 0.0f;
     }

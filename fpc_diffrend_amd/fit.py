@@ -857,6 +857,30 @@ def setup_dataset_free(n_frames, n_vertices_x3, device):
     return m1, m2, m3, torch.zeros(n_frames, dtype=torch.float32, device=device)
 
 
+def shard_indices(ft, frame_ids, view_ids=None):
+    """The frames (and views) of a pass over Fitter ft's shard as checked int64 index tensors on its device: frame_ids None: all of this
+    rank's frames, else a sequence or an integer tensor of any shape, flattened; view_ids: positions in cam_idxs, the same, None stays
+    None.  IndexError as Fitter.check_indices raises it.  -> (frames, views)."""
+    dev = ft.device
+    frames = torch.arange(ft.frame_lo, ft.frame_hi, device=dev) if frame_ids is None else torch.as_tensor(frame_ids).to(dev).reshape(-1)
+    views = None if view_ids is None else torch.as_tensor(view_ids).to(dev).reshape(-1)
+    ft.check_indices(frames, views)
+    return frames.long(), None if views is None else views.long()
+
+
+def sum_over_ranks(t, world, reduce=None):
+    """The convention of every pass that sums a table over the shards (bake_texture, equalise_exposure, align_to_landmarks): reduce(t) -> t
+    sums the tensor over the ranks where the caller gives one; None: one all_reduce(SUM), in place, when world > 1 and torch.distributed
+    is available and initialised, else t as it is.  Every rank then goes on from the same table, whatever the sharding."""
+    if reduce is not None:
+        return reduce(t)
+    if world > 1:
+        import torch.distributed as tdist
+        if tdist.is_available() and tdist.is_initialized():
+            tdist.all_reduce(t, op=tdist.ReduceOp.SUM)
+    return t
+
+
 class Fitter:
     """State + one optimisation step of the fit loop for a take: a synthetic Scene (scene.cfg: targets are rendered from
     its hidden ground truth) or one read from disk (scene.from_take: targets are its reference images).
@@ -1034,8 +1058,8 @@ class Fitter:
                 lres = (self.resolution[0] // s, self.resolution[1] // s)
                 lm = dr.downsample_images(self.full_masks, s) if self.full_masks is not None else None
                 self._levels[s] = (lt, lres, dr.reference_background_sumsq(lt.reshape(-1, *lres), BACKGROUND).reshape(lt.shape[:2]), lm)
-        self._pose_tables = None     # (the landmark tables of align_to_landmarks where the landmark term has not built its own)
-        self._lmk = None
+        self._lmk, self._lmk_obs, self._lmk_res = None, None, None      # (_landmark_tables: built on first use, by the term or by align_to_landmarks)
+        self._lmk_on, self._lmk_scratch = False, None      # (the landmark TERM's own: _build_landmarks)
         if cfg.init_pose == 'landmarks':      # (in front of the bake, which reads the pose)
             self.align_to_landmarks(iters=cfg.init_pose_iters, rotation=cfg.init_pose_rotation)
         baked = None
@@ -1091,26 +1115,23 @@ class Fitter:
                            for on, fn, inputs, weights, keys, step in table if on]
 
     def _build_landmarks(self):
-        """The landmark term's tables on the device ("Landmark rule"), or ValueError: the LandmarkSet, this rank's
-        observations [F_local * n_cam, L, 3] laid out as the targets are, and the scratch of the points' gradients for the most images a
-        step takes.  weight_landmark = 0 or use_landmarks = False: nothing is built.  The term is not one of _reg_terms: it reads the
-        matrices and the step's rows too, so loss_and_backward evaluates it itself (_landmark_term) and hands it over with them."""
+        """Switch the landmark term on ("Landmark rule"), or ValueError: the tables (_landmark_tables) and the scratch of the
+        points' gradients for the most images a step takes.  weight_landmark = 0 or use_landmarks = False: nothing is built.  The term is
+        not one of _reg_terms: it reads the matrices and the step's rows too, so loss_and_backward evaluates it itself (_landmark_term)
+        and hands it over with them."""
         cfg = self.cfg
-        self._lmk, self._lmk_obs, self._lmk_scratch = None, None, None
         if not cfg.weight_landmark or not cfg.use_landmarks:
             return
-        self._lmk, self._lmk_obs, self._lmk_res = self._landmark_tables("FitConfig.weight_landmark > 0")
-        self._lmk_scratch = torch.empty(self._lmk_obs.shape[0] * self._lmk.n * 3, dtype=torch.float32, device=self.device)
+        lms, obs, _ = self._landmark_tables("FitConfig.weight_landmark > 0")
+        self._lmk_on, self._lmk_scratch = True, torch.empty(obs.shape[0] * lms.n * 3, dtype=torch.float32, device=self.device)
 
     def _landmark_tables(self, who):
-        """(the LandmarkSet with the configured weights, this rank's observations [F_local * n_cam, L, 3], the observations' pixel grid) on
-        the device, or ValueError in the name of `who`: the landmark term's own if it has built them, else built on first use and kept
-        (Fitter.align_to_landmarks needs them without weight_landmark > 0)."""
+        """(the LandmarkSet with the configured weights, this rank's observations [F_local * n_cam, L, 3] laid out as the targets are, the
+        observations' pixel grid) on the device, or ValueError in the name of `who`: built on first use and kept, for the landmark term
+        and for Fitter.align_to_landmarks alike (which needs them without weight_landmark > 0)."""
         cfg, sc, dev = self.cfg, self.sc, self.device
         if self._lmk is not None:
             return self._lmk, self._lmk_obs, self._lmk_res
-        if getattr(self, "_pose_tables", None) is not None:
-            return self._pose_tables
         if sc.landmarks is None or not sc.landmark_points:
             raise ValueError(f"{who} needs a Scene with landmarks (Scene.landmark_points and Scene.landmarks; "
                              "scene.from_take(landmarkpath=...)), or use_landmarks=False")
@@ -1129,8 +1150,8 @@ class Fitter:
         # the pixel grid of the observations: the captures as read (a take fitted at a fixed reduced size keeps its landmarks' own grid:
         # the projection chain is pure NDC), which is full_resolution everywhere else
         res = tuple(sc.images.shape[2:]) if sc.images is not None else tuple(self.full_resolution)
-        self._pose_tables = (lms, torch.from_numpy(obs.reshape(-1, lms.n, 3)).to(dev), res)
-        return self._pose_tables
+        self._lmk, self._lmk_obs, self._lmk_res = lms, torch.from_numpy(obs.reshape(-1, lms.n, 3)).to(dev), res
+        return self._lmk, self._lmk_obs, self._lmk_res
 
     @torch.no_grad()
     def align_to_landmarks(self, frame_ids=None, iters=20, rotation=True, reduce=None):
@@ -1145,8 +1166,7 @@ class Fitter:
           rotation   False: the translation alone.  True on more than one frame needs quat_renorm='rows': the whole-tensor division
                      (quirk Q3) scales every row to 1 / sqrt(F), and rigid() applies q as it stands, R(q / sqrt(F)) = I + (R(q) - I) / F
           reduce     reduce(delta) -> delta sums the float32 [F,7] table of (q, t) changes, zero outside this rank's frames, over the ranks
-                     (bake_texture's convention); None: one all_reduce(SUM) when world > 1 and torch.distributed is initialised.  The
-                     replicated parameters stay identical on every rank
+                     (sum_over_ranks' convention).  The replicated parameters stay identical on every rank
 
         per_frame_q / per_frame_t are written in place (a captured graph replays with them); Adam's moments stay as they are: call it
         before the first step.  Returns {'before', 'after'}: the mean live |residual| in pixels over the solved frames, and 'info'
@@ -1161,12 +1181,7 @@ class Fitter:
                              "'tensor' every step divides per_frame_q by the norm of the WHOLE tensor, each row comes out at 1 / sqrt(F), "
                              "and the solved rotation is turned back to almost none (use rotation=False, or quat_renorm='rows')")
         lms, obs_all, res = self._landmark_tables("Fitter.align_to_landmarks")
-        if frame_ids is None:
-            frames = torch.arange(self.frame_lo, self.frame_hi, device=dev)
-        else:
-            frames = torch.as_tensor(frame_ids).to(dev).reshape(-1)
-        self.check_indices(frames)
-        frames = frames.long()
+        frames, _ = shard_indices(self, frame_ids)
         Fb, Nc = int(frames.shape[0]), len(self.cam_idxs)
         verts = self.vertices(frames, validate=False).reshape(Fb, -1, 3).contiguous()
         # base[c] = Rt(q_c, t_c) . MV_c . T(0,170,0), the float32 product k_mvp_fwd forms: its own launch with the frame at the identity and
@@ -1180,24 +1195,17 @@ class Fitter:
         obs = obs_all.index_select(0, self._target_rows(frames))
         q, t = self.per_frame_q.detach().index_select(0, frames).contiguous(), self.per_frame_t.detach().index_select(0, frames).contiguous()
         q0, t0 = q.clone(), t.clone()
-        kw = dict(scale=cfg.landmark_scale, rotation=bool(rotation))
 
-        def mean_residual():
-            rr = torch.empty(Fb * Nc, lms.n, 2, dtype=torch.float32, device=dev)
-            landmark_penalty(verts, self.mvp(frames, validate=False), lms, obs, 1.0, res, scale=cfg.landmark_scale, residuals=rr, validate=False)
+        def mean_residual():      # (over the solved frames, at the parameters as they stand)
+            rr = self.landmark_residuals(frames)
             live = ~torch.isnan(rr[..., 0])
             return float(rr[live].double().norm(dim=1).mean()) if bool(live.any()) else float('nan')
 
         before = mean_residual()
-        info = solve_pose(verts, self.proj, base, lms, obs, q, t, res, iters=int(iters), **kw)
+        info = solve_pose(verts, self.proj, base, lms, obs, q, t, res, scale=cfg.landmark_scale, iters=int(iters), rotation=bool(rotation))
         delta = torch.zeros(self.n_frames, 7, dtype=torch.float32, device=dev)
         delta.index_copy_(0, frames, torch.cat([q - q0, t - t0], dim=1))
-        if reduce is not None:
-            delta = reduce(delta)
-        elif self.world > 1:
-            import torch.distributed as tdist
-            if tdist.is_available() and tdist.is_initialized():
-                tdist.all_reduce(delta, op=tdist.ReduceOp.SUM)
+        delta = sum_over_ranks(delta, self.world, reduce)
         # (every rank applies the same sum to the same table, its own rows included: a row nobody solved adds an exact 0, a solved row
         #  is its old value plus the rounded difference -- the solved value itself from the identity start, within an ulp of it otherwise)
         self.per_frame_q.add_(delta[:, :4])
@@ -1207,7 +1215,7 @@ class Fitter:
     def landmark_on(self, i=None):
         """Whether iteration i (default: the current one) runs the landmark term (FitConfig.weight_landmark, landmark_iters)."""
         i = self.iteration if i is None else i
-        return self._lmk is not None and (not self.cfg.landmark_iters or i < self.cfg.landmark_iters)
+        return self._lmk_on and (not self.cfg.landmark_iters or i < self.cfg.landmark_iters)
 
     def _landmark_term(self, vtx, mvp, rows, step=True, residuals=None):
         """The landmark term on the step's meshes vtx [Fb,V,3], matrices mvp [Fb*Nc,4,4] and rows (_target_rows) of the observation table.
@@ -1224,10 +1232,9 @@ class Fitter:
         """(u - u*, v - v*) of every landmark at the current parameters, [Fb,Nc,L,2] in full-resolution pixels, NaN where the entry does
         not count (not observed, a landmark of weight 0, a point behind its camera): the number to look at to judge an alignment.
         frame_ids: frames of this rank's shard (None: all of them), a slice or an integer tensor; view_ids: positions in cam_idxs."""
-        tables = (self._lmk, self._lmk_obs, self._lmk_res) if self._lmk is not None else self._pose_tables
-        if tables is None:      # (neither the term nor align_to_landmarks has built them)
+        if self._lmk is None:      # (neither the term nor align_to_landmarks has built them)
             raise ValueError("Fitter.landmark_residuals needs FitConfig.weight_landmark > 0 on a Scene with landmarks")
-        lms, obs_all, lres = tables
+        lms, obs_all, lres = self._lmk, self._lmk_obs, self._lmk_res
         frames = slice(self.frame_lo, self.frame_hi) if frame_ids is None else frame_ids
         if torch.is_tensor(frames):
             frames = frames.to(self.device, torch.long)
@@ -1463,22 +1470,15 @@ class Fitter:
           view_ids       positions in cam_idxs (None: every selected camera)
           interior_only  leave out silhouette pixels, whose capture holds background
           assign         copy the result into tex_opt (Adam's moments stay as they are: call it before the first step)
-          reduce         reduce(acc) -> acc sums the int64 accumulator over the ranks; None: one all_reduce(SUM) when world > 1 and
-                         torch.distributed is initialised.  Integer sums: every rank resolves the same bits, whatever the sharding
+          reduce         reduce(acc) -> acc sums the int64 accumulator over the ranks (sum_over_ranks' convention).  Integer sums: every
+                         rank resolves the same bits, whatever the sharding
           chunk          frames rasterised at a time
 
         Returns (tex [Ht,Wt,C] float32, filled [Ht,Wt] bool: the texels a capture reached)."""
         dev = self.device
         H, W = self.full_resolution
         Ht, Wt, C = self.tex_opt.shape
-        if frame_ids is None:
-            frames = torch.arange(self.frame_lo, self.frame_hi, device=dev)
-        else:
-            frames = torch.as_tensor(frame_ids).to(dev).reshape(-1)
-        views = None if view_ids is None else torch.as_tensor(view_ids).to(dev).reshape(-1)
-        self.check_indices(frames, views)
-        frames = frames.long()
-        views = None if views is None else views.long()
+        frames, views = shard_indices(self, frame_ids, view_ids)
         glctx = dr.RasterizeGLContext(output_db=False, device=dev)
         targets = self.full_targets.reshape(-1, H, W)
         acc = torch.zeros(Ht, Wt, 2, dtype=torch.int64, device=dev)
@@ -1490,12 +1490,7 @@ class Fitter:
             texc, _ = dr.interpolate(self.uv[None, ...], rast, self.uv_idx)
             # (the targets' row 0 is the bottom row, as the raster's: no flip)
             dr.bake_accumulate(texc, rast, targets.index_select(0, self._target_rows(ids, views)), acc, interior_only=interior_only)
-        if reduce is not None:
-            acc = reduce(acc)
-        elif self.world > 1:
-            import torch.distributed as tdist
-            if tdist.is_available() and tdist.is_initialized():
-                tdist.all_reduce(acc, op=tdist.ReduceOp.SUM)
+        acc = sum_over_ranks(acc, self.world, reduce)
         plane, filled = dr.bake_resolve(acc, color_scale=255.0, dilate=dilate)
         tex = plane[..., None].expand(Ht, Wt, C).contiguous()
         if assign:
@@ -1533,9 +1528,8 @@ class Fitter:
           anchor_camera  a value of cam_idxs whose captures stay as they are (None: cfg.equalise_anchor_camera; without either the
                          common level is the mean over the usable cameras)
           max_gain       None: cfg.equalise_max_gain
-          reduce         reduce(sums) -> sums adds the int64 [Nc,6] table over the ranks (bake_texture's convention); None: one
-                         all_reduce(SUM) when world > 1 and torch.distributed is initialised.  Integer sums: every rank fits the same
-                         tables, whatever the sharding
+          reduce         reduce(sums) -> sums adds the int64 [Nc,6] table over the ranks (sum_over_ranks' convention).  Integer sums:
+                         every rank fits the same tables, whatever the sharding
           chunk          frames rendered at a time
           apply          False: fit and report only; the captures, the composite table and the captured graphs stay as they are
 
@@ -1555,12 +1549,7 @@ class Fitter:
             if isinstance(anchor_camera, bool) or anchor_camera not in self.cam_idxs:
                 raise ValueError(f"Fitter.equalise_exposure: anchor_camera must be one of cam_idxs {tuple(self.cam_idxs)} (got {anchor_camera!r})")
             anchor = self.cam_idxs.index(anchor_camera)
-        if frame_ids is None:
-            frames = torch.arange(self.frame_lo, self.frame_hi, device=dev)
-        else:
-            frames = torch.as_tensor(frame_ids).to(dev).reshape(-1)
-        self.check_indices(frames)
-        frames = frames.long()
+        frames, _ = shard_indices(self, frame_ids)
         lo, hi, keep_from = self.exposure_range()
         glctx = dr.RasterizeGLContext(output_db=bool(cfg.enable_mip), device=dev)
         targets = self.full_targets.reshape(-1, H, W)
@@ -1573,12 +1562,7 @@ class Fitter:
             sums = dr.exposure_sums(colour.contiguous(), rast, targets.index_select(0, rows), mask=None if masks is None else masks.index_select(0, rows),
                                     face_weights=self.face_w, lo=lo, hi=hi)
             table += sums.reshape(int(ids.shape[0]), Nc, 6).sum(0)
-        if reduce is not None:
-            table = reduce(table)
-        elif self.world > 1:
-            import torch.distributed as tdist
-            if tdist.is_available() and tdist.is_initialized():
-                tdist.all_reduce(table, op=tdist.ReduceOp.SUM)
+        table = sum_over_ranks(table, self.world, reduce)
         out = fit_gains(table, method=method, anchor=anchor, max_gain=max_gain, keep_from=keep_from)
         if apply:
             self._apply_exposure(out['lut'])

@@ -141,6 +141,36 @@ class _landmark_penalty(_penalty):
         return (gx if ctx.needs_input_grad[0] else None, gm if ctx.needs_input_grad[1] else None) + (None,) * (ctx.n_inputs - 2)
 
 
+def _check_entry_args(fn, lms, verts, own, obs, resolution, validate):
+    """What landmark_penalty and solve_pose ask of the arguments they share, or ValueError in the name of `fn`: lms, verts, obs [n,L,3],
+    resolution, the set's device and -- validate: one read-back, skipped while a stream is capturing -- the confidences.  own(F, device)
+    -> n: the caller's checks of its own arguments, in their place between verts and obs; its matrices tell the image count n.
+    -> (F, V, n, H, W)."""
+    if not isinstance(lms, LandmarkSet):
+        raise ValueError(f"{fn}: lms must be a LandmarkSet (got {type(lms).__name__})")
+    if not torch.is_tensor(verts) or verts.dim() != 3 or verts.shape[2] != 3 or verts.dtype != torch.float32:
+        raise ValueError(f"{fn}: verts must be float32 [F,V,3] (got {getattr(verts, 'dtype', None)} {tuple(getattr(verts, 'shape', ()))})")
+    F, V = int(verts.shape[0]), int(verts.shape[1])
+    if F < 1 or V != lms.n_vertices:
+        raise ValueError(f"{fn}: verts must hold at least one mesh of the landmark set's {lms.n_vertices} vertices (got {tuple(verts.shape)})")
+    n = own(F, verts.device)
+    if not torch.is_tensor(obs) or obs.dtype != torch.float32 or tuple(obs.shape) != (n, lms.n, 3) or obs.device != verts.device:
+        raise ValueError(f"{fn}: obs must be a float32 tensor [{n},{lms.n},3] on the device of verts")
+    try:
+        H, W = (int(v) for v in resolution)
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: resolution must be (H, W) (got {resolution!r})")
+    if H < 1 or W < 1:
+        raise ValueError(f"{fn}: resolution must be (H, W), both positive (got {resolution!r})")
+    if lms.vtx.device != verts.device:
+        raise ValueError(f"{fn}: the landmark set must be on the device of verts ({verts.device})")
+    if validate and not (verts.is_cuda and torch.cuda.is_current_stream_capturing()):
+        k = obs[..., 2]
+        if not bool((torch.isfinite(k) & (k >= 0)).all()):
+            raise ValueError(f"{fn}: the confidences obs[..., 2] must be finite and not negative")
+    return F, V, n, H, W
+
+
 def landmark_penalty(verts, mvp, lms, obs, weight, resolution, scale=None, eager_grad=False, unit_upstream=False, acc=None, scratch=None,
                      residuals=None, validate=True):
     """weight / F * sum over the meshes of verts [F,V,3] of the mean over the frame's Nc images and the L landmarks of
@@ -155,35 +185,19 @@ def landmark_penalty(verts, mvp, lms, obs, weight, resolution, scale=None, eager
     float32 tensor [F*Nc,L,2] that receives (u - u*, v - v*), NaN where the entry does not count.  validate: check obs on the host (one
     read-back; skipped while a stream is capturing)."""
     inv_c = landmark_inv_scale(scale)
-    if not isinstance(lms, LandmarkSet):
-        raise ValueError(f"landmark_penalty: lms must be a LandmarkSet (got {type(lms).__name__})")
-    if not torch.is_tensor(verts) or verts.dim() != 3 or verts.shape[2] != 3 or verts.dtype != torch.float32:
-        raise ValueError(f"landmark_penalty: verts must be float32 [F,V,3] (got {getattr(verts, 'dtype', None)} {tuple(getattr(verts, 'shape', ()))})")
-    F, V = int(verts.shape[0]), int(verts.shape[1])
-    if F < 1 or V != lms.n_vertices:
-        raise ValueError(f"landmark_penalty: verts must hold at least one mesh of the landmark set's {lms.n_vertices} vertices (got {tuple(verts.shape)})")
-    if (not torch.is_tensor(mvp) or mvp.dim() != 3 or tuple(mvp.shape[1:]) != (4, 4) or mvp.dtype != torch.float32 or mvp.shape[0] < F
-            or mvp.shape[0] % F or mvp.device != verts.device):
-        raise ValueError(f"landmark_penalty: mvp must be float32 [F*Nc,4,4] on the device of verts, frame-major (got {tuple(getattr(mvp, 'shape', ()))} "
-                         f"for {F} meshes)")
-    n = int(mvp.shape[0])
-    if not torch.is_tensor(obs) or obs.dtype != torch.float32 or tuple(obs.shape) != (n, lms.n, 3) or obs.device != verts.device:
-        raise ValueError(f"landmark_penalty: obs must be a float32 tensor [{n},{lms.n},3] on the device of verts")
-    try:
-        H, W = (int(v) for v in resolution)
-    except (TypeError, ValueError):
-        raise ValueError(f"landmark_penalty: resolution must be (H, W) (got {resolution!r})")
-    if H < 1 or W < 1:
-        raise ValueError(f"landmark_penalty: resolution must be (H, W), both positive (got {resolution!r})")
-    if lms.vtx.device != verts.device:
-        raise ValueError(f"landmark_penalty: the landmark set must be on the device of verts ({verts.device})")
-    if residuals is not None and (not torch.is_tensor(residuals) or residuals.dtype != torch.float32 or tuple(residuals.shape) != (n, lms.n, 2)
-                                  or residuals.device != verts.device or not residuals.is_contiguous()):
-        raise ValueError(f"landmark_penalty: residuals must be a contiguous float32 tensor [{n},{lms.n},2] on the device of verts")
-    if validate and not (verts.is_cuda and torch.cuda.is_current_stream_capturing()):
-        k = obs[..., 2]
-        if not bool((torch.isfinite(k) & (k >= 0)).all()):
-            raise ValueError("landmark_penalty: the confidences obs[..., 2] must be finite and not negative")
+
+    def own(F, dev):
+        if (not torch.is_tensor(mvp) or mvp.dim() != 3 or tuple(mvp.shape[1:]) != (4, 4) or mvp.dtype != torch.float32 or mvp.shape[0] < F
+                or mvp.shape[0] % F or mvp.device != dev):
+            raise ValueError(f"landmark_penalty: mvp must be float32 [F*Nc,4,4] on the device of verts, frame-major (got {tuple(getattr(mvp, 'shape', ()))} "
+                             f"for {F} meshes)")
+        n = int(mvp.shape[0])
+        if residuals is not None and (not torch.is_tensor(residuals) or residuals.dtype != torch.float32 or tuple(residuals.shape) != (n, lms.n, 2)
+                                      or residuals.device != dev or not residuals.is_contiguous()):
+            raise ValueError(f"landmark_penalty: residuals must be a contiguous float32 tensor [{n},{lms.n},2] on the device of verts")
+        return n
+
+    _, _, _, H, W = _check_entry_args("landmark_penalty", lms, verts, own, obs, resolution, validate)
     return _landmark_penalty.apply(verts, mvp, lms.vtx, lms.bary, lms.w, lms.inc, obs.contiguous(), inv_c, H, W, weight,
                                    bool(eager_grad and unit_upstream), acc, scratch, residuals)
 
@@ -212,45 +226,29 @@ def solve_pose(verts, proj, base, lms, obs, q, t, resolution, scale=None, iters=
     the INPUT pose (iters=0: nothing else happens).  -> info [F,4] float32 = (cost at the input pose, cost at the returned pose, live
     entries at the returned pose, accepted trials).  ValueError names what does not fit."""
     inv_c = landmark_inv_scale(scale)
-    if not isinstance(lms, LandmarkSet):
-        raise ValueError(f"solve_pose: lms must be a LandmarkSet (got {type(lms).__name__})")
-    if not torch.is_tensor(verts) or verts.dim() != 3 or verts.shape[2] != 3 or verts.dtype != torch.float32:
-        raise ValueError(f"solve_pose: verts must be float32 [F,V,3] (got {getattr(verts, 'dtype', None)} {tuple(getattr(verts, 'shape', ()))})")
-    F, V = int(verts.shape[0]), int(verts.shape[1])
-    if F < 1 or V != lms.n_vertices:
-        raise ValueError(f"solve_pose: verts must hold at least one mesh of the landmark set's {lms.n_vertices} vertices (got {tuple(verts.shape)})")
-    dev = verts.device
-    for name, m in (('proj', proj), ('base', base)):
-        if not torch.is_tensor(m) or m.dim() != 3 or tuple(m.shape[1:]) != (4, 4) or m.dtype != torch.float32 or m.shape[0] < 1 or m.device != dev:
-            raise ValueError(f"solve_pose: {name} must be float32 [Nc,4,4] on the device of verts (got {tuple(getattr(m, 'shape', ()))})")
-    Nc = int(proj.shape[0])
-    if int(base.shape[0]) != Nc:
-        raise ValueError(f"solve_pose: proj and base must hold the same cameras (got {Nc} and {int(base.shape[0])})")
-    if not torch.is_tensor(obs) or obs.dtype != torch.float32 or tuple(obs.shape) != (F * Nc, lms.n, 3) or obs.device != dev:
-        raise ValueError(f"solve_pose: obs must be a float32 tensor [{F * Nc},{lms.n},3] on the device of verts")
-    for name, p, k in (('q', q, 4), ('t', t, 3)):
-        if not torch.is_tensor(p) or p.dtype != torch.float32 or tuple(p.shape) != (F, k) or p.device != dev or not p.is_contiguous():
-            raise ValueError(f"solve_pose: {name} must be a contiguous float32 tensor [{F},{k}] on the device of verts "
-                             f"(got {tuple(getattr(p, 'shape', ()))})")
-    try:
-        H, W = (int(v) for v in resolution)
-    except (TypeError, ValueError):
-        raise ValueError(f"solve_pose: resolution must be (H, W) (got {resolution!r})")
-    if H < 1 or W < 1:
-        raise ValueError(f"solve_pose: resolution must be (H, W), both positive (got {resolution!r})")
-    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
-        raise ValueError(f"solve_pose: iters must be an integer >= 0 (got {iters!r})")
-    if isinstance(damping, bool) or not isinstance(damping, (int, float)) or not np.isfinite(damping) or not damping > 0:
-        raise ValueError(f"solve_pose: damping must be finite and positive (got {damping!r})")
-    if lms.vtx.device != dev:
-        raise ValueError(f"solve_pose: the landmark set must be on the device of verts ({dev})")
-    if normal_out is not None and (not torch.is_tensor(normal_out) or normal_out.dtype != torch.float32 or tuple(normal_out.shape) != (F, 28)
-                                   or normal_out.device != dev or not normal_out.is_contiguous()):
-        raise ValueError(f"solve_pose: normal_out must be a contiguous float32 tensor [{F},28] on the device of verts")
+
+    def own(F, dev):
+        for name, m in (('proj', proj), ('base', base)):
+            if not torch.is_tensor(m) or m.dim() != 3 or tuple(m.shape[1:]) != (4, 4) or m.dtype != torch.float32 or m.shape[0] < 1 or m.device != dev:
+                raise ValueError(f"solve_pose: {name} must be float32 [Nc,4,4] on the device of verts (got {tuple(getattr(m, 'shape', ()))})")
+        if int(base.shape[0]) != int(proj.shape[0]):
+            raise ValueError(f"solve_pose: proj and base must hold the same cameras (got {int(proj.shape[0])} and {int(base.shape[0])})")
+        for name, p, k in (('q', q, 4), ('t', t, 3)):
+            if not torch.is_tensor(p) or p.dtype != torch.float32 or tuple(p.shape) != (F, k) or p.device != dev or not p.is_contiguous():
+                raise ValueError(f"solve_pose: {name} must be a contiguous float32 tensor [{F},{k}] on the device of verts "
+                                 f"(got {tuple(getattr(p, 'shape', ()))})")
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
+            raise ValueError(f"solve_pose: iters must be an integer >= 0 (got {iters!r})")
+        if isinstance(damping, bool) or not isinstance(damping, (int, float)) or not np.isfinite(damping) or not damping > 0:
+            raise ValueError(f"solve_pose: damping must be finite and positive (got {damping!r})")
+        if normal_out is not None and (not torch.is_tensor(normal_out) or normal_out.dtype != torch.float32 or tuple(normal_out.shape) != (F, 28)
+                                       or normal_out.device != dev or not normal_out.is_contiguous()):
+            raise ValueError(f"solve_pose: normal_out must be a contiguous float32 tensor [{F},28] on the device of verts")
+        return F * int(proj.shape[0])
+
+    F, V, n, H, W = _check_entry_args("solve_pose", lms, verts, own, obs, resolution, True)
+    Nc, dev = n // F, verts.device
     if not (verts.is_cuda and torch.cuda.is_current_stream_capturing()):
-        k = obs[..., 2]
-        if not bool((torch.isfinite(k) & (k >= 0)).all()):
-            raise ValueError("solve_pose: the confidences obs[..., 2] must be finite and not negative")
         qn = q.detach().double().norm(dim=1)
         if not bool((torch.isfinite(qn) & (qn > 0)).all()):
             bad = int(torch.nonzero(~(torch.isfinite(qn) & (qn > 0)))[0])

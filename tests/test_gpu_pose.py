@@ -318,11 +318,11 @@ def _float32_solver_residual(ft):
 
 def test_align_to_landmarks_brings_every_frame_home_and_rows_keep_it_there():
     ft = _fitter(quat_renorm='rows')
-    assert ft._lmk is None and ft._pose_tables is None                           # weight_landmark = 0: nothing is built before the call
+    assert ft._lmk is None and ft._lmk_obs is None and not ft.landmark_on()       # weight_landmark = 0: nothing is built before the call
     with pytest.raises(ValueError, match="weight_landmark"):
         ft.landmark_residuals()
     out = ft.align_to_landmarks()
-    assert ft._lmk is None and ft._pose_tables is not None and not ft.landmark_on()      # ... and the term stays off
+    assert ft._lmk is not None and ft._lmk_scratch is None and not ft.landmark_on()      # ... and the term stays off
     after = LR.mean_live_residual(ft.landmark_residuals())                        # the independent chain: k_mvp_fwd, k_landmark_points
     ref, (q32, t32, info32) = _float32_solver_residual(ft)
     bound = 8 * ref + 4 * U * (RES[0] + RES[1])

@@ -425,3 +425,30 @@ def test_pixel_term_rules_need_no_fitter():
                           (dict(blur_sigma_end=1.0, **bk), False), (nk, False), (dict(fused_loss=False, hip_graph=True), False),
                           (dict(robust='charbonnier', robust_scale=10.0, face_weights=[1.0], saturation=140, weight_outside=0.0), True)]:
         fit.check_pixel_terms(fit.FitConfig(**kw), has_masks)
+
+
+def test_shard_pass_helpers_need_no_fitter():
+    """fit.shard_indices and fit.sum_over_ranks, the preamble and the cross-rank sum that bake_texture, equalise_exposure and
+    align_to_landmarks share, on CPU tensors and a stand-in for the Fitter's shard (frames 3..5 of 8, two cameras)."""
+    import functools
+    import types
+    from fpc_diffrend_amd import fit
+    ft = types.SimpleNamespace(frame_lo=3, frame_hi=6, cam_idxs=[0, 3], device=torch.device('cpu'))
+    ft.check_indices = functools.partial(fit.Fitter.check_indices, ft)
+    frames, views = fit.shard_indices(ft, None)
+    assert views is None and frames.dtype == torch.int64 and torch.equal(frames, torch.arange(3, 6))
+    for ids, vws in (([5, 3], [1, 0]), (torch.tensor([5, 3], dtype=torch.int32), torch.tensor([1, 0], dtype=torch.int32)),
+                     (torch.tensor([[5], [3]]), torch.tensor([[1, 0]]))):
+        frames, views = fit.shard_indices(ft, ids, vws)
+        assert frames.dtype == views.dtype == torch.int64 and frames.tolist() == [5, 3] and views.tolist() == [1, 0]
+    for ids, vws, why in (([2], None, r"frame numbers 2\.\.2 outside this rank's frames \[3, 6\)"), ([6], None, "outside this rank's frames"),
+                          ([], None, "non-empty 1-D integer tensor"), ([3.5], None, "non-empty 1-D integer tensor"),
+                          ([3], [2], r"view positions 2\.\.2 outside cam_idxs")):
+        with pytest.raises(IndexError, match=why):
+            fit.shard_indices(ft, ids, vws)
+    t = torch.arange(6).reshape(2, 3)
+    assert torch.equal(fit.sum_over_ranks(t, 2, reduce=lambda a: a + 1), t + 1)      # the caller's reduce, whatever the world
+    assert fit.sum_over_ranks(t, 1) is t
+    import torch.distributed as tdist
+    assert not (tdist.is_available() and tdist.is_initialized())
+    assert fit.sum_over_ranks(t, 2) is t and torch.equal(t, torch.arange(6).reshape(2, 3))      # no process group: the tensor as it is

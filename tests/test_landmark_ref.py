@@ -220,6 +220,29 @@ def test_landmark_penalty_argument_errors():
         fit.landmark_penalty(**ok, scale=2.0)
 
 
+_SHARED_BAD = [("lms", dict(lms=None), "lms must be a LandmarkSet"), ("verts dtype", dict(verts=torch.zeros(1, 4, 3, dtype=torch.float64)), "verts must be float32"),
+               ("verts rank", dict(verts=torch.zeros(4, 3)), "verts must be float32"), ("vertex count", dict(verts=torch.zeros(1, 5, 3)), "4 vertices"),
+               ("obs shape", dict(obs=torch.zeros(1, 3, 3)), "obs must be"), ("resolution pair", dict(resolution=8), "resolution must be"),
+               ("resolution positive", dict(resolution=(0, 8)), "both positive")]
+
+
+@pytest.mark.parametrize("entry", ["landmark_penalty", "solve_pose"])
+def test_the_shared_argument_checks_speak_in_the_callers_name(entry):
+    """What landmark_penalty and solve_pose ask of lms, verts, obs and resolution is one check: each fault raises ValueError, and the
+    message starts with the name of the function that was called.  CPU tensors: the checks come before any launch."""
+    from fpc_diffrend_amd import fit
+    lms = fit.LandmarkSet([{'vertex': 0}, {'face': 0, 'bary': (0.2, 0.3, 0.5)}], 4, np.array([[0, 1, 2], [2, 1, 3]]), 'cpu')
+    ok = dict(verts=torch.zeros(1, 4, 3), lms=lms, obs=torch.zeros(1, 2, 3), resolution=(8, 8))
+    if entry == "landmark_penalty":
+        ok.update(mvp=torch.eye(4).reshape(1, 4, 4), weight=1.0)
+    else:
+        ok.update(proj=torch.eye(4).reshape(1, 4, 4), base=torch.eye(4).reshape(1, 4, 4), q=torch.tensor([[0.0, 0.0, 0.0, 1.0]]), t=torch.zeros(1, 3))
+    for what, over, why in _SHARED_BAD:
+        with pytest.raises(ValueError, match=why) as e:
+            getattr(fit, entry)(**{**ok, **over})
+        assert str(e.value).startswith(entry + ": "), (what, str(e.value))
+
+
 def _lib_loaded():
     from fpc_diffrend_amd import _lib
     if not os.path.exists(_lib.LIB_PATH):

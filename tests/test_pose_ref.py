@@ -191,6 +191,29 @@ def test_header_declares_the_entry_and_the_binding_matches():
     assert "landmark_pose.hip" in open(os.path.join(ROOT, "fpc_diffrend_amd", "csrc", "Makefile")).read()
 
 
+def test_pose_kernel_has_no_private_segment():
+    """read from the built object (tests/codeobj.py).  LDS: the 29 partial sums of four waves, the new and the current
+    sums, the trial and the best pose, two flags -- 768 bytes, which the compiler lays out in 784."""
+    import codeobj
+    recs = codeobj.kernels("landmark_pose.o")
+    if recs is None:
+        pytest.skip("no built objects / llvm tools")
+    own = {name: (private, lds) for name, private, lds in recs if "k_landmark_pose" in name}
+    assert len(own) == 1 and list(own.values()) == [(0, 784)], own
+
+
+def test_the_landmark_entry_is_shared_not_copied():
+    """One statement of an entry's table read and of its robust pair, in the header that the term and the solve both include."""
+    csrc = os.path.join(ROOT, "fpc_diffrend_amd", "csrc")
+    marks = ("lm_vtx[(size_t)L + l]", "sqrtf(1.0f + (zu * zu")
+    for src in ("landmark.hip", "landmark_pose.hip"):
+        text = open(os.path.join(csrc, src)).read()
+        assert '#include "landmark_entry.h"' in text and not any(m in text for m in marks), src
+    header = open(os.path.join(csrc, "landmark_entry.h")).read()
+    assert [header.count(m) for m in marks] == [1, 1]
+    assert "landmark_entry.h" in open(os.path.join(csrc, "Makefile")).read()
+
+
 def test_fitconfig_refuses_bad_pose_options():
     from fpc_diffrend_amd import fit
     cfg = fit.FitConfig()
