@@ -211,6 +211,9 @@ SYMBOLS = {
     "fpcdr_landmark_penalty": (_int, [_p, _p, _p, _p, _p, _p, _p, ctypes.c_float, _i, _i, _p, _p, _p, _p, _p, _p, _p, ctypes.c_float,
                                       _i, _i, _i, _i, _i, _p]),
     "fpcdr_landmark_pose": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, ctypes.c_float, _i, _i, _i, _i, ctypes.c_float, _p, _p, _i, _i, _i, _i, _p]),
+    "fpcdr_landmark_expr_scratch_bytes": (_sz, [_i, _i, _i]),
+    "fpcdr_landmark_expr": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, ctypes.c_float, ctypes.c_float, _i, _i, _i, ctypes.c_float, _p, _p, _p, _sz,
+                                   _i, _i, _i, _i, _i, _p]),
     "fpcdr_tex_prior": (_int, [_p, _p, _p, _p, ctypes.c_float, ctypes.c_float, ctypes.c_float, _p, _p, _p, _p, _i, _i, _i, _p]),
     "fpcdr_blend_fwd": (_int, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "fpcdr_blend_bwd_w": (_int, [_p, _p, _p, _i, _i, _i, _p]),

@@ -8,13 +8,20 @@
 // the observation (u*, v*), wk = omega kappa, and seen = kappa > 0 && omega > 0: the part of the live test that does not need p.w
 struct LandmarkEntry { float us, vs, wk; bool seen; };
 
-// lm_vtx [3,L] int32 and lm_bary [3,L] float32, corner-major: landmark l is the point p = sum_k lm_bary[k][l] xf[lm_vtx[k][l]]; lm_w [L] or
-// null: 1.  o: the entry's (u*, v*, kappa) in raster pixels.
+// the three corners of landmark l and their weights, from lm_vtx [3,L] int32 and lm_bary [3,L] float32, corner-major
+struct LandmarkCorners { int i0, i1, i2; float b0, b1, b2; };
+
+__device__ __forceinline__ LandmarkCorners landmark_corners(const int32_t *__restrict__ lm_vtx, const float *__restrict__ lm_bary, int L, int l) {
+    return {lm_vtx[l], lm_vtx[(size_t)L + l], lm_vtx[2 * (size_t)L + l], lm_bary[l], lm_bary[(size_t)L + l], lm_bary[2 * (size_t)L + l]};
+}
+
+// landmark l is the point p = sum_k lm_bary[k][l] xf[lm_vtx[k][l]]; lm_w [L] or null: 1.  o: the entry's (u*, v*, kappa) in raster pixels.
 __device__ __forceinline__ void landmark_entry(const float *__restrict__ xf, const int32_t *__restrict__ lm_vtx,
                                                const float *__restrict__ lm_bary, const float *__restrict__ lm_w,
                                                const float *__restrict__ o, int L, int l, float (&p)[3], LandmarkEntry &e) {
-    const int i0 = lm_vtx[l], i1 = lm_vtx[(size_t)L + l], i2 = lm_vtx[2 * (size_t)L + l];
-    const float b0 = lm_bary[l], b1 = lm_bary[(size_t)L + l], b2 = lm_bary[2 * (size_t)L + l];
+    const LandmarkCorners c = landmark_corners(lm_vtx, lm_bary, L, l);
+    const int i0 = c.i0, i1 = c.i1, i2 = c.i2;
+    const float b0 = c.b0, b1 = c.b1, b2 = c.b2;
     const float omega = lm_w ? lm_w[l] : 1.0f;
     const float us = o[0], vs = o[1], kappa = o[2];
 #pragma unroll

@@ -36,8 +36,9 @@ import torch
 from . import _lib, camera
 from . import ops as dr
 from .exposure import check_exposure_options, compose, fit_gains, identity_lut, is_identity
-from .landmarks import (LandmarkSet, check_landmark_options, check_pose_options, landmark_incidence, landmark_inv_scale, landmark_penalty,
-                        landmark_tables, project_landmarks, read_landmarks, solve_pose, write_landmarks)
+from .landmarks import (LandmarkSet, check_expression_options, check_landmark_options, check_pose_options, landmark_incidence,
+                        landmark_inv_scale, landmark_penalty, landmark_tables, project_landmarks, read_landmarks, solve_expression, solve_pose,
+                        write_landmarks)
 from .mesh_reg import (MeshTopology, RestShape, _check_item_weights, _uniform_laplacian, bend_penalty, check_motion_options,
                        hinge_incidence, hinge_rest_cs, hinge_vertices, laplacian_penalty, mesh_edge_loss, mesh_laplacian_smoothing,
                        mesh_normal_consistency, motion_inv_scale, motion_penalty, rest_edge_lengths, stretch_penalty)
@@ -715,6 +716,13 @@ class FitConfig:
                                     # Needs a Scene with landmarks and use_landmarks, not weight_landmark > 0
     init_pose_iters: int = 20       # the trials of that solve
     init_pose_rotation: bool = True             # False: the translation alone (the only form quat_renorm='tensor' keeps on several frames)
+    init_expression: str = "keep"   # 'keep' | 'landmarks': every frame's blend weights are solved from its landmarks at the end of
+                                    # construction (Fitter.solve_expression; DESIGN.md 3, "Expression solve rule"), after init_pose and before
+                                    # init_texture='bake'.  mode 'prior' or 'combined'; needs a Scene with landmarks and use_landmarks
+    init_expression_iters: int = 20             # the trials of that solve
+    init_expression_ridge: float = 0.0          # its ridge towards neutral, px^2 per unit weight^2 (no recommended value: none is measured)
+    init_landmark_rounds: int = 1   # the pose solve (init_pose='landmarks') and then the expression solve (init_expression='landmarks') run
+                                    # this many times in turn: the two are solved alternately, not jointly
     quat_renorm: str = "tensor"     # 'tensor': the reference's division of q_opt and per_frame_q by the norm of the WHOLE tensor after every
                                     # step (quirk Q3) | 'rows': every quaternion divided by its own norm, so that a rotation survives the loop
     cam_idxs: Sequence[int] = (0, 1, 2, 3, 4, 5, 6, 7, 8)
@@ -833,6 +841,7 @@ class FitConfig:
         check_tex_prior_options(self)
         check_landmark_options(self)
         check_pose_options(self)
+        check_expression_options(self)
         check_exposure_options(self)
 
     def weights_configured(self):
@@ -1060,8 +1069,11 @@ class Fitter:
                 self._levels[s] = (lt, lres, dr.reference_background_sumsq(lt.reshape(-1, *lres), BACKGROUND).reshape(lt.shape[:2]), lm)
         self._lmk, self._lmk_obs, self._lmk_res = None, None, None      # (_landmark_tables: built on first use, by the term or by align_to_landmarks)
         self._lmk_on, self._lmk_scratch = False, None      # (the landmark TERM's own: _build_landmarks)
-        if cfg.init_pose == 'landmarks':      # (in front of the bake, which reads the pose)
-            self.align_to_landmarks(iters=cfg.init_pose_iters, rotation=cfg.init_pose_rotation)
+        for _ in range(cfg.init_landmark_rounds):      # (in front of the bake, which reads the pose and the shape)
+            if cfg.init_pose == 'landmarks':
+                self.align_to_landmarks(iters=cfg.init_pose_iters, rotation=cfg.init_pose_rotation)
+            if cfg.init_expression == 'landmarks':
+                self.solve_expression(iters=cfg.init_expression_iters, ridge=cfg.init_expression_ridge)
         baked = None
         if cfg.init_texture == 'bake':
             _, baked = self.bake_texture()
@@ -1210,6 +1222,69 @@ class Fitter:
         #  is its old value plus the rounded difference -- the solved value itself from the identity start, within an ulp of it otherwise)
         self.per_frame_q.add_(delta[:, :4])
         self.per_frame_t.add_(delta[:, 4:])
+        return {'before': before, 'after': mean_residual(), 'info': info}
+
+    @torch.no_grad()
+    def solve_expression(self, frame_ids=None, iters=20, ridge=None, reduce=None):
+        """Solve every frame's blend weights from its landmarks ("Expression solve rule"; fit.solve_expression), in ONE launch,
+        at the current meshes (Fitter.vertices), matrices (Fitter.mvp) and weights: the stage after align_to_landmarks of a
+        landmark-driven fit -- an open jaw is tens of pixels, and Adam moves a weight by lr_base a visit.  Every camera of cam_idxs, the
+        configured landmark_scale and landmark_weights.  Needs a Scene with landmarks and use_landmarks, NOT weight_landmark > 0.
+        mode 'prior' or 'combined' (the correctives stay where they are); mode='free' has no rig weights: ValueError.
+
+          frame_ids  frames of this rank's shard (None: all of them), a sequence or an integer tensor
+          iters      trials of the damped Gauss-Newton solve
+          ridge      the pull towards neutral, px^2 per unit weight^2 (None: FitConfig.init_expression_ridge, whose default is 0)
+          reduce     reduce(delta) -> delta sums the float32 [F,Kb] table of weight changes, zero outside this rank's frames, over the
+                     ranks (sum_over_ranks' convention).  The replicated parameters stay identical on every rank
+
+        Write-back: with W = maps_intermediate . maps ([Kb,F], the product the step forms), every rank writes maps_intermediate <- W +
+        delta^T and maps <- the identity, in place (a captured graph replays with them).  Any [Kb,F] table is representable so, whatever
+        Kb and F, and a product with the identity is exact: rig_weights() then returns the table itself, and a frame nobody solved keeps
+        its weights bit for bit.  On one rank (world = 1, no reduce) the solved rows are the kernel's output bit for bit, from any
+        start; across ranks every rank must form the same table from the summed change, W + (solved - W): the solved weights bit for
+        bit from a neutral start, within an ulp of them otherwise.  A frame may be named once (ValueError).  This RESETS the factorisation the optimiser has been working on and leaves Adam's moments as they are: call it before the
+        first step.  Returns {'before', 'after'}: the mean live |residual| in pixels over the solved frames, and 'info' [Fb,4] = (cost
+        before, cost after, live entries, accepted trials) per frame."""
+        cfg, dev = self.cfg, self.device
+        if cfg.mode == 'free':
+            raise ValueError("Fitter.solve_expression needs mode='prior' or 'combined': mode='free' has no rig weights to solve")
+        if not cfg.use_landmarks:
+            raise ValueError("Fitter.solve_expression needs FitConfig.use_landmarks")
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
+            raise ValueError(f"Fitter.solve_expression: iters must be an integer >= 0 (got {iters!r})")
+        ridge = cfg.init_expression_ridge if ridge is None else ridge
+        if isinstance(ridge, bool) or not isinstance(ridge, (int, float)) or not np.isfinite(ridge) or ridge < 0:
+            raise ValueError(f"Fitter.solve_expression: ridge must be finite and not negative (got {ridge!r})")
+        lms, obs_all, res = self._landmark_tables("Fitter.solve_expression")
+        frames, _ = shard_indices(self, frame_ids)
+        Fb = int(frames.shape[0])
+        if int(torch.unique(frames).shape[0]) != Fb:      # (a frame named twice would be written twice, in no fixed order)
+            raise ValueError("Fitter.solve_expression: frame_ids names a frame more than once")
+        mi, maps = self.maps_intermediate['local'], self.maps['local']
+        verts = self.vertices(frames, validate=False).reshape(Fb, -1, 3).contiguous()
+        mvp = self.mvp(frames, None, validate=False)
+        obs = obs_all.index_select(0, self._target_rows(frames))
+        table = rig_weights(mi.detach(), maps.detach(), slice(0, self.n_frames)).contiguous()      # W^T [F,Kb]
+        w = table.index_select(0, frames).contiguous()
+        w0 = w.clone()
+
+        def mean_residual():      # (over the solved frames, at the parameters as they stand)
+            rr = self.landmark_residuals(frames)
+            live = ~torch.isnan(rr[..., 0])
+            return float(rr[live].double().norm(dim=1).mean()) if bool(live.any()) else float('nan')
+
+        before = mean_residual()
+        info = solve_expression(verts, mvp, self.datasets['local'], lms, obs, w, res, scale=cfg.landmark_scale, ridge=float(ridge), iters=int(iters))
+        delta = torch.zeros(self.n_frames, w.shape[1], dtype=torch.float32, device=dev)
+        delta.index_copy_(0, frames, w - w0)
+        delta = sum_over_ranks(delta, self.world, reduce)
+        # (every rank applies the same sum to the same table: a row nobody solved adds an exact 0)
+        table = table + delta
+        if self.world == 1 and reduce is None:      # nobody else to agree with: the solved rows are the kernel's output itself
+            table.index_copy_(0, frames, w)
+        mi.copy_(table.t())
+        maps.copy_(torch.eye(self.n_frames, dtype=torch.float32, device=dev))
         return {'before': before, 'after': mean_residual(), 'info': info}
 
     def landmark_on(self, i=None):

@@ -1,7 +1,8 @@
 """
 The landmark term ("Landmark rule"): named points of the mesh held to their detected 2D positions in the captures -- the
-tables of a set of landmarks (LandmarkSet), the penalty whose device code is csrc/landmark.hip (landmark_penalty), the float64
-projection of a synthetic Scene's own landmarks (project_landmarks) and the landmark file of a take (read_landmarks / write_landmarks).
+tables of a set of landmarks (LandmarkSet), the penalty whose device code is csrc/landmark.hip (landmark_penalty), the two closed-form
+starts from the landmarks, every frame's rigid pose (solve_pose, csrc/landmark_pose.hip) and blend weights (solve_expression,
+csrc/landmark_expr.hip), the float64 projection of a synthetic Scene's own landmarks (project_landmarks) and the landmark file of a take (read_landmarks / write_landmarks).
 The reference has no such term.  fit.py imports these names: fit.LandmarkSet, fit.landmark_penalty, ... are the documented spelling.
 """
 import json
@@ -258,6 +259,81 @@ def solve_pose(verts, proj, base, lms, obs, q, t, resolution, scale=None, iters=
     _lib.call("fpcdr_landmark_pose", _ptr(x), _ptr(pj), _ptr(bs), _ptr(lms.vtx), _ptr(lms.bary), _ptr(lms.w), _ptr(ob), _ptr(q.detach()),
               _ptr(t.detach()), float(inv_c), W, H, int(iters), 1 if rotation else 0, float(damping), _ptr(info), _ptr(normal_out), F, Nc, V,
               lms.n, _stream())
+    return info
+
+
+EXPR_MAX_KB, EXPR_MAX_L = 160, 512      # what fpcdr_landmark_expr accepts (csrc/landmark_expr.hip)
+
+
+def check_expression_options(cfg):
+    """What FitConfig's init_expression / init_landmark_rounds fields ask (FitConfig.__post_init__), or ValueError.  Needs no GPU and no
+    Scene."""
+    if cfg.init_expression not in ('keep', 'landmarks'):
+        raise ValueError(f"FitConfig.init_expression must be 'keep' or 'landmarks' (got {cfg.init_expression!r})")
+    n = cfg.init_expression_iters
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+        raise ValueError(f"FitConfig.init_expression_iters must be an integer >= 0 (got {n!r})")
+    r = cfg.init_expression_ridge
+    if isinstance(r, bool) or not isinstance(r, (int, float)) or not np.isfinite(r) or r < 0:
+        raise ValueError(f"FitConfig.init_expression_ridge must be finite and not negative (got {r!r})")
+    k = cfg.init_landmark_rounds
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError(f"FitConfig.init_landmark_rounds must be an integer >= 1 (got {k!r})")
+    if cfg.init_expression == 'landmarks' and cfg.mode == 'free':
+        raise ValueError("FitConfig.init_expression='landmarks' needs mode='prior' or 'combined': mode='free' has no rig weights to solve")
+
+
+def solve_expression(verts, mvp, basis, lms, obs, w, resolution, scale=None, ridge=0.0, iters=20, damping=1e-3, normal_out=None):
+    """Every frame's blend weights (w [F,Kb] float32, written IN PLACE) solved from its landmarks by damped Gauss-Newton on the Landmark
+    rule's cost plus a ridge, one launch for all frames and trials ("Expression solve rule"; fpcdr_landmark_expr): verts
+    [F,V,3] are the meshes AT the weights w, mvp [F*Nc,4,4] the matrices as landmark_penalty takes them (the pose is fixed), basis
+    [3V,Kb] float32 the blend basis (datasets['local']), lms a LandmarkSet, obs [F*Nc,L,3] = (u*, v*, kappa) in raster pixels of a
+    resolution = (H, W) capture, scale the Charbonnier scale in pixels (None: L2).  The point of landmark l at the weights w' is its
+    point on verts plus A_l (w' - w), A the basis at the landmark's corners.  ridge >= 0, in px^2 per unit weight^2 on the Landmark
+    rule's per-entry scale, pulls towards neutral (the cost gains ridge * Nc * L * sum_k w_k^2).  iters trials from the damping
+    `damping`; a trial is kept when it has at least as many live entries and a smaller cost.  A frame with fewer than 3 live entries,
+    and a weight that no live landmark touches (without a ridge), stay bit for bit as they were.  Kb <= 160 and L <= 512.
+    normal_out: a contiguous float64 tensor [F, Kb (Kb + 1) / 2 + Kb + 2] that receives the packed lower triangle of H, g, E and the
+    live count at the INPUT weights (iters=0: nothing else happens).  -> info [F,4] float32 = (cost at the input weights, cost at the
+    returned weights, live entries there, accepted trials).  ValueError names what does not fit."""
+    inv_c = landmark_inv_scale(scale)
+
+    def own(F, dev):
+        if (not torch.is_tensor(mvp) or mvp.dim() != 3 or tuple(mvp.shape[1:]) != (4, 4) or mvp.dtype != torch.float32 or mvp.shape[0] < F
+                or mvp.shape[0] % F or mvp.device != dev):
+            raise ValueError(f"solve_expression: mvp must be float32 [F*Nc,4,4] on the device of verts, frame-major (got "
+                             f"{tuple(getattr(mvp, 'shape', ()))} for {F} meshes)")
+        V = int(verts.shape[1])
+        if (not torch.is_tensor(basis) or basis.dim() != 2 or basis.shape[0] != 3 * V or basis.shape[1] < 1 or basis.dtype != torch.float32
+                or basis.device != dev):
+            raise ValueError(f"solve_expression: basis must be float32 [{3 * V},Kb] on the device of verts (got {tuple(getattr(basis, 'shape', ()))})")
+        Kb = int(basis.shape[1])
+        if Kb > EXPR_MAX_KB or lms.n > EXPR_MAX_L:
+            raise ValueError(f"solve_expression: at most {EXPR_MAX_KB} blend weights and {EXPR_MAX_L} landmarks (got {Kb} and {lms.n})")
+        if not torch.is_tensor(w) or w.dtype != torch.float32 or tuple(w.shape) != (F, Kb) or w.device != dev or not w.is_contiguous():
+            raise ValueError(f"solve_expression: w must be a contiguous float32 tensor [{F},{Kb}] on the device of verts "
+                             f"(got {tuple(getattr(w, 'shape', ()))})")
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
+            raise ValueError(f"solve_expression: iters must be an integer >= 0 (got {iters!r})")
+        if isinstance(damping, bool) or not isinstance(damping, (int, float)) or not np.isfinite(damping) or not damping > 0:
+            raise ValueError(f"solve_expression: damping must be finite and positive (got {damping!r})")
+        if isinstance(ridge, bool) or not isinstance(ridge, (int, float)) or not np.isfinite(ridge) or ridge < 0:
+            raise ValueError(f"solve_expression: ridge must be finite and not negative (got {ridge!r})")
+        n_out = Kb * (Kb + 1) // 2 + Kb + 2
+        if normal_out is not None and (not torch.is_tensor(normal_out) or normal_out.dtype != torch.float64 or tuple(normal_out.shape) != (F, n_out)
+                                       or normal_out.device != dev or not normal_out.is_contiguous()):
+            raise ValueError(f"solve_expression: normal_out must be a contiguous float64 tensor [{F},{n_out}] on the device of verts")
+        return int(mvp.shape[0])
+
+    F, V, n, H, W = _check_entry_args("solve_expression", lms, verts, own, obs, resolution, True)
+    Nc, Kb, dev = n // F, int(basis.shape[1]), verts.device
+    info = torch.empty(F, 4, dtype=torch.float32, device=dev)
+    nbytes = int(_lib.load().fpcdr_landmark_expr_scratch_bytes(F, lms.n, Kb))
+    scratch = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
+    x, m, b, ob = verts.detach().contiguous(), mvp.detach().contiguous(), basis.detach().contiguous(), obs.contiguous()
+    _lib.call("fpcdr_landmark_expr", _ptr(x), _ptr(m), _ptr(b), _ptr(lms.vtx), _ptr(lms.bary), _ptr(lms.w), _ptr(ob), _ptr(w.detach()),
+              float(inv_c), float(ridge), W, H, int(iters), float(damping), _ptr(info), _ptr(normal_out), _ptr(scratch), nbytes, F, Nc, V,
+              lms.n, Kb, _stream())
     return info
 
 

@@ -498,6 +498,32 @@ int fpcdr_landmark_pose(const float *x /* [F,V,3] */, const float *proj /* [Nc,4
                         int32_t rotation, float lambda0, float *info /* [F,4] */, float *normal_out /* [F,28] or NULL */, int32_t F,
                         int32_t Nc, int32_t V, int32_t L, void *stream);
 
+/* Every frame's blend weights solved from its landmarks ("Expression solve rule"), two launches for all F frames (the landmark
+ * basis, then every trial of every frame).  A pure addition: FPCDR_ABI_VERSION stays 16.  The pose is fixed: mvp [F*Nc,4,4] are the step's
+ * own matrices and the Landmark rule's chain p = mvp (q, 1) is used as it stands; x [F,V,3] are the meshes AT the weights w [F,Kb] (in and
+ * out), basis [3V,Kb] row-major the blend basis.  A [3L,Kb] = the basis rows at the landmarks' corners, (b0 B0 + b1 B1) + b2 B2, float32.
+ *   q_l(w') = q_l(x) + A_l (w' - w_in) (float32, k ascending; at w' = w_in the entry is fpcdr_landmark_penalty's to the bit);  u, v, live,
+ *   the residual r, rho and d = rho'(s) as there;  E_f = sum over the live entries of lm_w kappa rho(s);  C_f = E_f + rs sum_k w_k^2
+ *   (float64, k ascending) with rs = ridge Nc L.
+ *   g_u = (width / 2) / p.w * (mvp_x[0:3] - (p.x / p.w) mvp_w[0:3]), g_v alike;  per landmark, in float32, over the cameras ascending with
+ *   w_e = lm_w kappa d:  S_l = sum w_e (g_u g_u^T + g_v g_v^T),  s_l = sum w_e (g_u r_u + g_v r_v);  then in float64, l ascending:
+ *   H = sum_l A_l^T S_l A_l (packed lower triangle, row-major: entry (i, k <= i) at i (i + 1) / 2 + k),  g = sum_l A_l^T s_l.
+ * A trial factors M + lambda diag M, M = H + rs I, by right-looking Cholesky in float64 (a pivot that is not positive, or a step that is
+ * not finite: a rejected trial) for the right-hand side -(g + rs w), forms w' = float32(w + delta), and is accepted iff it has at least as
+ * many live entries and a smaller C; then lambda <- max(lambda / 10, 1e-9), otherwise min(10 lambda, 1e9).  A weight whose M_kk is exactly 0
+ * stays bit for bit.  A frame with fewer than 3 live entries at its input, or without an accepted trial, keeps w bit for bit.
+ * info [F,4] = (C at the input, C at the returned weights, live entries there, accepted trials).  normal_out or NULL: per frame
+ * Kb (Kb + 1) / 2 + Kb + 2 float64 = the packed H, g, E, the live count, at the INPUT weights; iters = 0 returns only this (and info).
+ * scratch: fpcdr_landmark_expr_scratch_bytes(F, L, Kb) bytes (the landmark basis: 3 L Kb floats).  Kb <= 160 and L <= 512; anything larger,
+ * a negative or non-finite inv_c or ridge, a lambda0 that is not finite and positive, a misaligned buffer (4 bytes; normal_out 8) are errors
+ * before any launch.  The vertex ids are NOT checked on the device.                                                                    */
+size_t fpcdr_landmark_expr_scratch_bytes(int32_t F, int32_t L, int32_t Kb);
+int fpcdr_landmark_expr(const float *x /* [F,V,3] */, const float *mvp /* [F*Nc,4,4] */, const float *basis /* [3V,Kb] */,
+                        const int32_t *lm_vtx, const float *lm_bary, const float *lm_w /* [L] or NULL */, const float *obs /* [F*Nc,L,3] */,
+                        float *w /* [F,Kb] */, float inv_c /* 0: L2 */, float ridge, int32_t width, int32_t height, int32_t iters,
+                        float lambda0, float *info /* [F,4] */, double *normal_out /* or NULL */, void *scratch, size_t scratch_bytes,
+                        int32_t F, int32_t Nc, int32_t V, int32_t L, int32_t Kb, void *stream);
+
 /* The texture's prior ("Texture prior rule"), value and gradient in one call (two launches): smoothness over the pairs of
  * horizontally and vertically neighbouring texels -- none across the border -- and a hold to an anchor texture.
  *   s_pq = || t_p - t_q ||^2 over the C channels,   rho(s) = s  (inv_c = 0: L2)   or   2 s / (1 + sqrt(1 + s / c^2)),  c = 1 / inv_c
